@@ -1,6 +1,6 @@
 """bench.py -- Stage-I training rays/sec on MI355X (BASELINE.json metric).  One JSON line on rank 0.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--quick]]
         N = 1: runs in this process.  N > 1 without a torch.distributed environment: bench.py re-launches itself as
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
         (one rank per GPU over RCCL) and forwards the one JSON line; launched that way by the driver it just runs as a rank.
@@ -10,7 +10,11 @@ A step = one full training step of the GlossySynthetic 'bell' Stage-I shape conf
 (incl. the occlusion loss: schedule step 25000), backward including the second-order SDF term, flat RCCL gradient all-reduce,
 fused Adam.  Weak scaling: 4096 rays per rank.  Inputs are resident in HBM (device ray pool).
 
-Besides the contract fields the line carries: `roofline` (dominant MFMA kernel, live HIP-event timing), `protocol_8d` (SURVEY.md
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when --dump-outputs DIR is given (see
+dump_outputs: the inputs are seeded, so two builds can be compared output for output), and prints the line.  Everything else is
+measured only under --full (--full --quick: the roofline alone).
+
+With --full the line also carries: `roofline` (dominant MFMA kernel, live HIP-event timing), `protocol_8d` (SURVEY.md
 8d: median of >= 50 steps after >= 10 warm-up), `forward_only`, `f32_mfma_engine`, `stage2` (BASELINE configs[3]: P = 4096 surface
 points x 128+128 and the YAML default 512+256 MC directions), `reference_gpu_baseline` + `x_reference_gpu` (the UNMODIFIED reference
 -- oracle/_ref/, packaged by oracle/make_ref.py -- timed on the same MI355X by oracle/run_ref.py: the ">= 10x reference single-GPU
@@ -474,6 +478,24 @@ def dropin_trainer_bench(dev, cfg, rays, variance, step0=25000, warmup=5, steps=
                     'INTEGRATION.md option A (one batched weight-norm autograd node, the C step driver, the optimiser of torch)'}
 
 
+def dump_outputs(ts, info, out_dir):
+    """--dump-outputs: what the last timed step hands its caller, as DIR/<name>.npy (~18 MB for the bell model):
+        loss_terms     float32  the step's losses (total, rgb, eikonal, occlusion; the total alone where the step returns no terms)
+        sample_counts  float64  inner / outer samples of the step (n_in, n_out)
+        grad           float32  the flat gradient bucket the optimiser consumed (dL/dW_eff of every layer, the all-reduce payload)
+        params         float32  every parameter after the optimiser step, concatenated in named_parameters() order
+    The model, the ray pool and the per-step random draws are seeded (ShapeTrainStep), so the same arguments give the same inputs."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'loss_terms': info.get('loss_terms', info['loss']).detach().float().reshape(-1).cpu().numpy(),
+           'sample_counts': np.array([int(info['n_in']), int(info['n_out'])], dtype=np.float64),
+           'grad': ts.bucket.flat.detach().float().cpu().numpy(),
+           'params': torch.cat([p.detach().float().reshape(-1) for _, p in ts.net.named_parameters()]).cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a torch.distributed launcher: become the launcher"""
     if torch.cuda.device_count() < n:
@@ -495,7 +517,7 @@ def run_stage2(args, dev, rank, world, sync, max_over_ranks, rank_table=None):
     Dd, Ds = (int(x) for x in args.dirs.split('+'))
     P_ = args.points or (2048 if args.config == 'bear' else 4096)
     mesh = _bench_mesh()
-    r = stage2_step_bench(dev, args.config, P_, Dd, Ds, mesh, rank, world, args.warmup, args.steps, sync, max_over_ranks)
+    r = stage2_step_bench(dev, args.config, P_, Dd, Ds, mesh, rank, world, args.warmup, args.steps, sync, max_over_ranks, prof=args.full)
     ranks = rank_table(r['ms_per_step_this_rank']) if rank_table else {}
     if rank != 0:
         return
@@ -529,10 +551,17 @@ def main():
     ap.add_argument('--dirs', default='128+128', help='--stage 2: diffuse+specular MC directions (BASELINE configs[4]: 256+256)')
     ap.add_argument('--train-step', type=int, default=25000, help='training-schedule step the batch is evaluated at')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--quick', action='store_true', help='headline + roofline only (development runs)')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run every other measurement: protocol_8d, forward-only, the exact-f32 '
+                    'engine, the roofline, the small-batch / drop-in / inference / Stage-II legs and the torch, reference and CPU baselines')
+    ap.add_argument('--quick', action='store_true', help='with --full: headline + roofline only (development runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument('--dp-configs', action='store_true', help='N > 1 only: after the headline, also run BASELINE configs[2] (bear Stage I, 8192 rays '
                     'per global batch) and configs[4] (bear Stage II, 16384 points x 256+256) as data-parallel jobs of this world size')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.dump_outputs and args.stage != 1:
+        ap.error('--dump-outputs: Stage I (the headline step) only')
 
     if args.gpus > 1 and not all(k in os.environ for k in ('WORLD_SIZE', 'RANK', 'MASTER_ADDR', 'MASTER_PORT')):
         sys.exit(spawn_ranks(args.gpus))
@@ -611,10 +640,13 @@ def main():
     dt = max_over_ranks(dt_local)
     value = args.rays * world * args.steps / dt
     ranks = rank_table(dt_local / args.steps * 1e3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ts, info, args.dump_outputs)
+    extras = args.full and not args.quick          # --full: every measurement below; --full --quick: the roofline alone
 
     # ---- SURVEY.md 8d protocol: median of >= 50 steps (HIP events at the step boundaries) after >= 10 warm-up steps ------------
     proto = None
-    if not args.quick:
+    if extras:
         for i in range(max(0, 10 - args.warmup - args.steps)):
             ts.step(args.train_step + 500 + i)
         n8 = 50
@@ -633,7 +665,7 @@ def main():
     # ---- the same step on the exact-fp32 MFMA engine (NERO_GEMM=f32), reported next to the headline: 2 warmup + 5 timed steps --
     from nero_amd import chain as CH
     alt = None
-    if CH.GEMM_MODE['fwd'] != L.GEMM_F32 and not args.quick and world == 1:
+    if CH.GEMM_MODE['fwd'] != L.GEMM_F32 and extras and world == 1:
         saved = dict(CH.GEMM_MODE)
         CH.set_gemm_mode('f32')
         for i in range(2):
@@ -652,7 +684,7 @@ def main():
 
     # ---- forward-only (inference) rays/s on the default engines: 2 warmup + 5 timed renders --------------------
     fwd_only = None
-    if not args.quick:
+    if extras:
         for i in range(2):
             ts.forward_only(args.train_step + 400 + i)
         sync()
@@ -667,7 +699,7 @@ def main():
 
     # ---- roofline leg: per-launch HIP-event timing of the MFMA kernel classes, on extra (untimed) steps ------------
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         L.lib.nero_prof_enable(1)
         for i in range(3):
             ts.step(args.train_step + 100 + i)
@@ -709,7 +741,7 @@ def main():
             mb = mfma_busy_of(r[0])
             if mb:
                 pk['mfma_busy'] = mb['frac']
-    elif world > 1:
+    elif args.full and world > 1:
         for i in range(3):
             ts.step(args.train_step + 100 + i)
 
@@ -736,9 +768,10 @@ def main():
                        'fg_table': ('reference asset (' + os.path.relpath(os.environ['NERO_FG_LUT'], ROOT) + ')') if os.environ.get('NERO_FG_LUT') else 'computed fallback'},
             'step_mlp_flop_frac': round(flop_step / (dt / args.steps) / PEAK_OF_MODE[CH.GEMM_MODE['fwd']], 4),
             'step_mlp_flop_frac_of_f32_mfma_peak': round(flop_step / (dt / args.steps) / PEAK_F32_MFMA, 4),
-            'inner_samples_per_ray': round(n_in / args.steps / args.rays, 2),
-            'protocol_8d': proto, 'forward_only': fwd_only, 'roofline': roof, **ranks,
+            'inner_samples_per_ray': round(n_in / args.steps / args.rays, 2), **ranks,
         }
+        if args.full:
+            res.update(protocol_8d=proto, forward_only=fwd_only, roofline=roof)
         if alt is not None:
             res['f32_mfma_engine'] = alt
     del ts
@@ -758,7 +791,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    if world > 1 and args.dp_configs and not args.quick:
+    if world > 1 and args.dp_configs and extras:
         # (opt-in: an exception on ONE rank inside an extra collective leg would leave the others waiting in an all-reduce, and the
         # headline line of a scaling run must not depend on that)
         # BASELINE configs[2] and configs[4] as data-parallel jobs of THIS world size (every rank takes part; rank 0 reports):
@@ -782,7 +815,7 @@ def main():
         leg('configs4_bear_stage2_16384_points_dp',
             lambda: stage2_step_bench(dev, 'bear', max(64, 16384 // world), 256, 256, _bench_mesh(), rank, world, 5, 20, sync, max_over_ranks, prof=False))
     if rank == 0:
-        if world == 1 and not args.quick:          # (baselines, the small-batch / drop-in legs and the Stage-II legs: rank 0 at N = 1 only)
+        if world == 1 and extras:          # (baselines, the small-batch / drop-in legs and the Stage-II legs: rank 0 at N = 1 only)
             def r512():
                 # (60 steps after 8: a 20-step sample of a 5 ms step is 0.1 s and scatters by +- 4 % from run to run -- scripts/r06/dropin_ab2.py)
                 t5 = ShapeTrainStep(cfg, rays_per_rank=512, device=dev, variance=VARIANCE, prime_fraction=0.0)

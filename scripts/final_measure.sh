@@ -15,7 +15,7 @@ timeout 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/step -o step --o
 timeout 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/stage2 -o stage2 --output-format csv -- python scripts/bench_material_step.py 4096 128 128 7 bell fused > $O/stage2.log 2>&1
 find gpurun_out/prof/step -name "*kernel_stats.csv" -exec cp {} $O/step_kernel_stats.csv \;
 find gpurun_out/prof/stage2 -name "*kernel_stats.csv" -exec cp {} $O/stage2_kernel_stats.csv \;
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -1 $O/bench.json | cut -c1-400
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -1 $O/bench.json | cut -c1-400
 timeout 200 python scripts/trace_bench.py $O/trace_bench.json > $O/trace_bench.log 2>&1
 timeout 100 python scripts/bench_head_dw.py > $O/head_dw.txt 2>&1; cat $O/head_dw.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log

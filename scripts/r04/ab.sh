@@ -9,7 +9,7 @@ run() {
   [[ "$spec" == *:* ]] && envs=$(echo "${spec#*:}" | tr ',' ' ')
   [[ "$lib" != "-" ]] && envs="$envs NERO_HIP_LIB=$PWD/build/variants/lib_$lib.so"
   echo "== $spec" | tee -a $OUT
-  env $envs timeout 300 python bench.py --quick --steps ${STEPS:-16} --warmup 4 ${BENCH_ARGS} 2>&1 | tail -1 | python -c "
+  env $envs timeout 300 python bench.py --full --quick --steps ${STEPS:-16} --warmup 4 ${BENCH_ARGS} 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], {k[:3]: v['ms_per_step'] for k, v in d.get('roofline',{}).get('per_kernel',{}).items()})

@@ -8,7 +8,7 @@ OUT=gpurun_out/r04/exp1.txt
 run() {   # label, env...
   local label=$1; shift
   echo "== $label" | tee -a $OUT
-  env "$@" timeout 300 python bench.py --quick --steps 16 --warmup 4 2>&1 | tail -1 | python -c "
+  env "$@" timeout 300 python bench.py --full --quick --steps 16 --warmup 4 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'], {k: v['ms_per_step'] for k, v in d.get('roofline',{}).get('per_kernel',{}).items()})

@@ -27,8 +27,8 @@ for tag in step:"bench.py --quick" r512:"scripts/step_times.py 512 30" stage2:"s
   if [ $n = step ]; then find gpurun_out/prof/$n -name "*kernel_trace.csv" -exec python scripts/gap_analysis.py {} \; > $O/gap_analysis.txt 2>&1; fi
 done
 unset NERO_STREAMS
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -1 $O/bench.json | cut -c1-300
-timeout 300 python bench.py --stage 2 > $O/bench_stage2.json 2>> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -1 $O/bench.json | cut -c1-300
+timeout 300 python bench.py --full --stage 2 > $O/bench_stage2.json 2>> $O/bench.err
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 rm -rf gpurun_out/prof/*/*.db gpurun_out/prof/*/*kernel_trace.csv gpurun_out/prof/*/*/*.db gpurun_out/prof/*/*/*kernel_trace.csv gpurun_out/prof/fetch* gpurun_out/prof/write* gpurun_out/prof/step gpurun_out/prof/r512 gpurun_out/prof/stage2
 ls -la $O | head -30; tail -3 $O/bench.err

@@ -1,6 +1,9 @@
 """CPU tier: the drop-in renderers accept every YAML the reference ships (config surface) and expose the
-reference's parameter names.  Skipped when the reference tree is not mounted (GPU box)."""
+reference's parameter names.  The YAMLs and the reference variance network's outputs are fixtures taken from the unmodified
+reference by oracle/gen_golden_configs.py (tests/golden/configs/, tests/golden/ref_std_act.json), so the checks run everywhere;
+where the reference tree is mounted its own YAMLs are checked as well, each against its fixture byte for byte."""
 import glob
+import json
 import os
 
 import pytest
@@ -8,12 +11,24 @@ import torch
 import yaml
 
 REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'configs')), reason='reference tree not available')
+needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'configs')), reason='reference tree not available')
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+CONFIGS = os.path.join(GOLDEN, 'configs')
 
 
-@pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(REF, 'configs', 'shape', '*', '*.yaml')) +
-                                        glob.glob(os.path.join(REF, 'configs', 'custom', '*shape*.yaml'))))
-def test_shape_yaml_constructs(path):
+def _fixtures(*patterns):
+    """parametrise over the config fixtures; ids relative to tests/golden/configs/, the same on every machine"""
+    paths = sorted(p for pat in patterns for p in glob.glob(os.path.join(CONFIGS, pat)))
+    assert paths, f'no config fixtures under {CONFIGS} match {patterns}'
+    return pytest.mark.parametrize('path', paths, ids=[os.path.relpath(p, CONFIGS) for p in paths])
+
+
+def _same_as_fixture(path):
+    fixture = os.path.join(CONFIGS, os.path.relpath(path, os.path.join(REF, 'configs')))
+    assert open(fixture, 'rb').read() == open(path, 'rb').read(), fixture
+
+
+def _shape_constructs(path):
     from nero_amd.renderer import name2renderer
     cfg = yaml.load(open(path), Loader=yaml.FullLoader)
     net = name2renderer[cfg['network']](cfg, training=False)
@@ -26,9 +41,7 @@ def test_shape_yaml_constructs(path):
     assert n_params == (2346073 if cfg.get('shader_config', {}).get('human_light', False) else 2206289)
 
 
-@pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(REF, 'configs', 'material', '*', '*.yaml')) +
-                                        glob.glob(os.path.join(REF, 'configs', 'custom', '*material*.yaml'))))
-def test_material_yaml_constructs(path):
+def _material_constructs(path):
     from nero_amd.renderer import name2renderer
     from nero_amd.synthetic import icosphere
     cfg = yaml.load(open(path), Loader=yaml.FullLoader)
@@ -42,17 +55,41 @@ def test_material_yaml_constructs(path):
     assert n_params == (1561886 if (human and cfg['shader_cfg']['outer_light_version'] == 'sphere_direction') else 1403670), n_params
 
 
+@needs_ref
+@pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(REF, 'configs', 'shape', '*', '*.yaml')) +
+                                        glob.glob(os.path.join(REF, 'configs', 'custom', '*shape*.yaml'))))
+def test_shape_yaml_constructs(path):
+    _shape_constructs(path)
+    _same_as_fixture(path)
+
+
+@_fixtures('shape/*/*.yaml', 'custom/*shape*.yaml')
+def test_shape_yaml_fixture_constructs(path):
+    _shape_constructs(path)
+
+
+@needs_ref
+@pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(REF, 'configs', 'material', '*', '*.yaml')) +
+                                        glob.glob(os.path.join(REF, 'configs', 'custom', '*material*.yaml'))))
+def test_material_yaml_constructs(path):
+    _material_constructs(path)
+    _same_as_fixture(path)
+
+
+@_fixtures('material/*/*.yaml', 'custom/*material*.yaml')
+def test_material_yaml_fixture_constructs(path):
+    _material_constructs(path)
+
+
 @pytest.mark.parametrize('act', ['exp', 'linear', 'square'])
 def test_std_act_matches_the_reference_variance_network(act):
-    """std_act (network/field.py:184-198) -- the reference class under the import shim against the drop-in module, the oracle's
-    restatement, and the log-domain scalar the HIP kernels are handed (they form exp(10 v'))"""
-    from oracle import ref_shim
+    """std_act (network/field.py:184-198) -- the reference class's outputs (recorded under the import shim) against the drop-in module,
+    the oracle's restatement, and the log-domain scalar the HIP kernels are handed (they form exp(10 v'))"""
     from oracle import nero_oracle as O
     from nero_amd.fields import SingleVarianceNetwork
-    _, field = ref_shim.load_reference()
+    ref = json.load(open(os.path.join(GOLDEN, 'ref_std_act.json')))[act]
     for v in (0.3, 0.07, 2.0):
-        ref = field.SingleVarianceNetwork(v, act)
-        want = float(ref(torch.zeros(1, 3))[0, 0])
+        want = ref[repr(v)]
         mine = SingleVarianceNetwork(v, act)
         assert abs(float(mine.inv_s()) - want) <= 1e-6 * abs(want)
         assert abs(float(O.deviation_inv_s({'deviation_network.variance': torch.tensor(v)}, act)) - want) <= 1e-6 * abs(want)
