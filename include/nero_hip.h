@@ -637,6 +637,33 @@ int nero_stage2_shade_bwd(nero_stage2* h, const float* d_rgb, const float* d_dl,
 /* d_raw5 [n,5] -> dW / db of the feats network and the material predictors (entries 0..19) */
 int nero_stage2_predict_bwd(nero_stage2* h, const float* d_raw5, const nero_stage2_grads* grads, void* stream);
 
+/* ---- marching cubes: Stage-I SDF grid -> triangle mesh (nero_amd/csrc/mcubes.hip) -----------------------------------------------------
+ * Replaces `vertices, triangles = mcubes.marching_cubes(u, threshold)` (PyMCubes, network/field.py:1110-1117, called from extract_mesh.py:24-31),
+ * the step between Stage I and Stage II.
+ *   u [nx][ny][nz] fp32, contiguous, z fastest (NeROShapeRenderer.extract_fields' layout); any nx, ny, nz >= 1 with nx*ny*nz < 2^32 (1024^3 is
+ *   2^30).  A grid with fewer than 2 points on an axis has no cell: the empty mesh, NERO_OK.
+ *   Inside: corner c is "below" when u < threshold (strict); cube index bit c = corner c below.  Corners (x,y,z index offsets) 0:(0,0,0)
+ *   1:(1,0,0) 2:(1,1,0) 3:(0,1,0) 4:(0,0,1) 5:(1,0,1) 6:(1,1,1) 7:(0,1,1); edges 0:(0,1) 1:(1,2) 2:(2,3) 3:(3,0) 4:(4,5) 5:(5,6) 6:(6,7)
+ *   7:(7,4) 8:(0,4) 9:(1,5) 10:(2,6) 11:(3,7); Paul Bourke's triangle table (nero_amd/csrc/mcubes_tables.h).
+ *   Orientation: cross(v_b - v_a, v_c - v_a) of a triangle (a,b,c) points into u < threshold -- for an SDF, inward (the winding the reference's
+ *   Stage II expects: NeROMaterialRenderer.trace flips the tracer's face normals, network/renderer.py:719-723).
+ *   Vertices: one per grid edge whose endpoints straddle the threshold, float32 [V,3] in index space; the edge from point a to a + e_axis
+ *   gives a + t e_axis, t = (threshold - u_a) / (u_b - u_a) in fp32, t in [0, 1].  Order: (linear index (i*ny + j)*nz + k of a, axis x<y<z).
+ *   Triangles: int32 [T,3] vertex ids, ordered by (linear index of the cell's min corner, position in the table).  Fixed by prefix sums,
+ *   not atomics: independent of the launch shape, bit-identical run to run.  NaN / inf in u: never a fault or a write out of range;
+ *   such cells give some deterministic mesh.
+ * nero_mcubes_workspace_bytes: the workspace both calls share: 5 bytes per grid point + 32 bytes per 2048 points + the scan's scratch
+ *   (< 6 nx*ny*nz + 64 KiB; 256 bytes for a grid without cells; 0 for a grid the calls refuse).
+ * nero_mcubes_count: -> totals [2] (device int64) = {V, T}, also kept in the workspace for nero_mcubes_emit.
+ * nero_mcubes_emit: same u, sizes, threshold and workspace as the count before it -> verts [V,3], tris [T,3].  Before any launch it reads
+ *   the 16-byte totals back from the workspace -- the one synchronisation of these calls, on `stream` -- and fails (nothing written) when
+ *   V > v_cap or T > t_cap (NERO_ERR_ARG) or V or T >= 2^31 (NERO_ERR_UNSUPPORTED); every store is also bounded by v_cap / t_cap on the
+ *   device. */
+size_t nero_mcubes_workspace_bytes(int nx, int ny, int nz);
+int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, void* ws, int64_t* totals /*device, {V, T}*/, void* stream);
+int nero_mcubes_emit(const float* u, int nx, int ny, int nz, float threshold, void* ws, float* verts, int64_t v_cap, int* tris, int64_t t_cap,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

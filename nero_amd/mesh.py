@@ -1,0 +1,196 @@
+"""Marching cubes on the device (libnero_hip.so, nero_mcubes_*) and PLY mesh IO: the Stage-I -> Stage-II handoff without third-party packages.
+
+The reference extracts the Stage-I mesh with PyMCubes (`mcubes.marching_cubes`, network/field.py:1110-1117, extract_mesh.py:24-31) and writes /
+reads it with trimesh (extract_mesh.py:34-37, network/renderer.py:704).  This module provides both:
+  * marching_cubes_device(u, threshold): the HIP kernels on a CUDA grid -> device tensors;
+  * marching_cubes(volume, isovalue): PyMCubes' signature on numpy arrays, so `sys.modules['mcubes'] = nero_amd.mesh` runs the reference's own
+    extract_geometry / extract_mesh.py unmodified;
+  * write_ply / read_ply: the binary PLY the reference's Stage II reads (`cfg['mesh']`).
+Conventions (include/nero_hip.h): a corner is inside when u < threshold; vertices are index-space, one per crossing grid edge, ordered by
+(linear grid index, axis x<y<z); triangles are ordered by (cell, table position) and wound so that their normals point into u < threshold --
+inward for an SDF, which NeROMaterialRenderer.trace flips to outward shading normals."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+_INT31 = 1 << 31
+
+L.lib.nero_mcubes_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mcubes_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+L.lib.nero_mcubes_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+L.lib.nero_mcubes_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_int64, C.c_void_p]
+
+
+def workspace_bytes(shape):
+    """device bytes nero_mcubes_count / _emit need beside the grid (< 6 bytes per grid point + 64 KiB)"""
+    nx, ny, nz = (int(s) for s in shape)
+    return int(L.lib.nero_mcubes_workspace_bytes(nx, ny, nz))
+
+
+def marching_cubes_device(u, threshold=0.0):
+    """u: CUDA float32 [nx, ny, nz] (x, y, z order, z fastest: NeROShapeRenderer's grid) -> (verts float32 [V,3] in index space,
+    tris int32 [T,3]) on u's device.  One readback of the 16-byte totals between the two launches sizes the outputs exactly."""
+    if not (torch.is_tensor(u) and u.is_cuda and u.dtype == torch.float32 and u.dim() == 3):
+        raise TypeError(f'marching_cubes_device wants a CUDA float32 [nx, ny, nz] tensor, got '
+                        f'{tuple(u.shape) if torch.is_tensor(u) else type(u).__name__} {getattr(u, "dtype", "")}')
+    u = u.contiguous()
+    nx, ny, nz = u.shape
+    dev = u.device
+    need = workspace_bytes(u.shape)
+    if need == 0:
+        raise ValueError(f'marching_cubes_device: grid {nx} x {ny} x {nz} is not supported (every size >= 1, fewer than 2^32 points)')
+    L.check_workspace_fits(need, dev, what='marching-cubes workspace')
+    with torch.cuda.device(dev):
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        s = L.stream_ptr()
+        L.check(L.lib.nero_mcubes_count(L.ptr(u), nx, ny, nz, float(threshold), L.ptr(ws), L.ptr(totals), s))
+        V, T = (int(x) for x in totals.tolist())
+        if V >= _INT31 or T >= _INT31:
+            raise L.NeroHipError(f'marching_cubes_device: {V} vertices / {T} triangles: the int32 triangle ids cannot hold them')
+        L.check_workspace_fits(12 * (V + T), dev, what='marching-cubes mesh')
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        L.check(L.lib.nero_mcubes_emit(L.ptr(u), nx, ny, nz, float(threshold), L.ptr(ws), L.ptr(verts) if V else None, V,
+                                       L.ptr(tris) if T else None, T, s))
+    return verts, tris
+
+
+def marching_cubes(volume, isovalue):
+    """PyMCubes' `mcubes.marching_cubes(volume, isovalue)`: numpy [nx, ny, nz] -> (vertices float64 [V,3] in index space, triangles int64
+    [T,3]), computed on the current CUDA device.  The volume is evaluated in float32 (the reference's grid is float32 already:
+    extract_fields, network/field.py:1096)."""
+    vol = torch.from_numpy(np.ascontiguousarray(np.asarray(volume), dtype=np.float32))
+    v, f = marching_cubes_device(vol.cuda(), float(isovalue))
+    return v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(np.int64)
+
+
+def index_to_world(verts, resolution, bound_min, bound_max):
+    """the reference's mapping of index-space vertices to the box (network/field.py:1114-1116), in float64 on the host"""
+    bmin = np.asarray(bound_min.detach().cpu().numpy() if torch.is_tensor(bound_min) else bound_min)
+    bmax = np.asarray(bound_max.detach().cpu().numpy() if torch.is_tensor(bound_max) else bound_max)
+    v = np.asarray(verts, dtype=np.float64)
+    return v / (resolution - 1.0) * (bmax - bmin)[None, :] + bmin[None, :]
+
+
+# ---- PLY --------------------------------------------------------------------------------------------------------------------------------
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def write_ply(path, v, f):
+    """binary little-endian PLY: `float x, y, z` per vertex, `list uchar int vertex_indices` per face (what trimesh writes for a mesh
+    without attributes, extract_mesh.py:37)"""
+    v = np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype='<f4').reshape(-1, 3)
+    f = np.asarray(f.detach().cpu().numpy() if torch.is_tensor(f) else f).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError('write_ply: a face index is out of range')
+    faces = np.empty(len(f), dtype=[('n', 'u1'), ('idx', '<i4', (3,))])
+    faces['n'] = 3
+    faces['idx'] = f
+    head = (f'ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n'
+            f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
+    with open(path, 'wb') as fh:
+        fh.write(head.encode('ascii'))
+        fh.write(v.tobytes())
+        fh.write(faces.tobytes())
+
+
+def _read_header(fh):
+    if fh.readline().strip() != b'ply':
+        raise ValueError('read_ply: not a PLY file')
+    fmt, elements = None, []
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError('read_ply: the header has no end_header')
+        tok = line.decode('ascii', 'replace').split()
+        if not tok or tok[0] in ('comment', 'obj_info'):
+            continue
+        if tok[0] == 'end_header':
+            return fmt, elements
+        if tok[0] == 'format':
+            fmt = tok[1]
+        elif tok[0] == 'element':
+            elements.append({'name': tok[1], 'count': int(tok[2]), 'props': []})
+        elif tok[0] == 'property':
+            if not elements:
+                raise ValueError('read_ply: a property before any element')
+            if tok[1] == 'list':
+                elements[-1]['props'].append((tok[4], 'list', _ply_type(tok[2]), _ply_type(tok[3])))
+            else:
+                elements[-1]['props'].append((tok[2], _ply_type(tok[1])))
+
+
+def _ply_type(name):
+    if name not in _PLY_TYPES:
+        raise ValueError(f'read_ply: unknown property type {name!r}')
+    return _PLY_TYPES[name]
+
+
+def _triangles(counts, where):
+    bad = np.nonzero(np.asarray(counts) != 3)[0]
+    if bad.size:
+        raise ValueError(f'read_ply: face {int(bad[0])} of {where} has {int(np.asarray(counts)[bad[0]])} vertices; only triangle meshes are '
+                         f'supported')
+
+
+def read_ply(path):
+    """-> (vertices float64 [V,3], faces int64 [T,3]).  binary_little_endian or ascii; float or double x, y, z, other vertex properties
+    (normals, colours, ...) skipped; faces must be triangles.  Big-endian files and polygon faces raise ValueError."""
+    with open(path, 'rb') as fh:
+        fmt, elements = _read_header(fh)
+        if fmt == 'binary_big_endian':
+            raise ValueError(f'read_ply: {os.path.basename(path)} is big-endian; only binary_little_endian and ascii PLY are supported')
+        if fmt not in ('binary_little_endian', 'ascii'):
+            raise ValueError(f'read_ply: unknown format {fmt!r}')
+        body = fh.read()
+    verts = faces = None
+    if fmt == 'ascii':
+        lines = body.decode('ascii').split('\n')
+        at = 0
+        for el in elements:
+            rows = [ln.split() for ln in lines[at:at + el['count']]]
+            at += el['count']
+            if el['name'] == 'vertex':
+                cols = [p[0] for p in el['props']]
+                if any(p[1] == 'list' for p in el['props']):
+                    raise ValueError('read_ply: list properties on vertices are not supported')
+                a = np.array(rows, dtype=np.float64).reshape(el['count'], len(cols))
+                verts = a[:, [cols.index(c) for c in 'xyz']]
+            elif el['name'] == 'face':
+                if el['props'][0][1] != 'list':
+                    raise ValueError('read_ply: the face element has no leading vertex-index list')
+                _triangles([int(r[0]) for r in rows], path)
+                faces = np.array([r[1:4] for r in rows], dtype=np.int64).reshape(el['count'], 3)
+    else:
+        at = 0
+        for el in elements:
+            if el['name'] == 'face':
+                p0 = el['props'][0]
+                if p0[1] != 'list' or any(p[1] == 'list' for p in el['props'][1:]):
+                    raise ValueError('read_ply: faces must be one leading vertex-index list plus scalar properties')
+                # one record per triangle: count, three indices, the remaining scalar properties
+                dt = np.dtype([('n', '<' + p0[2]), ('idx', '<' + p0[3], (3,))] + [(p[0], '<' + p[1]) for p in el['props'][1:]])
+                rec = np.frombuffer(body, dtype=dt, count=el['count'], offset=at) if el['count'] else np.zeros(0, dt)
+                _triangles(rec['n'], path)                # (the first polygon's count is read at its true position: all before it were triangles)
+                faces = rec['idx'].astype(np.int64)
+                at += dt.itemsize * el['count']
+            else:
+                if any(p[1] == 'list' for p in el['props']):
+                    raise ValueError(f'read_ply: list properties on element {el["name"]!r} are not supported in binary files')
+                dt = np.dtype([(p[0], '<' + p[1]) for p in el['props']])
+                rec = np.frombuffer(body, dtype=dt, count=el['count'], offset=at) if el['count'] else np.zeros(0, dt)
+                if el['name'] == 'vertex':
+                    verts = np.stack([rec[c].astype(np.float64) for c in 'xyz'], -1).reshape(el['count'], 3)
+                at += dt.itemsize * el['count']
+    if verts is None or faces is None:
+        raise ValueError(f'read_ply: {os.path.basename(path)} has no vertex or no face element')
+    if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError('read_ply: a face index is out of range')
+    return verts, faces

@@ -220,6 +220,21 @@ class NeROShapeRenderer(nn.Module):
     def extract_fields(self, bound_min=(-1., -1., -1.), bound_max=(1., 1., 1.), resolution=512, chunk=2 ** 21, outside_val=1.0):
         """SDF on a resolution^3 grid for marching cubes (extract_fields, network/field.py:1090-1108; used by extract_mesh.py:24-27):
         value-only SDF chain, points outside the unit sphere set to `outside_val`.  -> float32 numpy [res,res,res] (x,y,z order)"""
+        return self._sdf_grid(bound_min, bound_max, resolution, chunk, outside_val).cpu().numpy()
+
+    def extract_geometry(self, bound_min=(-1., -1., -1.), bound_max=(1., 1., 1.), resolution=512, threshold=0.0, outside_val=1.0):
+        """the Stage-I mesh (extract_geometry, network/field.py:1110-1117; extract_mesh.py:24-31): the extract_fields grid, kept on the
+        device, through the HIP marching cubes (nero_amd.mesh), mapped to the box in float64 as the reference does.  Only the mesh is copied
+        to the host.  -> (vertices float64 [V,3], triangles int64 [T,3]), wound inward (normals towards sdf < threshold), the winding
+        NeROMaterialRenderer(cfg, mesh=...) expects"""
+        from . import mesh as M
+        u = self._sdf_grid(bound_min, bound_max, resolution, 2 ** 21, outside_val)
+        v, f = M.marching_cubes_device(u, threshold)
+        del u
+        return M.index_to_world(v.cpu().numpy(), resolution, bound_min, bound_max), f.cpu().numpy().astype(np.int64)
+
+    def _sdf_grid(self, bound_min, bound_max, resolution, chunk, outside_val):
+        """extract_fields' grid on the device: float32 [res,res,res] (x,y,z order)"""
         dev = next(self.parameters()).device
         with torch.no_grad():
             _, _, K = self._kernels()
@@ -232,7 +247,7 @@ class NeROShapeRenderer(nn.Module):
                 pts = torch.stack([axes[0][ix], axes[1][iy], axes[2][iz]], -1).contiguous()
                 val = K.sdf.sdf(pts)[:, 0]
                 u[i:i + idx.numel()] = torch.where(torch.norm(pts, dim=-1) >= 1.0, torch.full_like(val, outside_val), val)
-        return u.reshape(resolution, resolution, resolution).cpu().numpy()
+        return u.reshape(resolution, resolution, resolution)
 
     def nvs(self, pose, K, h, w):
         """network/renderer.py:189-222 -> [h,w,3] numpy image"""
@@ -505,9 +520,14 @@ class NeROMaterialRenderer(nn.Module):
             try:
                 import trimesh
             except ImportError as e:
-                raise ImportError('pass mesh=(vertices, triangles) or install trimesh to read cfg["mesh"]') from e
-            tm = trimesh.load(self.cfg['mesh'], force='mesh', skip_material=True, process=False)
-            mesh = (np.asarray(tm.vertices), np.asarray(tm.faces))
+                # a .ply (what extract_mesh.py and nero_amd.mesh.write_ply write) is read without trimesh
+                if not str(self.cfg['mesh']).lower().endswith('.ply'):
+                    raise ImportError('pass mesh=(vertices, triangles), give cfg["mesh"] as a .ply, or install trimesh to read cfg["mesh"]') from e
+                from .mesh import read_ply
+                mesh = read_ply(self.cfg['mesh'])
+            else:
+                tm = trimesh.load(self.cfg['mesh'], force='mesh', skip_material=True, process=False)
+                mesh = (np.asarray(tm.vertices), np.asarray(tm.faces))
         self.ray_tracer = RayTracer(mesh[0], mesh[1])
         self.cfg['shader_cfg'] = dict(self.cfg['shader_cfg'])
         self.cfg['shader_cfg']['is_real'] = self.cfg['database_name'].startswith('real')
