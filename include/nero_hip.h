@@ -664,6 +664,52 @@ int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, v
 int nero_mcubes_emit(const float* u, int nx, int ny, int nz, float threshold, void* ws, float* verts, int64_t v_cap, int* tris, int64_t t_cap,
                      void* stream);
 
+/* ---- geometry evaluation: Chamfer distance of the extracted mesh (nero_amd/csrc/geom_eval.hip) --------------------------------------------
+ * The reference's only geometry metric (eval_synthetic_shape.py, eval_real_shape.py, eval.md) without nvdiffrast / open3d / trimesh.  No
+ * atomics decide a value or a position: every result is bit-identical run to run.  Host counterpart: nero_amd/eval_shape.py.
+ *
+ * nero_nn_dist -- `nearest_dist` (eval_synthetic_shape.py:16-25): exact brute-force nearest neighbour.  q [nq,3], r [nr,3] fp32;
+ *   dist [nq] = sqrt(min_j d2(i,j)), d2 = fma(dz,dz, fma(dy,dy, dx*dx)) with dx = q_x - r_x ... formed first, all fp32 (within 4 * 2^-24 relative of
+ *   the float64 distance of the same inputs); idx [nq] int32 or NULL = the j of the minimum, the lowest j among equal fp32 d2.  nq = 0: no-op;
+ *   nr = 0: NERO_ERR_ARG; nr >= 2^31 with idx: NERO_ERR_UNSUPPORTED.  `splits`: over how many workgroups the reference set is divided (a second
+ *   pass takes the minimum); 0 = chosen from the sizes (nero_nn_dist_splits) so that a 50 k x 50 k call fills 256 CUs; at most 4096.  The result
+ *   does not depend on it.  ws: nero_nn_dist_workspace_bytes(nq, nr, splits) bytes (8 bytes per query and split; 0 = refused arguments).
+ *
+ * nero_voxel_downsample -- open3d `voxel_down_sample` (eval_synthetic_shape.py:79-82, dataset/database.py:451-456), whose output order is
+ *   unspecified, made deterministic.  pts [n,3] fp32; origin o = min(pts) - voxel / 2 per axis; voxel index floor((p - o) / voxel) per axis in
+ *   float64; the points are ordered by a stable radix sort of the key ix << 42 | iy << 21 | iz; out [n_out,3] = for each occupied voxel in
+ *   ascending key order the float64 sum of its points in ascending input index, divided by their count, stored as fp32.  n_out: device int64 (may
+ *   be NULL).  The call reads the count back on `stream` (its one synchronisation, as nero_mcubes_emit) before it writes: more voxels than
+ *   out_cap is NERO_ERR_ARG with nothing written; a cloud spanning more than 2^21 voxels on an axis, or holding a non-finite coordinate, is
+ *   NERO_ERR_UNSUPPORTED; n >= 2^31 - 1 likewise.  n = 0: n_out = 0.  ws: nero_voxel_downsample_workspace_bytes(n) (about 24 bytes per point +
+ *   the sort's scratch).
+ *
+ * nero_view_rays -- primary rays of one view through the pixel centres (x + 0.5, y + 0.5): rays_o [h*w,3] = the camera centre -R^T t, rays_d
+ *   [h*w,3] = normalised R^T inv(K) (x + 0.5, y + 0.5, 1), row-major pixels.  K [9], pose [12] = [R|t] world -> camera: HOST doubles, row-major.
+ * nero_view_points -- t [h*w] = the hit distances nero_bvh_trace returns for those rays (`depth` output; a miss is 10) -> depth [h*w] fp32
+ *   camera-space z = t * d_z / |d| for the pixel's inv(K) direction d (0 where missed), mask [h*w] bytes = t < 10, and pts = the masked pixels
+ *   back-projected to the world exactly as mask_depth_to_pts + pose_inverse + pose_apply do (utils/base_utils.py:44-52, 562-565, 583-584): pixel
+ *   coordinates and depth float32, (x + off) * z and (y + off) * z float32 products, then float64: (xz, yz, z) inv(K)^T R + c, stored fp32 in row-major
+ *   pixel order at positions fixed by a prefix sum.  unproject_offset = 0 is the reference (integer pixel coordinates: a half-pixel quirk its
+ *   ground-truth points share); 0.5 puts the points on the rays they were traced along.  n_pts: device int64, the number of masked pixels;
+ *   no store past pts_cap points.  Together these stand in for rasterize_depth_map (eval_synthetic_shape.py:39-60).  DEVIATION: the depth is ray
+ *   cast through pixel centres; nvdiffrast rasterises (screen-affine z, top-left fill rule), so boundary pixels and the depth inside a triangle
+ *   can differ.  That difference is not measured: nvdiffrast is not available to this project.
+ * nero_depth_points -- the same back-projection of a given depth map + mask (ground truth: database.get_depth, dataset/database.py:443-449).
+ *   ws of both: nero_view_points_workspace_bytes(h, w). */
+int nero_nn_dist_splits(int64_t nq, int64_t nr);
+size_t nero_nn_dist_workspace_bytes(int64_t nq, int64_t nr, int splits);
+int nero_nn_dist(const float* q, int64_t nq, const float* r, int64_t nr, void* ws, int splits, float* dist, int* idx /*or NULL*/, void* stream);
+size_t nero_voxel_downsample_workspace_bytes(int64_t n);
+int nero_voxel_downsample(const float* pts, int64_t n, double voxel, void* ws, float* out, int64_t out_cap, int64_t* n_out /*device*/,
+                          void* stream);
+int nero_view_rays(const double* K /*host [9]*/, const double* pose /*host [12]*/, int h, int w, float* rays_o, float* rays_d, void* stream);
+size_t nero_view_points_workspace_bytes(int h, int w);
+int nero_view_points(const float* t, const double* K /*host*/, const double* pose /*host*/, int h, int w, float unproject_offset, void* ws,
+                     float* depth, unsigned char* mask, float* pts, int64_t pts_cap, int64_t* n_pts /*device*/, void* stream);
+int nero_depth_points(const float* depth, const unsigned char* mask, const double* K /*host*/, const double* pose /*host*/, int h, int w,
+                      float unproject_offset, void* ws, float* pts, int64_t pts_cap, int64_t* n_pts /*device*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,73 @@
+"""Chamfer distance of an extracted mesh on the GPU (nero_amd/eval_shape.py), the reference's two procedures:
+
+    python scripts/eval_shape.py --pr A.ply --gt B.ply
+        eval_real_shape.py: nearest distances between the vertices (or points) of two PLY files.
+    python scripts/eval_shape.py --mesh M.ply --views views.npz (--gt-points P.ply | --gt-depths D.npz)
+        eval_synthetic_shape.py: the mesh's depth map in every view of views.npz (poses [n,3,4] world -> camera, Ks [n,3,3], hw [n,2]),
+        back-projected and voxel-down-sampled, against the ground-truth points (the data set's eval_pts.ply) or the points made the same way
+        from ground-truth depth maps (D.npz: depths [n,h,w], masks [n,h,w]).
+
+Prints `<stem> <chamfer:.5f>` as the reference does.  Loading a data set's images and poses is not part of this project."""
+import argparse
+import os
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--pr', type=str, help='predicted mesh or point cloud (PLY)')
+    ap.add_argument('--gt', type=str, help='ground-truth mesh or point cloud (PLY)')
+    ap.add_argument('--mesh', type=str, help='extracted mesh (PLY) for the synthetic procedure')
+    ap.add_argument('--views', type=str, help='npz with poses [n,3,4], Ks [n,3,3], hw [n,2]')
+    ap.add_argument('--gt-points', type=str, help='ground-truth eval points (PLY)')
+    ap.add_argument('--gt-depths', type=str, help='npz with depths [n,h,w] and masks [n,h,w]')
+    ap.add_argument('--voxel-size', type=float, default=0.01)
+    ap.add_argument('--unproject-offset', type=float, default=0.0,
+                    help='0 = the reference (integer pixel coordinates), 0.5 = through the pixel centres')
+    ap.add_argument('--batch_size', type=int, default=None, help='accepted for compatibility with the reference; nothing is batched')
+    a = ap.parse_args(argv)
+    real, syn = a.pr is not None or a.gt is not None, a.mesh is not None or a.views is not None
+    if real == syn:
+        ap.error('choose one procedure: --pr A.ply --gt B.ply, or --mesh M.ply --views views.npz with a ground truth')
+    if real and (a.pr is None or a.gt is None):
+        ap.error('the real-shape procedure needs both --pr and --gt')
+    if syn:
+        if a.mesh is None or a.views is None:
+            ap.error('the synthetic procedure needs both --mesh and --views')
+        if (a.gt_points is None) == (a.gt_depths is None):
+            ap.error('the synthetic procedure needs one ground truth: --gt-points P.ply or --gt-depths D.npz')
+    return a
+
+
+def main(argv=None):
+    a = parse(argv)
+    for path in (a.pr, a.gt, a.mesh, a.views, a.gt_points, a.gt_depths):
+        if path is not None and not os.path.exists(path):
+            sys.exit(f'eval_shape: {path} does not exist')
+    from nero_amd import eval_shape as E
+    from nero_amd import mesh as M
+    if a.pr is not None:
+        stem = Path(a.pr).stem
+        chamfer = E.eval_point_clouds(E.read_ply_points(a.pr), E.read_ply_points(a.gt))
+    else:
+        stem = Path(a.mesh).stem
+        v, f = M.read_ply(a.mesh)
+        views = np.load(a.views)
+        kw = dict(voxel_size=a.voxel_size, unproject_offset=a.unproject_offset)
+        if a.gt_points is not None:
+            kw['gt_points'] = E.read_ply_points(a.gt_points)
+        else:
+            gt = np.load(a.gt_depths)
+            kw['gt_depths'], kw['gt_masks'] = gt['depths'], gt['masks']
+        chamfer = E.eval_mesh(v, f, views['poses'], views['Ks'], views['hw'], **kw)
+    print(f'{stem} {chamfer:.5f}')
+    return chamfer
+
+
+if __name__ == '__main__':
+    main()
