@@ -427,6 +427,45 @@ __device__ __forceinline__ void gemm_f16x3_lean(f32x16 (&aH)[2], f32x16 (&aL)[2]
 #undef NERO_CL
 }
 
+// dual-tile k-loop of the paired kernels (mlp_f16p.hip, NW = 4): a wave that owns TWO feature tiles (weights wp0 / wp1) walks the k-steps
+// once.  One k-step = four activation-fragment reads (shared by both tiles: the second tile's fragments are byte for byte the first's),
+// four weight loads, twelve MFMAs -- half the LDS operand reads, trip count, wait counts and fences of two gemm_f16x3_loop passes, the
+// same weight stream and MFMA count.  Every accumulator sees the products of ops_compute in the same order over ascending k, so the
+// results are those of the single-tile loop bit for bit.  A k-step lasts twice as long, so the weight PAIRS are requested two steps ahead
+// in a ring of three (48 registers; the single-tile loop: three steps ahead in a ring of four), the fragments one step ahead.
+struct WF2 { WF a, b; };
+__device__ __forceinline__ void load_w2(WF2& o, const uint4* wp0, const uint4* wp1, int c) {
+    load_w(o.a, wp0, c);
+    load_w(o.b, wp1, c);
+}
+__device__ __forceinline__ void ops_compute2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const WF2& w, const XF& x) {
+    ops_compute(aH0, aL0, w.a, x);
+    ops_compute(aH1, aL1, w.b, x);
+}
+__device__ __forceinline__ void gemm_f16x3_dual(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const uint4* wp0,
+                                                const uint4* wp1, const char* xp, int half_bytes, int plane_bytes, int n) {
+    if (n <= 0) return;
+    WF2 w0, w1, w2;
+    XF xa, xb;
+    const int last = n - 1;
+#define NERO_CL(c) ((c) < last ? (c) : last)
+#define NERO_K2(W, X) NERO_MID_FENCE(); ops_compute2(aH0, aL0, aH1, aL1, W, X); NERO_FENCE()
+    load_w2(w0, wp0, wp1, 0);
+    load_w2(w1, wp0, wp1, NERO_CL(1));
+    load_x(xa, xp, half_bytes, plane_bytes, 0);
+    NERO_FENCE();
+    for (int c = 0; c < n; c += 6) {
+        load_w2(w2, wp0, wp1, NERO_CL(c + 2)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 1)); NERO_K2(w0, xa);
+        if (c + 1 < n) { load_w2(w0, wp0, wp1, NERO_CL(c + 3)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_K2(w1, xb); }
+        if (c + 2 < n) { load_w2(w1, wp0, wp1, NERO_CL(c + 4)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_K2(w2, xa); }
+        if (c + 3 < n) { load_w2(w2, wp0, wp1, NERO_CL(c + 5)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_K2(w0, xb); }
+        if (c + 4 < n) { load_w2(w0, wp0, wp1, NERO_CL(c + 6)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 5)); NERO_K2(w1, xa); }
+        if (c + 5 < n) { load_w2(w1, wp0, wp1, NERO_CL(c + 7)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 6)); NERO_K2(w2, xb); }
+    }
+#undef NERO_K2
+#undef NERO_CL
+}
+
 // compile-time step count (the 256-wide layers: 16 steps), fully unrolled: no clamps, no branches, every ring slot a fixed register
 // set.  XD = how many steps ahead the activation fragments are requested (ring of XD + 1 sets), weights three steps ahead.
 template <int V> struct IC { static constexpr int value = V; };

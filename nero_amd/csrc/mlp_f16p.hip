@@ -17,8 +17,9 @@
 // (GEMM -> activation / saves -> row-maximum exchange -> plane conversion, two barriers), so the matrix pipe idles through every
 // epilogue, barrier and HBM wait: the per-phase shader-clock profile (scripts/phase_timing.py, profiles/r02_phase_timing.txt)
 // shows 57 % of a forward layer inside the GEMM loop and 30-45 % of a reverse layer, the rest serial.  Here a workgroup is
-// 256 threads = 4 waves that still own 64 rows; wave w computes the feature tiles w and w + 4 one after the other (same packed
-// operand images, same per-row scaling, same results bit for bit).  LDS per workgroup drops to 79.4 KB -- the aux operand
+// 256 threads = 4 waves that still own 64 rows; wave w computes the feature tiles w and w + 4 (same packed operand images, same per-row
+// scaling, same results bit for bit) -- in ONE walk over the k-steps where both exist (P_DUAL_TILE below: the activation fragments of the
+// second tile are those of the first, so a k-step reads them once for twelve MFMAs), one after the other otherwise.  LDS per workgroup drops to 79.4 KB -- the aux operand
 // (skip / direction inputs, <= 96 columns) is converted from global memory inside its k-steps instead of living in LDS, the
 // store-transposition scratch covers 16 rows at a time -- so two workgroups share a CU and one's epilogue, barriers and HBM
 // latency are covered by the other's MFMAs.
@@ -32,7 +33,7 @@ namespace {
 
 #include "mlp_f16_util.h"
 
-// NW = waves per workgroup.  4 (round 2 / 5): wave w computes the feature tiles w and w + 4 one after the other, 256 registers per wave,
+// NW = waves per workgroup.  4 (round 2 / 5): wave w computes the feature tiles w and w + 4, 256 registers per wave,
 // two waves per SIMD.  8 (round 6): wave w computes tile w only, at most 128 registers per wave, FOUR waves per SIMD from two workgroups --
 // the occupancy at which scripts/probe/rowowner_probe.hip measures today's layer structure 13 % faster than with one workgroup per CU.
 // reverse kernel: the saved activations of a wave's first / second feature tile are requested in front of (true) or behind (false) its GEMM
@@ -62,6 +63,9 @@ __device__ __forceinline__ LdsP carve_p(char* smem) {
 #endif
 inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + 4 * SCRP_BYTES + P_LDS_EXTRA; }      // 79488 (NW = 8: 8 x 8-row scratch, the same)
 
+// the per-lane addresses of the chain's OUTPUTS (d_init, d_aux: written once, by the first layer) are formed from a row index the compiler
+// cannot see through: otherwise it hoists them out of the layer loop and they occupy registers -- or scratch -- through every GEMM
+#define P_LOCAL_V(x) asm volatile("" : "+v"(x))
 struct Ctx { LdsP S; int wave, lane, i, h, row0, n_rows; float* scr; };
 
 // rows [row0, row0+64) x first k columns of a row-major fp32 matrix -> scaled plane pairs + per-row scale (NW threads per row)
@@ -151,6 +155,87 @@ __device__ __forceinline__ void gemm_aux_global(f32x16 (&aH)[2], f32x16 (&aL)[2]
             ops_compute(aH, aL, wb, x);
             NERO_FENCE();
         }
+    }
+}
+
+// the same for the two feature tiles of a wave (weights wp0 / wp1) in one walk: one conversion of the raw fragments per k-step
+__device__ __forceinline__ void gemm_aux_global2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const uint4* wp0,
+                                                 const uint4* wp1, const float* __restrict__ aux, int ld, int k, int n, const Ctx& c, float inv0,
+                                                 float inv1) {
+    if (n <= 0) return;
+    int g0 = c.row0 + c.i, g1 = c.row0 + 32 + c.i;
+    g0 = g0 < c.n_rows ? g0 : c.n_rows - 1;
+    g1 = g1 < c.n_rows ? g1 : c.n_rows - 1;
+    const float* p0 = aux + (size_t)g0 * ld;
+    const float* p1 = aux + (size_t)g1 * ld;
+    WF2 wa, wb;
+    RawX ra, rb;
+    XF x;
+    load_w2(wa, wp0, wp1, 0);
+    load_raw(ra, p0, p1, 0, c.h, k);
+    for (int s = 0; s < n; s += 2) {
+        if (s + 1 < n) { load_w2(wb, wp0, wp1, s + 1); load_raw(rb, p0, p1, s + 1, c.h, k); }
+        NERO_FENCE();
+        raw_to_x(x, ra, inv0, inv1);
+        ops_compute2(aH0, aL0, aH1, aL1, wa, x);
+        NERO_FENCE();
+        if (s + 1 < n) {
+            if (s + 2 < n) { load_w2(wa, wp0, wp1, s + 2); load_raw(ra, p0, p1, s + 2, c.h, k); }
+            NERO_FENCE();
+            raw_to_x(x, rb, inv0, inv1);
+            ops_compute2(aH0, aL0, aH1, aL1, wb, x);
+            NERO_FENCE();
+        }
+    }
+}
+
+// P_DUAL_TILE (default on): a wave of the 4-wave kernels that owns two feature tiles (t and t + 4) computes both in ONE k-loop
+// (mlp_f16_util.h: gemm_f16x3_dual); 0 restores the two sequential single-tile loops.  The two-accumulator debug format stays sequential.
+// Forward and tangent (P_DUAL_TILE_TAN).  The REVERSE kernels keep the sequential loops: the mask-only kernel measured no gain from one
+// loop (class 5.16 against 5.13 ms), the softplus kernel does not fit (35 spilled registers): profiles/paired_dual_tile_ab.txt.
+#ifndef P_DUAL_TILE
+#ifdef F16_TWO_ACC
+#define P_DUAL_TILE 0
+#else
+#define P_DUAL_TILE 1
+#endif
+#endif
+#ifndef P_DUAL_TILE_TAN
+#define P_DUAL_TILE_TAN P_DUAL_TILE
+#endif
+
+// aux part then main part of the feature tiles t and t + NW together; the units U are those of gemm_tile (they do not depend on the tile)
+template <int NW>
+__device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], float (&U)[2], const Ctx& c,
+                                           int t, const float* w_main, const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx,
+                                           const float* aux, int ld_aux, int k_aux_cols) {
+    if (sx > 0) {
+        const float wsc = wsc_aux;
+        const float ra0 = c.S.rs_aux[c.i], ra1 = c.S.rs_aux[32 + c.i];
+        const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)t * sx * 128 + c.lane;
+        gemm_aux_global2(aH0, aL0, aH1, aL1, wp, wp + (size_t)NW * sx * 128, aux, ld_aux, k_aux_cols, sx, c, 1.f / ra0, 1.f / ra1);
+        U[0] = wsc * ra0;
+        U[1] = wsc * ra1;
+    }
+    if (sm > 0) {
+        const float wsc = wsc_main;
+        const float u0 = wsc * c.S.rs_main[c.i], u1 = wsc * c.S.rs_main[32 + c.i];
+        if (sx > 0) {
+            const float r0 = U[0] / u0, r1 = U[1] / u1;    // exact: powers of two
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                aH0[0][v] *= r0; aH0[1][v] *= r1;
+                aH1[0][v] *= r0; aH1[1][v] *= r1;
+#ifdef F16_TWO_ACC
+                aL0[0][v] *= r0; aL0[1][v] *= r1;
+                aL1[0][v] *= r0; aL1[1][v] *= r1;
+#endif
+            }
+        }
+        U[0] = u0;
+        U[1] = u1;
+        const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)t * sm * 128 + c.lane;
+        gemm_f16x3_dual(aH0, aL0, aH1, aL1, wp, wp + (size_t)NW * sm * 128, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
     }
 }
 
@@ -280,6 +365,45 @@ __device__ __forceinline__ void fwd_values(const f32x16 (&aH)[2], const f32x16 (
     }
 }
 
+// bias of feature tile t in the accumulator layout of this lane
+__device__ __forceinline__ void fwd_load_bias(float4 (&bq)[4], const nero_fwd_layer& L, const Ctx& c, int t) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        bq[g] = L.bias ? *reinterpret_cast<const float4*>(L.bias + 32 * t + 8 * g + 4 * c.h) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// epilogue of one feature tile: bias + activation -> val, row-major save, ReLU sign words, row maxima
+template <int NW>
+__device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2], const f32x16 (&aL)[2],
+                                             const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4], float (&m)[2] PH_PARAM) {
+    if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, aL, bq, U, val, m);
+    else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, aL, bq, U, val, m);
+    else fwd_values<NERO_ACT_NONE>(aH, aL, bq, U, val, m);
+    PH(3);
+    if (L.save) {
+        float* sblock = L.save + (size_t)c.row0 * NERO_HID + 32 * t;
+        acc_to_global_rows<64 / NW>(c.scr, val[0], sblock, c.lane);
+        acc_to_global_rows<64 / NW>(c.scr, val[1], sblock + (size_t)32 * NERO_HID, c.lane);
+    }
+    if (L.relu_mask) {                              // sign bits of this lane's 2 x 16 outputs -> one word per (row, tile)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            unsigned bits = 0u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                bits |= (val[r][g].x > 0.f ? 1u : 0u) << (4 * g);
+                bits |= (val[r][g].y > 0.f ? 1u : 0u) << (4 * g + 1);
+                bits |= (val[r][g].z > 0.f ? 1u : 0u) << (4 * g + 2);
+                bits |= (val[r][g].w > 0.f ? 1u : 0u) << (4 * g + 3);
+            }
+            const unsigned other = other_half(bits, c.h);
+            if (c.h == 0) L.relu_mask[(size_t)(c.row0 + 32 * r + c.i) * 8 + t] = bits | (other << 16);
+        }
+    }
+    publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
+    PH(4);
+}
+
 template <int NW>
 __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fwd_layer& L, int l, const Ctx& c, int t, float4 (&val)[2][4],
                                          float (&m)[2] PH_PARAM) {
@@ -289,44 +413,40 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
         zero2(aH);
         zero2(aL);
         float4 bq[4];
-        auto load_bias = [&]() {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                bq[g] = L.bias ? *reinterpret_cast<const float4*>(L.bias + 32 * t + 8 * g + 4 * c.h) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        if (NW == 4) load_bias();                       // (NW = 8: behind the GEMM -- 16 registers its 128 have no room for)
+        if (NW == 4) fwd_load_bias(bq, L, c, t);        // (NW = 8: behind the GEMM -- 16 registers its 128 have no room for)
         float U[2] = {1.f, 1.f};
         PH(1);
         gemm_tile<NW>(aH, aL, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
-        if (NW == 8) { NERO_FENCE(); load_bias(); }
+        if (NW == 8) { NERO_FENCE(); fwd_load_bias(bq, L, c, t); }
         PH(2);
-        if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, aL, bq, U, val, m);
-        else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, aL, bq, U, val, m);
-        else fwd_values<NERO_ACT_NONE>(aH, aL, bq, U, val, m);
-        PH(3);
-        if (L.save) {
-            float* sblock = L.save + (size_t)c.row0 * NERO_HID + 32 * t;
-            acc_to_global_rows<64 / NW>(c.scr, val[0], sblock, c.lane);
-            acc_to_global_rows<64 / NW>(c.scr, val[1], sblock + (size_t)32 * NERO_HID, c.lane);
-        }
-        if (L.relu_mask) {                              // sign bits of this lane's 2 x 16 outputs -> one word per (row, tile)
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                unsigned bits = 0u;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bits |= (val[r][g].x > 0.f ? 1u : 0u) << (4 * g);
-                    bits |= (val[r][g].y > 0.f ? 1u : 0u) << (4 * g + 1);
-                    bits |= (val[r][g].z > 0.f ? 1u : 0u) << (4 * g + 2);
-                    bits |= (val[r][g].w > 0.f ? 1u : 0u) << (4 * g + 3);
-                }
-                const unsigned other = other_half(bits, c.h);
-                if (c.h == 0) L.relu_mask[(size_t)(c.row0 + 32 * r + c.i) * 8 + t] = bits | (other << 16);
-            }
-        }
+        fwd_epilogue<NW>(L, c, t, aH, aL, bq, U, val, m PH_ARG);
+    } else {
+        publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
+        PH(4);
     }
-    publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
-    PH(4);
+}
+
+// the feature tiles t and t + NW of one wave (both exist): ONE walk over the k-steps for both (gemm_tile2), then the two epilogues one
+// after the other -- an accumulator set becomes its `val` registers only when its epilogue runs
+template <int NW>
+__device__ __forceinline__ void fwd_tile_pair(const nero_fwd_chain& ch, const nero_fwd_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
+                                              float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2] PH_PARAM) {
+    f32x16 aH0[2], aL0[2], aH1[2], aL1[2];
+    zero2(aH0);
+    zero2(aL0);
+    zero2(aH1);
+    zero2(aL1);
+    float4 bq[4];
+    fwd_load_bias(bq, L, c, t);
+    float U[2] = {1.f, 1.f};
+    PH(1);
+    gemm_tile2<NW>(aH0, aL0, aH1, aL1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+                   ch.ld_aux, ch.k_aux);
+    float4 bq1[4];                                     // (behind the GEMM: its round trip passes under the first tile's epilogue)
+    fwd_load_bias(bq1, L, c, t + NW);
+    PH(2);
+    fwd_epilogue<NW>(L, c, t, aH0, aL0, bq, U, v0, m0 PH_ARG);
+    fwd_epilogue<NW>(L, c, t + NW, aH1, aL1, bq1, U, v1, m1 PH_ARG);
 }
 
 template <int NW>
@@ -351,8 +471,17 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
         if (L.n_tiles == 0) continue;
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
+#if P_DUAL_TILE
+        // (wave-uniform: no second tile for n_tiles <= 4 -- the 128-wide layers -- and for wave 3 of the 217-wide SDF layer)
+        if (NW == 4 && c.wave + NW < L.n_tiles) fwd_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1 PH_ARG);
+        else {
+            fwd_tile<NW>(ch, L, l, c, c.wave, v0, m0 PH_ARG);
+            if (NW == 4) fwd_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
+        }
+#else
         fwd_tile<NW>(ch, L, l, c, c.wave, v0, m0 PH_ARG);
         if (NW == 4) fwd_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
+#endif
         commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
         PH(5);
     }
@@ -366,59 +495,85 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
 // ---------------------------------------------------------------------------------------------------------------------
 // tangent chain (softplus networks):  adot_l = s_l * (W_l adot_{l-1}),  inj_l = gbar_l * beta (1-s_l) * zdot_l
 // ---------------------------------------------------------------------------------------------------------------------
+// epilogue of one feature tile of a tangent layer: adot = s * zdot (and the finished injection when the chain asks for it), row maxima
+template <int NW>
+__device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2], const f32x16 (&aL)[2],
+                                             const float (&U)[2], float4 (&val)[2][4], float (&m)[2]) {
+    const size_t goff = (size_t)(c.row0 + c.i) * NERO_HID + 32 * t + 4 * c.h;     // + r*32*HID + 8g
+    const size_t boff = (size_t)c.row0 * NERO_HID + 32 * t;
+    const bool want_inj = L.inj != nullptr;        // (default: NULL -- the reverse kernel forms the injection, nero_bwd_layer.inj_adot)
+    m[0] = m[1] = 0.f;
+    // the saved activations are requested BEHIND the GEMM (32 registers it has no room for at two workgroups per CU: 23 spilled);
+    // the round trip is covered by the other workgroup's MFMAs, which is what this engine is for
+    NERO_FENCE();
+    float4 pa[2][4], pg[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            pa[r][g] = *reinterpret_cast<const float4*>(L.a_saved + goff + (size_t)r * 32 * NERO_HID + 8 * g);
+            pg[r][g] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    if (want_inj) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) pg[r][g] = *reinterpret_cast<const float4*>(L.gbar + goff + (size_t)r * 32 * NERO_HID + 8 * g);
+    }
+    float* scr = c.scr;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const bool live = (c.row0 + 32 * r + c.i) < c.n_rows;
+        float4 ijq[4], adq[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 a = pa[r][g], gb = pg[r][g];
+            float4 ad, ij;
+            tan_elem(a.x, ACCV(aH, aL, r, 4 * g) * U[r], gb.x, live, ad.x, ij.x);
+            tan_elem(a.y, ACCV(aH, aL, r, 4 * g + 1) * U[r], gb.y, live, ad.y, ij.y);
+            tan_elem(a.z, ACCV(aH, aL, r, 4 * g + 2) * U[r], gb.z, live, ad.z, ij.z);
+            tan_elem(a.w, ACCV(aH, aL, r, 4 * g + 3) * U[r], gb.w, live, ad.w, ij.w);
+            val[r][g] = ad;
+            m[r] = fmaxf(m[r], amax4(ad));
+            adq[g] = live ? ad : make_float4(0.f, 0.f, 0.f, 0.f);
+            ijq[g] = ij;
+        }
+        acc_to_global_rows<64 / NW>(scr, adq, L.adot + boff + (size_t)r * 32 * NERO_HID, c.lane);
+        if (want_inj) acc_to_global_rows<64 / NW>(scr, ijq, L.inj + boff + (size_t)r * 32 * NERO_HID, c.lane);
+    }
+    publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
+}
+
 template <int NW>
 __device__ __forceinline__ void tan_tile(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&val)[2][4],
                                          float (&m)[2]) {
-    m[0] = m[1] = 0.f;
     if (t < L.n_tiles) {
-        const size_t goff = (size_t)(c.row0 + c.i) * NERO_HID + 32 * t + 4 * c.h;     // + r*32*HID + 8g
-        const size_t boff = (size_t)c.row0 * NERO_HID + 32 * t;
-        const bool want_inj = L.inj != nullptr;        // (default: NULL -- the reverse kernel forms the injection, nero_bwd_layer.inj_adot)
         f32x16 aH[2], aL[2];
         zero2(aH);
         zero2(aL);
         float U[2] = {1.f, 1.f};
         gemm_tile<NW>(aH, aL, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
-        // the saved activations are requested BEHIND the GEMM (32 registers it has no room for at two workgroups per CU: 23 spilled);
-        // the round trip is covered by the other workgroup's MFMAs, which is what this engine is for
-        NERO_FENCE();
-        float4 pa[2][4], pg[2][4];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                pa[r][g] = *reinterpret_cast<const float4*>(L.a_saved + goff + (size_t)r * 32 * NERO_HID + 8 * g);
-                pg[r][g] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        if (want_inj) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) pg[r][g] = *reinterpret_cast<const float4*>(L.gbar + goff + (size_t)r * 32 * NERO_HID + 8 * g);
-        }
-        float* scr = c.scr;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const bool live = (c.row0 + 32 * r + c.i) < c.n_rows;
-            float4 ijq[4], adq[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 a = pa[r][g], gb = pg[r][g];
-                float4 ad, ij;
-                tan_elem(a.x, ACCV(aH, aL, r, 4 * g) * U[r], gb.x, live, ad.x, ij.x);
-                tan_elem(a.y, ACCV(aH, aL, r, 4 * g + 1) * U[r], gb.y, live, ad.y, ij.y);
-                tan_elem(a.z, ACCV(aH, aL, r, 4 * g + 2) * U[r], gb.z, live, ad.z, ij.z);
-                tan_elem(a.w, ACCV(aH, aL, r, 4 * g + 3) * U[r], gb.w, live, ad.w, ij.w);
-                val[r][g] = ad;
-                m[r] = fmaxf(m[r], amax4(ad));
-                adq[g] = live ? ad : make_float4(0.f, 0.f, 0.f, 0.f);
-                ijq[g] = ij;
-            }
-            acc_to_global_rows<64 / NW>(scr, adq, L.adot + boff + (size_t)r * 32 * NERO_HID, c.lane);
-            if (want_inj) acc_to_global_rows<64 / NW>(scr, ijq, L.inj + boff + (size_t)r * 32 * NERO_HID, c.lane);
-        }
+        tan_epilogue<NW>(L, c, t, aH, aL, U, val, m);
+    } else {
+        m[0] = m[1] = 0.f;
+        publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
     }
-    publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
+}
+
+// both feature tiles of a wave in one walk over the k-steps (fwd_tile_pair)
+template <int NW>
+__device__ __forceinline__ void tan_tile_pair(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
+                                              float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2]) {
+    f32x16 aH0[2], aL0[2], aH1[2], aL1[2];
+    zero2(aH0);
+    zero2(aL0);
+    zero2(aH1);
+    zero2(aL1);
+    float U[2] = {1.f, 1.f};
+    gemm_tile2<NW>(aH0, aL0, aH1, aL1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+                   ch.ld_aux, ch.k_aux);
+    tan_epilogue<NW>(L, c, t, aH0, aL0, U, v0, m0);
+    tan_epilogue<NW>(L, c, t + NW, aH1, aL1, U, v1, m1);
 }
 
 template <int NW>
@@ -436,8 +591,16 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void tan_p_kernel(nero_tan_chain c
         const nero_tan_layer L = load_layer(ch, l);
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
+#if P_DUAL_TILE_TAN
+        if (NW == 4 && c.wave + NW < L.n_tiles) tan_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1);
+        else {
+            tan_tile<NW>(ch, L, l, c, c.wave, v0, m0);
+            if (NW == 4) tan_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1);
+        }
+#else
         tan_tile<NW>(ch, L, l, c, c.wave, v0, m0);
         if (NW == 4) tan_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1);
+#endif
         commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
     }
 }
@@ -504,12 +667,15 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
                        xp, 32 * SA, PLANE_A, steps);
             const float u[2] = {wsc * rs0, wsc * rs1};
             combine_acc(gq, aH, aL, u);
+            int li = c.i, lf = fbase;
+            P_LOCAL_V(li);
+            P_LOCAL_V(lf);
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int f = fbase + 8 * g;
-                    if (f < ch.ld_daux) *reinterpret_cast<float4*>(ch.d_aux + (size_t)(c.row0 + 32 * r + c.i) * ch.ld_daux + f) = gq[r][g];
+                    const int f = lf + 8 * g;
+                    if (f < ch.ld_daux) *reinterpret_cast<float4*>(ch.d_aux + (size_t)(c.row0 + 32 * r + li) * ch.ld_daux + f) = gq[r][g];
                 }
         }
         if (!live_t || (first && !ch.d_init)) { publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h); return; }
@@ -528,14 +694,17 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
         if (first) {
             if (ch.d_init) {
                 const int ldi = ch.ld_dinit;
+                int li = c.i, lf = fbase;
+                P_LOCAL_V(li);
+                P_LOCAL_V(lf);
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const int f = fbase + 8 * g;
+                        const int f = lf + 8 * g;
                         if (f < ldi) {
                             float4 v = gq[r][g];
-                            float4* dstp = reinterpret_cast<float4*>(ch.d_init + (size_t)(c.row0 + 32 * r + c.i) * ldi + f);
+                            float4* dstp = reinterpret_cast<float4*>(ch.d_init + (size_t)(c.row0 + 32 * r + li) * ldi + f);
                             if (ch.accumulate_dinit) { const float4 o = *dstp; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
                             *dstp = v;
                         }
