@@ -710,6 +710,60 @@ int nero_view_points(const float* t, const double* K /*host*/, const double* pos
 int nero_depth_points(const float* depth, const unsigned char* mask, const double* K /*host*/, const double* pose /*host*/, int h, int w,
                       float unproject_offset, void* ws, float* pts, int64_t pts_cap, int64_t* n_pts /*device*/, void* stream);
 
+/* ---- texture baking: the Stage-II materials as UV maps (nero_amd/csrc/texture.hip) --------------------------------------------------------
+ * The device steps of extract_materials_texture_map.py without nvdiffrast / scipy / sklearn / cv2 (the unwrapping itself, xatlas, stays with
+ * the caller: any vt / ft will do).  Maps are row-major [h][w], texel (row y, column x) has index y w + x and its centre at u = (x + 0.5) / w,
+ * v = (y + 0.5) / h; h and w in [1, 16384], anything else is NERO_ERR_ARG.  Host counterpart: nero_amd/texture.py.  No floating-point
+ * atomics, no atomics that decide a position: every result is bit-identical run to run.
+ *
+ * nero_uv_raster -- `dr.rasterize(glctx, uv, ft, (h, w))` (extract_materials_texture_map.py:89-99) with a coverage rule of this project's own,
+ *   exact integer arithmetic.  vt [nvt,2] fp32, ft [nt,3] int32 -> tri_id [h w] int32, -1 where uncovered.  A vertex snaps to
+ *   X = rint(double(u) w 256), Y = rint(double(v) h 256) (int64); a texel centre is (256 x + 128, 256 y + 128).  A = (x1-x0)(y2-y0) -
+ *   (x2-x0)(y1-y0); A == 0 covers nothing; A < 0 swaps vertices 1 and 2 (both windings are accepted).  For each directed edge a -> b,
+ *   e = (bx-ax)(py-ay) - (by-ay)(px-ax); the texel is inside when for all three edges e > 0, or e == 0 and the edge owns its boundary: dy < 0,
+ *   or dy == 0 and dx > 0.  Every centre of a triangulated region is covered exactly once.  Where triangles overlap the lowest index wins
+ *   (an integer atomic minimum: independent of arrival order).  Vertices outside [0, 1] are legal and clipped by the texel loop bounds; a
+ *   triangle with a vertex that is not finite or snaps beyond 2^30 in magnitude covers nothing.  An index of ft outside [0, nvt) is
+ *   NERO_ERR_ARG with nothing written: one validation kernel whose flag is read back on `stream`, the call's one synchronisation.
+ *   Work is binned by bounding-box size: boxes of at most 16 texel centres are finished by the lane that set the triangle up, the others are
+ *   cut into blocks of 8 x 8 texels that a fixed grid of waves shares.  ws: nero_uv_raster_workspace_bytes(nt) (16 bytes per triangle + the
+ *   scan's scratch; 0 = a refused count).
+ * nero_uv_interp -- `dr.interpolate(v, rast, f)`, the mask and `xyzs[mask]` (:100-113).  attr [nv,C] fp32 with its own face array fa [nt,3]
+ *   (the reference rasterises with the UV faces and interpolates with the position faces) -> the covered texels compacted in ascending
+ *   row-major order: texel [n] int32, out [n,C] = (e0 a0 + e1 a1 + e2 a2) / A with e_k the edge function opposite vertex k at the centre,
+ *   formed in float64 (products, then the two sums left to right, then the quotient) and rounded once to fp32; mask [h w] bytes (may be NULL)
+ *   = covered; n_out: device int64 (may be NULL).  Positions come from a prefix sum.  The call reads the count back on `stream` before it
+ *   writes: more covered texels than `cap`, or an index of ft / fa out of range, is NERO_ERR_ARG with nothing written.
+ *   ws: nero_uv_interp_workspace_bytes(h, w) (8 bytes per texel + the scan's scratch).
+ * nero_tex_quantize -- `feats[mask] = ...; linear_to_srgb; (feats * 255).astype(np.uint8)` (:127-133; utils/raw_utils.py:4-15).  feat [n,C]
+ *   fp32 at the texels texel [n] (distinct) -> tex [h w, C] uint8, zero elsewhere: x clamped to [0, 1] (NaN -> 0), srgb in float64 (as the reference's
+ *   numpy branch), times 255, truncated toward zero.  1 <= C <= 64.
+ * nero_tex_regions -- `binary_dilation(mask, iterations=32)` minus the mask and the mask minus `binary_erosion(mask, iterations=3)` (:136-141;
+ *   cross structuring element, border_value 0).  mask [h w] bytes (non-zero = covered) -> region [h w] bytes: 3 (to be filled) = uncovered
+ *   and within city-block distance `pad` of a covered texel; 2 (search band) = covered and within city-block distance `border` of an
+ *   uncovered texel, everything outside the image counting as uncovered; 1 = covered interior; 0 = nothing.  A row pass and a column pass
+ *   over clamped byte distances.  pad in [0, 64], border in [1, 16], else NERO_ERR_ARG.  ws: nero_tex_regions_workspace_bytes(h, w) (one byte
+ *   per texel).
+ * nero_tex_fill -- the kd-tree query and the copy (:143-149), in place on tex [h w, C]: every region-3 texel takes the C bytes of the nearest
+ *   region-2 texel among those within `pad` rows and `pad` columns of it: smallest integer squared Euclidean distance, ties to the lowest
+ *   row-major index (sklearn leaves ties unspecified).  For regions made by nero_tex_regions with the same pad that window always holds the
+ *   global nearest (the city-block-nearest covered texel is a chart-border texel at Euclidean distance <= pad).  A fill texel without a search
+ *   texel in its window is left as it is.  src [h w] int32 (may be NULL) = the source index, -1 where nothing was filled.  Sources are never
+ *   written and destinations never read, so in place is safe.  pad in [0, 64], 1 <= C <= 64.
+ * nero_tex_downsample2 -- `cv2.resize(..., (w, h), INTER_LINEAR)` of a [2h, 2w, C] map (:157-160): out [h,w,C] = (a + b + c + d + 2) >> 2 over each
+ *   2 x 2 block (cv2's rounding of ties is not verified: cv2 is not available to this project).  2h, 2w <= 16384. */
+size_t nero_uv_raster_workspace_bytes(int64_t nt);
+int nero_uv_raster(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int* tri_id, void* stream);
+size_t nero_uv_interp_workspace_bytes(int h, int w);
+int nero_uv_interp(const int* tri_id, const float* vt, int64_t nvt, const int* ft, int64_t nt, const float* attr, int64_t nv, int C, const int* fa,
+                   int h, int w, void* ws, int* texel, float* out, int64_t cap, unsigned char* mask /*or NULL*/, int64_t* n_out /*device, or NULL*/,
+                   void* stream);
+int nero_tex_quantize(const float* feat, const int* texel, int64_t n, int C, int h, int w, unsigned char* tex, void* stream);
+size_t nero_tex_regions_workspace_bytes(int h, int w);
+int nero_tex_regions(const unsigned char* mask, int h, int w, int pad, int border, void* ws, unsigned char* region, void* stream);
+int nero_tex_fill(unsigned char* tex, const unsigned char* region, int h, int w, int C, int pad, int* src /*or NULL*/, void* stream);
+int nero_tex_downsample2(const unsigned char* in, int h, int w, int C, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

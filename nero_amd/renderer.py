@@ -529,6 +529,8 @@ class NeROMaterialRenderer(nn.Module):
                 tm = trimesh.load(self.cfg['mesh'], force='mesh', skip_material=True, process=False)
                 mesh = (np.asarray(tm.vertices), np.asarray(tm.faces))
         self.ray_tracer = RayTracer(mesh[0], mesh[1])
+        # the mesh itself, for what works on its surface rather than on rays (extract_texture_maps)
+        self.mesh_vertices, self.mesh_triangles = self.ray_tracer._v.reshape(-1, 3), self.ray_tracer._f.reshape(-1, 3)   # float32 / int32, host
         self.cfg['shader_cfg'] = dict(self.cfg['shader_cfg'])
         self.cfg['shader_cfg']['is_real'] = self.cfg['database_name'].startswith('real')
         self.shader_network = MCShadingNetwork(self.cfg['shader_cfg'], lambda o, d: self.trace(o, d))
@@ -772,6 +774,12 @@ class NeROMaterialRenderer(nn.Module):
                 out['roughness'].append(torch.sqrt(torch.clamp(r, min=1e-7)).cpu().numpy())
                 out['albedo'].append(a.cpu().numpy())
         return {k: np.concatenate(v, 0) for k, v in out.items()}
+
+    def extract_texture_maps(self, **kw):
+        """albedo / metallic / roughness baked into UV texture maps on the device (extract_materials_texture_map.py): nero_amd.texture.
+        bake_materials(self, **kw) -- vt / ft of any unwrapper, or the built-in simple_atlas"""
+        from .texture import bake_materials
+        return bake_materials(self, **kw)
 
     def shade_train(self, pts, view_dirs, normals, human_poses, rgb_gt, step, rand_d=None, rand_s=None, reg_ang=None, reg_eps=None):
         """the arithmetic of train_step (network/renderer.py:837-844) for an explicit batch"""

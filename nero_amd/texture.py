@@ -1,0 +1,409 @@
+"""Baking the Stage-II materials into UV texture maps on the device (libnero_hip.so, nero_uv_* / nero_tex_*), and the textured OBJ.
+
+The reference does this in extract_materials_texture_map.py with xatlas (unwrap), nvdiffrast (rasterise / interpolate in UV space), scipy
+(dilation / erosion), sklearn (kd-tree gutter fill) and cv2 (resize, images), copying every 640 k-texel chunk to the host.  Only the unwrapping
+needs xatlas; every other step is a kernel of nero_amd/csrc/texture.hip here:
+  * rasterize_uv / interpolate: coverage in UV space by an exact integer rule, positions interpolated in float64 and compacted by prefix sum;
+  * quantize: linear_to_srgb, 8 bits;
+  * gutter_regions / fill_gutter: the 32-texel gutter filled from the nearest chart-border texel;
+  * downsample2: the 2 x 2 mean of the supersampled maps;
+  * bake_materials: all of it around NeROMaterialRenderer.predict_materials, the only host traffic being the count readbacks;
+  * simple_atlas: a dependency-free one-chart-per-triangle atlas for when no unwrapper is at hand; any (vt, ft) can be passed instead;
+  * write_textured_obj / read_textured_obj: the reference's OBJ / MTL layout with lossless PNG maps.
+Conventions (include/nero_hip.h): maps are [h, w] row-major, texel (row y, column x) has its centre at u = (x + 0.5) / w, v = (y + 0.5) / h."""
+import ctypes as C
+import os
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+_lib = L.lib
+_lib.nero_uv_raster_workspace_bytes.restype = C.c_size_t
+_lib.nero_uv_raster_workspace_bytes.argtypes = [C.c_int64]
+_lib.nero_uv_raster.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_uv_interp_workspace_bytes.restype = C.c_size_t
+_lib.nero_uv_interp_workspace_bytes.argtypes = [C.c_int, C.c_int]
+_lib.nero_uv_interp.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_tex_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+_lib.nero_tex_regions_workspace_bytes.restype = C.c_size_t
+_lib.nero_tex_regions_workspace_bytes.argtypes = [C.c_int, C.c_int]
+_lib.nero_tex_regions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_tex_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+_lib.nero_tex_downsample2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+
+
+def _dev(*tensors):
+    for t in tensors:
+        if torch.is_tensor(t) and t.is_cuda:
+            return t.device
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _to(x, dtype, dev, cols=None):
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    x = x.to(device=dev, dtype=dtype).contiguous()
+    if cols is not None and (x.dim() != 2 or x.shape[1] != cols):
+        raise ValueError(f'expected an array [n, {cols}], got {tuple(x.shape)}')
+    return x
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+# ---- kernels --------------------------------------------------------------------------------------------------------------------------------
+def rasterize_uv(vt, ft, h, w, out=None):
+    """vt [nvt,2] in [0,1] (u along the columns, v along the rows), ft [nt,3] -> tri_id int32 [h, w] on the device, -1 where uncovered
+    (nero_uv_raster: the exact-cover integer rule of include/nero_hip.h; overlapping charts resolve to the lowest triangle index).  `out`:
+    an int32 [h, w] tensor to write into.  A size outside [1, 16384] or a face index outside [0, nvt) raises NeroHipError, nothing written."""
+    dev = _dev(vt, ft, out)
+    vt, ft = _to(vt, torch.float32, dev, 2), _to(ft, torch.int32, dev, 3)
+    h, w = int(h), int(w)
+    with torch.cuda.device(dev):
+        need = int(_lib.nero_uv_raster_workspace_bytes(ft.shape[0]))
+        ws = _ws(need, dev)
+        if out is None:
+            out = torch.empty((max(h, 0), max(w, 0)) if max(h, w) <= 16384 else (0, 0), dtype=torch.int32, device=dev)
+        L.check(_lib.nero_uv_raster(L.ptr(vt), vt.shape[0], L.ptr(ft), ft.shape[0], h, w, L.ptr(ws), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def interpolate(tri_id, vt, ft, attr, fa, cap=None, return_mask=False, out=None):
+    """the covered texels of tri_id [h, w] in ascending row-major order: (texel int32 [n], values float32 [n, C]) with values = the attribute
+    attr [nv, C], indexed by its own faces fa [nt, 3], interpolated at the texel centre in float64 and rounded once (nero_uv_interp).  One
+    readback of the count sizes the outputs; `cap`: allocate for that many texels instead (fewer than covered raises NeroHipError, nothing
+    written); `out` = (texel, values) buffers to write into; return_mask: also the coverage as bytes [h, w]."""
+    dev = _dev(tri_id)
+    h, w = tri_id.shape
+    tri_id = _to(tri_id, torch.int32, dev)
+    vt, ft, fa = _to(vt, torch.float32, dev, 2), _to(ft, torch.int32, dev, 3), _to(fa, torch.int32, dev, 3)
+    attr = _to(attr, torch.float32, dev)
+    if attr.dim() != 2 or fa.shape != ft.shape:
+        raise ValueError(f'interpolate: attr must be [nv, C] and fa shaped like ft, got {tuple(attr.shape)} and {tuple(fa.shape)} vs {tuple(ft.shape)}')
+    Cn = attr.shape[1]
+    with torch.cuda.device(dev):
+        ws = _ws(_lib.nero_uv_interp_workspace_bytes(h, w), dev)
+        mask = torch.empty((h, w), dtype=torch.uint8, device=dev) if return_mask else None
+        n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+        if out is not None:
+            texel, vals = out
+            cap = texel.shape[0] if cap is None else int(cap)
+        else:
+            if cap is None:
+                cap = int((tri_id >= 0).sum())                      # the count readback that sizes the outputs
+            texel = torch.empty(cap, dtype=torch.int32, device=dev)
+            vals = torch.empty((cap, Cn), dtype=torch.float32, device=dev)
+        L.check(_lib.nero_uv_interp(L.ptr(tri_id), L.ptr(vt), vt.shape[0], L.ptr(ft), ft.shape[0], L.ptr(attr), attr.shape[0], Cn, L.ptr(fa), h, w,
+                                    L.ptr(ws), L.ptr(texel), L.ptr(vals), int(cap), L.ptr(mask), L.ptr(n_out), L.stream_ptr()))
+        n = int(n_out)
+    res = (texel[:n], vals[:n])
+    return res + (mask,) if return_mask else res
+
+
+def quantize(values, texel, h, w):
+    """values float32 [n, C] at the texels texel [n] -> uint8 [h, w, C], zero elsewhere: uint8(linear_to_srgb(clamp(x, 0, 1)) * 255), truncated
+    (nero_tex_quantize; extract_materials_texture_map.py:127-133)"""
+    dev = _dev(values)
+    values, texel = _to(values, torch.float32, dev), _to(texel, torch.int32, dev)
+    if values.dim() != 2 or texel.shape != values.shape[:1]:
+        raise ValueError(f'quantize: values [n, C] and texel [n] expected, got {tuple(values.shape)} and {tuple(texel.shape)}')
+    with torch.cuda.device(dev):
+        tex = torch.empty((h, w, values.shape[1]), dtype=torch.uint8, device=dev)
+        L.check(_lib.nero_tex_quantize(L.ptr(values), L.ptr(texel), values.shape[0], values.shape[1], int(h), int(w), L.ptr(tex), L.stream_ptr()))
+    return tex
+
+
+def gutter_regions(mask, pad=32, border=3):
+    """mask [h, w] (non-zero = covered) -> region uint8 [h, w]: 0 nothing, 1 covered interior, 2 covered and in the search band (within
+    city-block distance `border` of an uncovered texel or of the image edge), 3 to be filled (uncovered, within city-block distance `pad` of a
+    covered texel) -- binary_dilation(iterations=pad) / binary_erosion(iterations=border) of the reference (:136-141) as two separable passes
+    (nero_tex_regions).  pad in [0, 64], border in [1, 16]."""
+    dev = _dev(mask)
+    mask = _to(mask, torch.uint8, dev)
+    h, w = mask.shape
+    with torch.cuda.device(dev):
+        ws = _ws(_lib.nero_tex_regions_workspace_bytes(h, w), dev)
+        region = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        L.check(_lib.nero_tex_regions(L.ptr(mask), h, w, int(pad), int(border), L.ptr(ws), L.ptr(region), L.stream_ptr()))
+    return region
+
+
+def fill_gutter(tex, region, pad=32, return_source=False):
+    """IN PLACE on tex uint8 [h, w, C] (or [h, w]): every region-3 texel takes the bytes of its nearest region-2 texel (squared Euclidean
+    distance in integers, ties to the lowest row-major index), searched within `pad` rows and columns (nero_tex_fill; :143-149).  -> tex, or
+    (tex, source int32 [h, w]: the source's row-major index, -1 where nothing was filled)."""
+    dev = _dev(tex)
+    if not (torch.is_tensor(tex) and tex.is_cuda and tex.dtype == torch.uint8 and tex.is_contiguous() and tex.dim() in (2, 3)):
+        raise TypeError('fill_gutter works in place on a contiguous CUDA uint8 tensor [h, w, C] or [h, w]')
+    h, w = tex.shape[:2]
+    region = _to(region, torch.uint8, dev)
+    if region.shape != (h, w):
+        raise ValueError(f'fill_gutter: region {tuple(region.shape)} does not match the map {(h, w)}')
+    with torch.cuda.device(dev):
+        src = torch.empty((h, w), dtype=torch.int32, device=dev) if return_source else None
+        L.check(_lib.nero_tex_fill(L.ptr(tex), L.ptr(region), h, w, 1 if tex.dim() == 2 else tex.shape[2], int(pad), L.ptr(src), L.stream_ptr()))
+    return (tex, src) if return_source else tex
+
+
+def downsample2(tex):
+    """uint8 [2h, 2w, C] (or [2h, 2w]) -> [h, w, C]: (a + b + c + d + 2) >> 2 per 2 x 2 block (nero_tex_downsample2; cv2.resize INTER_LINEAR at
+    an exact factor of two, :157-160)"""
+    dev = _dev(tex)
+    tex = _to(tex, torch.uint8, dev)
+    if tex.dim() not in (2, 3) or tex.shape[0] % 2 or tex.shape[1] % 2 or tex.shape[0] < 2 or tex.shape[1] < 2:
+        raise ValueError(f'downsample2 wants [2h, 2w, C] or [2h, 2w], got {tuple(tex.shape)}')
+    h, w = tex.shape[0] // 2, tex.shape[1] // 2
+    with torch.cuda.device(dev):
+        out = torch.empty((h, w) + tuple(tex.shape[2:]), dtype=torch.uint8, device=dev)
+        L.check(_lib.nero_tex_downsample2(L.ptr(tex), h, w, 1 if tex.dim() == 2 else tex.shape[2], L.ptr(out), L.stream_ptr()))
+    return out
+
+
+# ---- the built-in atlas ---------------------------------------------------------------------------------------------------------------------
+def simple_atlas(verts, tris, size):
+    """A deterministic atlas with one chart per triangle and no dependencies: -> (vt float32 [3T, 2], ft int32 [T, 3]).
+
+    A FALLBACK, not xatlas: every triangle becomes a right-angled chart of its own, so texture space is used poorly, texel density follows
+    nothing, and every edge is a seam.  A full-resolution marching-cubes mesh needs decimation first or a real unwrapper (pass its vt / ft to
+    bake_materials).  Layout: G = ceil(sqrt(ceil(T / 2))) cells per side, each s = size // G texels wide, origins on texel corners; triangles 2k
+    and 2k + 1 share cell k (row-major), one in the low corner, one in the high corner.  With n = s - 1 the first chart covers the texels
+    i + j <= p of the cell and the second those with i + j >= p + 3, i, j <= n - 1 (p = (2n - 5) // 2); the last row and column of a cell stay
+    empty.  So at `size` every chart covers at least one texel centre, and texels of two different charts are never 8-neighbours: at least
+    one uncovered texel lies between any two charts (two texel steps apart), at `size` and at any multiple of it.  All chart corners are
+    quarter texels, exact in float32.  Raises ValueError when the cells would be smaller than 4 texels, naming the smallest size that works."""
+    T = int(np.asarray(tris).shape[0])
+    size = int(size)
+    G = max(1, int(np.ceil(np.sqrt(np.ceil(T / 2)))))
+    while G * G * 2 < T:                                            # (float sqrt rounding)
+        G += 1
+    s = size // G
+    if s < 4:
+        raise ValueError(f'simple_atlas: {T} triangles need {G} x {G} cells; at size {size} a cell is {s} texels wide, below the minimum of 4: '
+                         f'the smallest size that works is {4 * G}')
+    n = s - 1
+    p = (2 * n - 5) // 2
+    q = p + 3
+    lo = np.array([[0.25, 0.25], [p + 1.25, 0.25], [0.25, p + 1.25]])
+    hi = np.array([[n - 0.25, n - 0.25], [q - n + 0.75, n - 0.25], [n - 0.25, q - n + 0.75]])
+    t = np.arange(T)
+    cell = t // 2
+    origin = np.stack([(cell % G) * s, (cell // G) * s], -1).astype(np.float64)          # (x, y) texels
+    local = np.where((t % 2 == 0)[:, None, None], lo[None], hi[None])                     # [T, 3, 2]
+    vt = ((origin[:, None, :] + local) / size).reshape(-1, 2).astype(np.float32)
+    ft = np.arange(3 * T, dtype=np.int32).reshape(T, 3)
+    return vt, ft
+
+
+# ---- the pipeline ---------------------------------------------------------------------------------------------------------------------------
+def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=1 << 19, border=3, return_intermediates=False):
+    """NeROMaterialRenderer -> {'albedo' [size, size, 3], 'metallic' [size, size], 'roughness' [size, size]: uint8 device tensors, 'mask'
+    [size, size] bool (a chart covers the texel), 'vt', 'ft'}: extract_materials_texture_map.py:89-160 on the device.
+
+    Rasterise the UV triangles at size * ssaa, interpolate the mesh vertices at the covered texels, evaluate predict_materials there in chunks
+    of `chunk` rows with the packed kernels cached (as predict_materials_of_vertices does), quantise, fill the `pad`-texel gutter at the
+    supersampled size, halve.  Channels follow predict_materials_n2m (network/field.py:925-932): albedo, metallic, roughness -- the network's
+    roughness WITHOUT the square root predict_materials_of_vertices applies.  vt / ft default to simple_atlas of the renderer's mesh at `size`;
+    pass an unwrapper's (xatlas) for a real asset.  The only host traffic is the count readbacks of rasterize_uv / interpolate.  The MLPs run
+    on this project's fp32-grade engine (the reference: fp16 autocast), so single 8-bit levels can differ from the reference's maps.
+    return_intermediates: also 'tri_id', 'texel', 'points', 'values' [n, 5], 'region', 'source' and 'texture' (the filled maps [H, W, 5])
+    at the supersampled size."""
+    if ssaa not in (1, 2):
+        raise ValueError(f'bake_materials: ssaa must be 1 or 2, got {ssaa}')
+    verts, tris = renderer.mesh_vertices, renderer.mesh_triangles
+    dev = next(renderer.parameters()).device
+    if dev.type != 'cuda':
+        raise RuntimeError('bake_materials runs on the GPU: move the renderer to a CUDA device first')
+    if (vt is None) != (ft is None):
+        raise ValueError('bake_materials: pass both vt and ft, or neither')
+    if vt is None:
+        vt, ft = simple_atlas(verts, tris, size)
+    if np.asarray(ft.cpu() if torch.is_tensor(ft) else ft).shape[0] != tris.shape[0]:
+        raise ValueError(f'bake_materials: ft has {len(ft)} faces, the mesh {tris.shape[0]}')
+    H = W = int(size) * ssaa
+    chunk = max(1, int(chunk))
+    with torch.cuda.device(dev), torch.no_grad():
+        vt_d, ft_d = _to(vt, torch.float32, dev, 2), _to(ft, torch.int32, dev, 3)
+        v_d, f_d = _to(verts, torch.float32, dev, 3), _to(tris, torch.int32, dev, 3)
+        tri_id = rasterize_uv(vt_d, ft_d, H, W)
+        texel, pts, mask = interpolate(tri_id, vt_d, ft_d, v_d, f_d, return_mask=True)
+        n = pts.shape[0]
+        values = torch.empty((n, 5), dtype=torch.float32, device=dev)
+        kern = renderer._kernels()
+        for i in range(0, n, chunk):
+            m, r, a = renderer.predict_materials(pts[i:i + chunk], kern)
+            values[i:i + chunk, 0:3] = a
+            values[i:i + chunk, 3:4] = m
+            values[i:i + chunk, 4:5] = r
+        tex = quantize(values, texel, H, W)
+        region = gutter_regions(mask, pad, border)
+        tex, src = fill_gutter(tex, region, pad, return_source=True) if return_intermediates else (fill_gutter(tex, region, pad), None)
+        tex_ss = tex
+        if ssaa == 2:
+            tex = downsample2(tex)
+            mask_out = mask.view(size, 2, size, 2).amax(dim=(1, 3)) > 0
+        else:
+            mask_out = mask > 0
+        out = {'albedo': tex[..., 0:3].contiguous(), 'metallic': tex[..., 3].contiguous(), 'roughness': tex[..., 4].contiguous(), 'mask': mask_out,
+               'vt': vt, 'ft': ft}
+        if return_intermediates:
+            out.update(tri_id=tri_id, texel=texel, points=pts, values=values, region=region, source=src, texture=tex_ss)
+    return out
+
+
+# ---- OBJ / MTL / PNG ------------------------------------------------------------------------------------------------------------------------
+def _np(x, dtype=None):
+    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return x if dtype is None else x.astype(dtype)
+
+
+def _png_chunk(tag, data):
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+
+
+def png_bytes(img):
+    """uint8 [h, w] (grey) or [h, w, 3] (RGB) -> the bytes of a non-interlaced 8-bit PNG (filter 0 on every row): the writer used where PIL is
+    not importable"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3):
+        raise ValueError(f'png_bytes: [h, w] or [h, w, 3] expected, got {img.shape}')
+    h, w = img.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, -1)], 1)
+    ihdr = struct.pack('>IIBBBBB', w, h, 8, 0 if img.ndim == 2 else 2, 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', ihdr) + _png_chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + _png_chunk(b'IEND', b'')
+
+
+def write_png(path, img, use_pil=None):
+    """lossless 8-bit PNG, image row 0 = array row 0 (as cv2.imwrite).  use_pil: None = PIL when importable, else the zlib writer above"""
+    img = np.ascontiguousarray(_np(img), dtype=np.uint8)
+    if use_pil is None or use_pil:
+        try:
+            from PIL import Image
+            Image.fromarray(img).save(path, format='PNG')
+            return
+        except ImportError:
+            if use_pil:
+                raise
+    with open(path, 'wb') as fh:
+        fh.write(png_bytes(img))
+
+
+def read_png(path):
+    """-> uint8 [h, w] or [h, w, C]: 8-bit grey / RGB / RGBA / grey+alpha non-interlaced PNG, all five row filters (what write_png and PIL
+    write), decoded without PIL"""
+    data = open(path, 'rb').read()
+    if data[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError(f'read_png: {path} is not a PNG')
+    at, idat, hdr = 8, [], None
+    while at < len(data):
+        n, tag = struct.unpack('>I4s', data[at:at + 8])
+        body = data[at + 8:at + 8 + n]
+        at += 12 + n
+        if tag == b'IHDR':
+            hdr = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+        elif tag == b'IEND':
+            break
+    w, h, depth, ctype, _, _, interlace = hdr
+    ch = {0: 1, 2: 3, 4: 2, 6: 4}.get(ctype)
+    if depth != 8 or ch is None or interlace:
+        raise ValueError(f'read_png: only 8-bit non-interlaced grey / RGB (with or without alpha) is supported, got depth {depth} type {ctype}')
+    raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8).reshape(h, 1 + w * ch)
+    out = np.zeros((h, w * ch), np.int32)
+    prev = np.zeros(w * ch, np.int32)
+    for y in range(h):
+        f, line = int(raw[y, 0]), raw[y, 1:].astype(np.int32)
+        if f == 0:
+            cur = line
+        elif f == 2:
+            cur = (line + prev) & 255
+        else:                                                       # filters that look left: sequential per channel
+            cur = np.zeros(w * ch, np.int32)
+            for i in range(w * ch):
+                a = cur[i - ch] if i >= ch else 0
+                b = prev[i]
+                c = prev[i - ch] if i >= ch else 0
+                if f == 1:
+                    pred = a
+                elif f == 3:
+                    pred = (a + b) >> 1
+                elif f == 4:
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+                else:
+                    raise ValueError(f'read_png: unknown row filter {f}')
+                cur[i] = (line[i] + pred) & 255
+        out[y] = cur
+        prev = cur
+    out = out.astype(np.uint8)
+    return out.reshape(h, w) if ch == 1 else out.reshape(h, w, ch)
+
+
+def _map_names(name):
+    cas = name[5:] if name.startswith('mesh_') and len(name) > 5 else name
+    return [f'feat{k}_{cas}.png' for k in range(3)]
+
+
+def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=None):
+    """the reference's OBJ / MTL layout (extract_materials_texture_map.py:166-197) in `dir`: <name>.obj with `v x y z`, `vt u 1-v`, 1-based
+    `f a/b` faces; <name>.mtl whose map_Kd names the albedo image; feat0_<cas>.png (albedo), feat1_<cas>.png (metallic), feat2_<cas>.png
+    (roughness), the two scalar maps as three equal channels (COLOR_GRAY2BGR), image row 0 = texel row 0.  maps: the dict bake_materials
+    returns.  Differences from the reference: lossless PNG instead of JPEG.  -> the path of the OBJ."""
+    os.makedirs(dir, exist_ok=True)
+    v = _np(verts, np.float64).reshape(-1, 3)
+    f = _np(tris, np.int64).reshape(-1, 3)
+    uv = _np(vt).reshape(-1, 2)
+    fuv = _np(ft, np.int64).reshape(-1, 3)
+    if f.shape != fuv.shape:
+        raise ValueError(f'write_textured_obj: {len(f)} faces but {len(fuv)} UV faces')
+    if f.size and (f.min() < 0 or f.max() >= len(v) or fuv.min() < 0 or fuv.max() >= len(uv)):
+        raise ValueError('write_textured_obj: a face index is out of range')
+    names = _map_names(name)
+    for fname, key in zip(names, ('albedo', 'metallic', 'roughness')):
+        img = np.ascontiguousarray(_np(maps[key]), dtype=np.uint8)
+        if img.ndim == 2:
+            img = np.repeat(img[..., None], 3, -1)
+        write_png(os.path.join(dir, fname), img, use_pil)
+    uv_out = np.stack([uv[:, 0].astype(np.float64), 1.0 - uv[:, 1].astype(np.float64)], -1)
+    faces = np.stack([f + 1, fuv + 1], -1).reshape(-1, 6)
+    obj = os.path.join(dir, name + '.obj')
+    with open(obj, 'w') as fh:
+        fh.write(f'mtllib {name}.mtl\n')
+        np.savetxt(fh, v, fmt='v %.9g %.9g %.9g')
+        np.savetxt(fh, uv_out, fmt='vt %.17g %.17g')
+        fh.write('usemtl defaultMat\n')
+        np.savetxt(fh, faces, fmt='f %d/%d %d/%d %d/%d')
+    with open(os.path.join(dir, name + '.mtl'), 'w') as fh:
+        fh.write(f'newmtl defaultMat\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nTr 1\nillum 1\nNs 0\nmap_Kd {names[0]}\n')
+    return obj
+
+
+def read_textured_obj(path, load_maps=True):
+    """what write_textured_obj writes -> {'v' float64 [V,3], 'f' int64 [T,3], 'vt' float32 [Vt,2] (the file's 1 - v undone), 'ft' int64 [T,3],
+    'mtllib', 'map_Kd', and with load_maps 'albedo' [h,w,3], 'metallic' [h,w], 'roughness' [h,w] uint8 from the PNGs beside it}"""
+    lines = open(path).read().split('\n')
+    pick = lambda key: [ln[len(key):] for ln in lines if ln.startswith(key)]
+    v = np.array([x.split() for x in pick('v ')], dtype=np.float64).reshape(-1, 3)
+    uv = np.array([x.split() for x in pick('vt ')], dtype=np.float64).reshape(-1, 2)
+    fl = pick('f ')
+    faces = np.array([x.replace('/', ' ').split() for x in fl], dtype=np.int64).reshape(len(fl), 3, 2) - 1
+    out = {'v': v, 'f': np.ascontiguousarray(faces[..., 0]), 'vt': np.stack([uv[:, 0], 1.0 - uv[:, 1]], -1).astype(np.float32),
+           'ft': np.ascontiguousarray(faces[..., 1]), 'mtllib': (pick('mtllib ') or [None])[0], 'map_Kd': None}
+    out['mtllib'] = out['mtllib'].strip() if out['mtllib'] else None
+    d = os.path.dirname(os.path.abspath(path))
+    if out['mtllib'] and os.path.exists(os.path.join(d, out['mtllib'])):
+        kd = [ln.split(None, 1)[1].strip() for ln in open(os.path.join(d, out['mtllib'])).read().split('\n') if ln.startswith('map_Kd ')]
+        out['map_Kd'] = kd[0] if kd else None
+    if load_maps and out['map_Kd'] and out['map_Kd'].startswith('feat0_'):
+        for k, key in enumerate(('albedo', 'metallic', 'roughness')):
+            p = os.path.join(d, f'feat{k}_' + out['map_Kd'][6:])
+            if os.path.exists(p):
+                img = read_png(p)
+                out[key] = img if k == 0 else np.ascontiguousarray(img[..., 0])
+    return out

@@ -1,0 +1,70 @@
+#!/usr/bin/env python
+"""Bake the Stage-II materials into albedo / metallic / roughness texture maps and write the textured OBJ (the reference's
+extract_materials_texture_map.py) through nero_amd.texture -- no xatlas / nvdiffrast / scipy / sklearn / cv2.
+
+    python scripts/extract_texture_maps.py --cfg configs/material/syn/bell.yaml --ckpt data/model/bell_material/model.pth --out data/materials/bell
+    python scripts/extract_texture_maps.py --mesh mesh.ply --ckpt model.pth --uv atlas.npz --size 2048 --out out_dir
+
+--cfg: the material YAML (or JSON); its `mesh` entry names the Stage-I mesh unless --mesh does.  --ckpt: a trainer checkpoint (the
+`network_state_dict` entry) or a bare state dict; without it the maps show the freshly initialised network (a dry run of the pipeline).
+--uv: an .npz with `vt` [nvt, 2] in [0, 1] and `ft` [T, 3] from any unwrapper (xatlas: `vmapping, ft, vt = xatlas.parametrize(v, f)`); without it
+the built-in one-chart-per-triangle atlas is used, which needs size >= 4 * ceil(sqrt(T / 2)) -- a fallback for small or decimated meshes."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def load_cfg(path):
+    text = open(path).read()
+    if path.endswith('.json'):
+        return json.loads(text)
+    import yaml
+    return yaml.safe_load(text)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--cfg')
+    ap.add_argument('--ckpt')
+    ap.add_argument('--mesh', help='PLY of the Stage-I mesh (overrides the cfg entry)')
+    ap.add_argument('--size', type=int, default=1024)
+    ap.add_argument('--ssaa', type=int, default=2, choices=(1, 2))
+    ap.add_argument('--pad', type=int, default=32)
+    ap.add_argument('--uv', help='.npz holding vt and ft')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--name', default='mesh_0')
+    args = ap.parse_args()
+    if not (args.cfg or args.mesh):
+        ap.error('give --cfg (with a mesh entry) or --mesh')
+    from nero_amd import texture as TX
+    from nero_amd.mesh import read_ply
+    from nero_amd.renderer import NeROMaterialRenderer
+    cfg = load_cfg(args.cfg) if args.cfg else {}
+    mesh_path = args.mesh or cfg['mesh']
+    v, f = read_ply(mesh_path)
+    net = NeROMaterialRenderer({k: cfg[k] for k in ('shader_cfg', 'database_name') if k in cfg}, is_train=False, mesh=(v, f))
+    if args.ckpt:
+        sd = torch.load(args.ckpt, map_location='cpu')
+        net.load_state_dict(sd.get('network_state_dict', sd))
+    else:
+        print('no --ckpt: baking the freshly initialised network', file=sys.stderr)
+    net = net.cuda().eval()
+    vt = ft = None
+    if args.uv:
+        z = np.load(args.uv)
+        vt, ft = z['vt'], z['ft']
+    maps = net.extract_texture_maps(vt=vt, ft=ft, size=args.size, ssaa=args.ssaa, pad=args.pad)
+    obj = TX.write_textured_obj(args.out, net.mesh_vertices, net.mesh_triangles, maps['vt'], maps['ft'], maps, name=args.name)
+    print(json.dumps({'obj': obj, 'size': args.size, 'ssaa': args.ssaa, 'pad': args.pad, 'triangles': int(len(f)),
+                      'covered_texels': int(maps['mask'].sum()), 'atlas': 'given' if args.uv else 'simple_atlas'}))
+
+
+if __name__ == '__main__':
+    main()
