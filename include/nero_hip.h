@@ -764,6 +764,37 @@ int nero_tex_regions(const unsigned char* mask, int h, int w, int pad, int borde
 int nero_tex_fill(unsigned char* tex, const unsigned char* region, int h, int w, int C, int pad, int* src /*or NULL*/, void* stream);
 int nero_tex_downsample2(const unsigned char* in, int h, int w, int C, unsigned char* out, void* stream);
 
+/* ---- validation metrics: PSNR and SSIM of 8-bit images (nero_amd/csrc/image_metrics.hip) --------------------------------------------------
+ * What ShapeRenderMetrics / MaterialRenderMetrics (network/metrics.py:39-102) compute per validation view, on images that stay on the device.
+ * Host counterpart: nero_amd/metrics.py.  The calls never allocate and never synchronise; no atomics; every result is bit-identical run to
+ * run and independent of what the workspace held before.
+ *
+ * nero_img_quantize -- color_map_backward, `np.clip(rgb * 255, 0, 255).astype(np.uint8)` (utils/base_utils.py:453-456).  in [n] fp32 -> out [n]
+ *   uint8: one fp32 multiply by 255 (never contracted with anything), clamped to [0, 255], truncated towards zero.  +inf -> 255, -inf -> 0,
+ *   NaN -> 0: numpy leaves the cast of NaN to uint8 undefined, so the value 0 is THIS PROJECT'S definition, not the reference's.  n = 0 is a
+ *   no-op; n < 0 is NERO_ERR_ARG.
+ * nero_img_metrics -- compute_psnr (network/metrics.py:11-17) and `structural_similarity(gt, pr, win_size=11, channel_axis=2, data_range=255)`
+ *   (network/metrics.py:50, 85; skimage's defaults otherwise) of B image pairs.  gt, pr [B, h, w, C] uint8, row-major, channels interleaved ->
+ *     sse [B] uint64 (may be NULL): the exact sum of squared differences over the h w C bytes of image b;
+ *     ssim_c [B, C] fp64 (may be NULL): the SSIM of each channel;
+ *     out [B, 2] fp64: {psnr, ssim}.  psnr = 10 log10(65025 / (sse / (h w C))), +inf when sse = 0 -- the exact value; the reference averages
+ *       in float32 and is up to 2e-3 dB off it at 800 x 800.  ssim = the mean of ssim_c over the channels.
+ *   SSIM per channel: uniform 11 x 11 window; with sx, sy, sxx, syy, sxy the window's sums of x, y, x^2, y^2, x y (exact integers),
+ *     ux = sx / 121, uy = sy / 121, vx = (121 sxx - sx^2) / (121 * 120) (the sample covariance: skimage's 121 / 120 normalisation), vy and vxy
+ *     likewise, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) in fp64;
+ *     ssim_c = the mean of S over the (h - 10)(w - 10) window positions that lie wholly inside the image (skimage crops 5 pixels per side, so
+ *     its filter's border mode never reaches the result).  This is this project's statement of skimage's algorithm: skimage itself is not
+ *     available to it.
+ *   The sums of S are added in a fixed order: per 32 x 32 tile of window positions (within a thread by rising row, a shuffle tree across the
+ *     wave, the four waves in order), then the tiles of an image (thread t takes tiles t, t + 256, ... by rising index, then the same tree).
+ *   Limits: B in [1, 65535], h and w in [11, 16384] (skimage raises for a window larger than the image), C in [1, 4]; anything else is
+ *   NERO_ERR_ARG before any launch.  ws: nero_img_metrics_workspace_bytes(B, h, w, C) bytes, 8-byte aligned (40 bytes per tile and image;
+ *   0 = a refused shape). */
+int nero_img_quantize(const float* in, int64_t n, unsigned char* out, void* stream);
+size_t nero_img_metrics_workspace_bytes(int64_t B, int h, int w, int C);
+int nero_img_metrics(const unsigned char* gt, const unsigned char* pr, int64_t B, int h, int w, int C, void* ws, unsigned long long* sse /*or NULL*/,
+                     double* ssim_c /*or NULL*/, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
