@@ -795,6 +795,33 @@ size_t nero_img_metrics_workspace_bytes(int64_t B, int h, int w, int C);
 int nero_img_metrics(const unsigned char* gt, const unsigned char* pr, int64_t B, int h, int w, int C, void* ws, unsigned long long* sse /*or NULL*/,
                      double* ssim_c /*or NULL*/, double* out, void* stream);
 
+/* ---- the learned environment light as a lat-long panorama (nero_amd/csrc/envlight.hip) ------------------------------------------------------
+ * What MCShadingNetwork.env_light / get_env_light (network/field.py:1020-1059) compute, around the outer_light chain of the MLP engine.
+ * Host counterpart: nero_amd/envlight.py.  The calls never allocate and never synchronise; every output is a function of the pixel (or row)
+ * alone, so results are bit-identical run to run and for every split of a panorama into windows.
+ *
+ * nero_env_encode -- the direction grid (:1021-1034) and sph_enc(pts, 0) of predict_outer_lights_pts (:1049-1055) for the pixels
+ *   first .. first + n - 1 (row-major) of an h x w panorama.  Pixel (row r, column c): az = linspace(1, 0, w)[c] 2 pi - pi / 2,
+ *   el = linspace(1, -1, h)[r] pi / 2 (a one-element linspace is its start value), formed in fp64 on the device from the pixel index;
+ *   d = (cos el cos az, cos el sin az, sin el) when is_real, else (cos el sin az, sin el, cos el cos az), rounded once to fp32.
+ *   X [NERO_ROW_PAD(n), 72] = IDE(d, roughness) (generate_ide_fn(5), utils/ref_utils.py:85-117; roughness = kappa_inv, 0 in Stage II);
+ *   sphere != 0: X [NERO_ROW_PAD(n), 144] = the same 72 columns twice ('sphere_direction').  Rows n .. NERO_ROW_PAD(n) - 1 are written as
+ *   zero rows: the layout nero_mc_encode_miss gives the chain engine.  dirs [n, 3] (may be NULL) receives d.  X may be NULL when dirs is
+ *   not (directions only).  On the z axis the reference's IDE is NaN (its complex power of 0); here it is the finite limit.
+ *   h, w in [1, 16384], the window inside the panorama, roughness >= 0, else NERO_ERR_ARG.
+ * nero_env_encode_dirs -- the same rows for n given directions src [n, 3] (get_env_light's light_pts, :1058-1059).
+ * nero_env_finish -- raw [rows, 4] (the chain's head output, columns 0-2) -> rgb [n, 3] = exp(min(raw, exp_max)) (ExpActivation,
+ *   network/field.py:301-307), then linear_to_srgb (utils/raw_utils.py:4-10) when gamma != 0.  No clamp to 1, as in the reference.
+ * nero_env_rgbe -- Radiance RGBE of rgb [n, 3] fp32 -> out [n, 4] bytes: v = max(r, g, b) with negative channels counted as 0; v < 1e-32
+ *   gives (0, 0, 0, 0); otherwise v = m 2^e with m in [0.5, 1), the colour bytes are trunc(c 2^(8 - e)) (an exact product: the scale is a power
+ *   of two, nothing is divided) and the fourth byte is e + 128.  Decoding is byte 2^(E - 136).  v >= 2^127 (or not finite) saturates at
+ *   e = 127 with bytes capped at 255; the host writer refuses such images.  n in [0, 2^30] for both. */
+int nero_env_encode(int h, int w, int64_t first, int n, int is_real, int sphere, float roughness, float* X /*or NULL*/, float* dirs /*or NULL*/,
+                    void* stream);
+int nero_env_encode_dirs(const float* src, int n, int sphere, float roughness, float* X, void* stream);
+int nero_env_finish(const float* raw, int64_t n, float exp_max, int gamma, float* rgb, void* stream);
+int nero_env_rgbe(const float* rgb, int64_t n, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

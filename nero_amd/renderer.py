@@ -378,6 +378,21 @@ class NeROShapeRenderer(nn.Module):
             self._kern_cache = (key, (names, eff, K))
         return names, eff, K
 
+    def env_light(self, h, w, gamma=True, roughness=0.0, chunk=None):
+        """the illumination AppShadingNetwork.outer_light has learned, as an h x w lat-long panorama: float32 [h, w, 3] on the device.  The
+        reference has no such method for Stage I; this is MCShadingNetwork.env_light (network/field.py:1020-1047) on the Stage-I light: the
+        predictor's inputs are IDE(d, roughness) -- with shader_config.sphere_direction the same encoding twice -- so roughness 0 is the light
+        itself and a roughness above 0 the light pre-filtered for that roughness, as predict_specular_lights sees it.  light_exp_max comes from
+        shader_config, the axis convention from database_name (z up for 'real...', else y up); conventions, chunking and the finite value
+        on the z axis: nero_amd.envlight.  gamma: linear_to_srgb, not clamped."""
+        from . import envlight
+        dev = next(self.parameters()).device
+        with torch.no_grad():
+            _, _, K = self._kernels()
+            scfg = self.color_network.cfg
+            return envlight.render_env_light(K.outer_light, h, w, str(self.cfg['database_name']).startswith('real'), K.sphere,
+                                             scfg['light_exp_max'], gamma, roughness, chunk, dev)
+
     def sample_ray(self, rays_o, rays_d, near, far, perturb, rand1=None, rand_bg=None, K=None, trace=None):
         """network/renderer.py:403-443 on the HIP sampler.  rand1 [R,1] / rand_bg [R,n_bg]: optional explicit uniform draws
         (default: torch.rand on the device when perturb > 0, like the reference)."""
@@ -780,6 +795,26 @@ class NeROMaterialRenderer(nn.Module):
         bake_materials(self, **kw) -- vt / ft of any unwrapper, or the built-in simple_atlas"""
         from .texture import bake_materials
         return bake_materials(self, **kw)
+
+    def env_light(self, h, w, gamma=True, chunk=None):
+        """MCShadingNetwork.env_light (network/field.py:1020-1047): the estimated illumination as an h x w lat-long panorama, float32 [h, w, 3]
+        on the device -- the outer_light predictor at IDE(d, 0) of every pixel's direction ('sphere_direction': the encoding twice), through
+        exp(min(., light_exp_max)) and, with gamma, linear_to_srgb; never clamped.  is_real, outer_light_version and light_exp_max come from
+        shader_cfg.  Runs on the cached packed kernels in chunks of `chunk` pixels (same bits for every chunk).  Unlike the reference, the
+        pixel whose direction lies exactly on the z axis is finite (nero_amd.envlight)."""
+        from . import envlight
+        dev = next(self.parameters()).device
+        with torch.no_grad():
+            _, _, K = self._kernels()
+            scfg = self.shader_network.cfg
+            return envlight.render_env_light(K.outer_light, h, w, scfg['is_real'], K.sphere, scfg['light_exp_max'], gamma, 0.0, chunk, dev)
+
+    def get_env_light(self):
+        """MCShadingNetwork.get_env_light (network/field.py:1058-1059): the linear outer light at the 8192 Fibonacci light_pts, [8192, 3]"""
+        from . import envlight
+        with torch.no_grad():
+            _, _, K = self._kernels()
+            return envlight.eval_env_light(K.outer_light, self.shader_network.light_pts, K.sphere, self.shader_network.cfg['light_exp_max'])
 
     def shade_train(self, pts, view_dirs, normals, human_poses, rgb_gt, step, rand_d=None, rand_s=None, reg_ang=None, reg_eps=None):
         """the arithmetic of train_step (network/renderer.py:837-844) for an explicit batch"""
