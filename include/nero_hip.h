@@ -664,6 +664,39 @@ int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, v
 int nero_mcubes_emit(const float* u, int nx, int ny, int nz, float threshold, void* ws, float* verts, int64_t v_cap, int* tris, int64_t t_cap,
                      void* stream);
 
+/* ---- mesh clean-up: connected components of the extracted mesh and their removal (nero_amd/csrc/mesh_clean.hip) -------------------------
+ * A marching-cubes surface of a learned SDF holds floaters, hidden inner shells and scraps of the support surface.  The reference has no
+ * counterpart (its users delete them in a mesh editor); Stage II traces its secondary rays against whatever the mesh holds.  Host
+ * counterpart: nero_amd/mesh.py.
+ *   tris [T,3] int32 over V vertices, verts [V,3] fp32; 0 <= V, T < 2^31 (else NERO_ERR_UNSUPPORTED); V = 0 and T = 0 are valid and launch
+ *   nothing over zero items.  Two vertices are connected when a triangle holds both.  Degenerate and duplicate triangles and non-manifold
+ *   edges are ordinary input.  A triangle with an index outside [0, V) is skipped by every kernel and never dereferenced.
+ *   No floating-point atomics, no atomics that decide a position or a label: every result is bit-identical run to run.
+ * nero_mesh_cc_label -- label [V] = the smallest vertex index of the vertex's component (an unreferenced vertex is a component of its own).
+ *   A concurrent union-find: label doubles as the parent array, every change of it is an agent-scope compare-and-swap or minimum, and a
+ *   launch of its own flattens it; near-linear in V + T whatever the diameter of the mesh graph.  info [2] (device int64) = {K, the number
+ *   of components; the number of skipped triangles}.  Never synchronises: the caller reads info.
+ * nero_mesh_cc_stats -- label and K as nero_mesh_cc_label gave them -> comp [V] = the component of each vertex, numbered 0..K-1 in ascending
+ *   order of the smallest vertex, and per component n_verts [K], n_faces [K] (a face belongs to the component of its first vertex), area [K]
+ *   float64 (0.5 |(b - a) x (c - a)| in float64 from the fp32 vertices; the faces of a component, in ascending order, are cut into pieces of
+ *   2048, a wave sums a piece and then the pieces: two fixed levels, the same bits every run), bbox_min / bbox_max [K,3] fp32 (exact; -0
+ *   orders below +0).  Never synchronises.  ws: nero_mesh_cc_stats_workspace_bytes(V, T) (20 V + 16 T bytes + the sort's scratch).
+ * nero_mesh_compact_count -- keep [K] bytes (non-zero = the component stays) -> totals [2] (device int64) = {V', T'}: the triangles of the
+ *   kept components and the vertices they use (an unreferenced vertex is always dropped); also kept in the workspace.
+ * nero_mesh_compact_emit -- same tris, sizes and workspace as the count before it -> verts_out [V',3], tris_out [T',3] in their original
+ *   relative order with the indices remapped, vmap [V] (may be NULL) = the new index of each vertex or -1.  As nero_mcubes_emit it first
+ *   reads the 16-byte totals back on `stream`, its one synchronisation, and fails with nothing written when V' > v_cap or T' > t_cap
+ *   (NERO_ERR_ARG).  ws of both: nero_mesh_compact_workspace_bytes(V, T) (8 V + 8 T bytes + the scan's scratch). */
+int nero_mesh_cc_label(const int* tris, int64_t T, int64_t V, int* label, int64_t* info /*device, {K, skipped}*/, void* stream);
+size_t nero_mesh_cc_stats_workspace_bytes(int64_t V, int64_t T);
+int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V, const int* label, int64_t K, void* ws, int* comp,
+                       int* n_verts, int* n_faces, double* area, float* bbox_min, float* bbox_max, void* stream);
+size_t nero_mesh_compact_workspace_bytes(int64_t V, int64_t T);
+int nero_mesh_compact_count(const int* tris, int64_t T, int64_t V, const int* comp, const unsigned char* keep, int64_t K, void* ws,
+                            int64_t* totals /*device, {V', T'}*/, void* stream);
+int nero_mesh_compact_emit(const float* verts, const int* tris, int64_t T, int64_t V, void* ws, float* verts_out, int64_t v_cap, int* tris_out,
+                           int64_t t_cap, int* vmap /*or NULL*/, void* stream);
+
 /* ---- geometry evaluation: Chamfer distance of the extracted mesh (nero_amd/csrc/geom_eval.hip) --------------------------------------------
  * The reference's only geometry metric (eval_synthetic_shape.py, eval_real_shape.py, eval.md) without nvdiffrast / open3d / trimesh.  No
  * atomics decide a value or a position: every result is bit-identical run to run.  Host counterpart: nero_amd/eval_shape.py.

@@ -5,7 +5,10 @@ reads it with trimesh (extract_mesh.py:34-37, network/renderer.py:704).  This mo
   * marching_cubes_device(u, threshold): the HIP kernels on a CUDA grid -> device tensors;
   * marching_cubes(volume, isovalue): PyMCubes' signature on numpy arrays, so `sys.modules['mcubes'] = nero_amd.mesh` runs the reference's own
     extract_geometry / extract_mesh.py unmodified (INTEGRATION.md);
-  * write_ply / read_ply: the binary PLY the reference's Stage II reads (`cfg['mesh']`).
+  * write_ply / read_ply: the binary PLY the reference's Stage II reads (`cfg['mesh']`);
+  * connected_components_device / clean_mesh_device / clean_mesh: the connected components of a mesh, their statistics, and the mesh without
+    the unwanted ones (floaters, inner shells, scraps of the support surface), on the device (nero_mesh_*).  The reference has no
+    counterpart: its users delete the debris in a mesh editor.
 Conventions (include/nero_hip.h): a corner is inside when u < threshold; vertices are index-space, one per crossing grid edge, ordered by
 (linear grid index, axis x<y<z); triangles are ordered by (cell, table position) and wound so that their normals point into u < threshold --
 inward for an SDF, which NeROMaterialRenderer.trace flips to outward shading normals."""
@@ -24,6 +27,16 @@ L.lib.nero_mcubes_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
 L.lib.nero_mcubes_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
 L.lib.nero_mcubes_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_int64, C.c_void_p]
+L.lib.nero_mesh_cc_label.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+L.lib.nero_mesh_cc_stats_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mesh_cc_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+L.lib.nero_mesh_cc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+L.lib.nero_mesh_compact_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mesh_compact_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+L.lib.nero_mesh_compact_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+L.lib.nero_mesh_compact_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_void_p]
 
 
 def workspace_bytes(shape):
@@ -76,6 +89,141 @@ def index_to_world(verts, resolution, bound_min, bound_max):
     bmax = np.asarray(bound_max.detach().cpu().numpy() if torch.is_tensor(bound_max) else bound_max)
     v = np.asarray(verts, dtype=np.float64)
     return v / (resolution - 1.0) * (bmax - bmin)[None, :] + bmin[None, :]
+
+
+# ---- connected components and clean-up ---------------------------------------------------------------------------------------------------
+class MeshComponents:
+    """the connected components of a mesh (connected_components_device): K, and on the mesh's device label int32 [V] (the smallest vertex
+    of each vertex's component), comp int32 [V] (the component of each vertex, numbered in ascending order of the smallest vertex), n_verts /
+    n_faces int32 [K] (a face belongs to the component of its first vertex), area float64 [K], bbox_min / bbox_max float32 [K,3]"""
+    __slots__ = ('K', 'label', 'comp', 'n_verts', 'n_faces', 'area', 'bbox_min', 'bbox_max')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def table(self):
+        """-> one dict per component, on the host (for reports)"""
+        cols = [getattr(self, k).tolist() for k in self.__slots__[3:]]
+        return [{'component': i, 'n_verts': nv, 'n_faces': nf, 'area': a, 'bbox_min': lo, 'bbox_max': hi}
+                for i, (nv, nf, a, lo, hi) in enumerate(zip(*cols))]
+
+
+class CleanInfo:
+    """what clean_mesh_device did: components (MeshComponents of the input), keep bool [K] (the components that stayed), vmap int32 [V]
+    (the new index of every input vertex, -1 where it was dropped)"""
+    __slots__ = ('components', 'keep', 'vmap')
+
+    def __init__(self, components, keep, vmap):
+        self.components, self.keep, self.vmap = components, keep, vmap
+
+
+def _check_mesh(fn, verts, tris):
+    ok_v = torch.is_tensor(verts) and verts.is_cuda and verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    ok_t = torch.is_tensor(tris) and tris.is_cuda and tris.dtype == torch.int32 and tris.dim() == 2 and tris.shape[1] == 3
+    if not (ok_v and ok_t and verts.device == tris.device):
+        d = lambda x: f'{tuple(x.shape)} {x.dtype} {x.device.type}' if torch.is_tensor(x) else type(x).__name__
+        raise TypeError(f'{fn} wants CUDA float32 [V,3] vertices and CUDA int32 [T,3] triangles on one device, got {d(verts)} and {d(tris)}')
+    if verts.shape[0] >= _INT31 or tris.shape[0] >= _INT31:
+        raise L.NeroHipError(f'{fn}: {verts.shape[0]} vertices / {tris.shape[0]} triangles: 2^31 or more')
+    return verts.contiguous(), tris.contiguous()
+
+
+def connected_components_device(verts, tris):
+    """verts CUDA float32 [V,3], tris CUDA int32 [T,3] -> MeshComponents.  Two vertices are connected when a triangle holds both; an
+    unreferenced vertex is a component of its own with no face.  One readback of 16 bytes (K and the out-of-range flag) sizes the
+    statistics.  A triangle index outside [0, V) raises ValueError (the kernels skip such a triangle, they never follow it)."""
+    verts, tris = _check_mesh('connected_components_device', verts, tris)
+    V, T = verts.shape[0], tris.shape[0]
+    dev = verts.device
+    need = int(L.lib.nero_mesh_cc_stats_workspace_bytes(V, T))
+    L.check_workspace_fits(need + 8 * V, dev, what='connected-components workspace')
+    with torch.cuda.device(dev):
+        s = L.stream_ptr()
+        label = torch.empty(V, dtype=torch.int32, device=dev)
+        info = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(L.lib.nero_mesh_cc_label(L.ptr(tris) if T else None, T, V, L.ptr(label) if V else None, L.ptr(info), s))
+        K, bad = (int(x) for x in info.tolist())
+        if bad:
+            raise ValueError(f'connected_components_device: {bad} of {T} triangles hold a vertex index outside [0, {V})')
+        comp = torch.empty(V, dtype=torch.int32, device=dev)
+        out = MeshComponents(K=K, label=label, comp=comp, n_verts=torch.empty(K, dtype=torch.int32, device=dev),
+                             n_faces=torch.empty(K, dtype=torch.int32, device=dev), area=torch.empty(K, dtype=torch.float64, device=dev),
+                             bbox_min=torch.empty((K, 3), dtype=torch.float32, device=dev),
+                             bbox_max=torch.empty((K, 3), dtype=torch.float32, device=dev))
+        if V:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            L.check(L.lib.nero_mesh_cc_stats(L.ptr(verts), L.ptr(tris) if T else None, T, V, L.ptr(label), K, L.ptr(ws), L.ptr(comp),
+                                             L.ptr(out.n_verts), L.ptr(out.n_faces), L.ptr(out.area), L.ptr(out.bbox_min),
+                                             L.ptr(out.bbox_max), s))
+    return out
+
+
+def select_components(n_faces, keep=None, min_faces=0, min_face_ratio=0.0):
+    """the selection rule of clean_mesh_device on the face counts n_faces [K] (a tensor on any device) -> bool [K].  keep: 'largest' (= 1) or
+    an integer k: the k components with the most faces, ties towards the smaller component number; min_faces: at least that many faces;
+    min_face_ratio: at least that fraction of the largest component's face count (compared in float64).  The rules intersect."""
+    if keep == 'largest':
+        keep = 1
+    if keep is not None and (isinstance(keep, bool) or not isinstance(keep, int) or keep < 0):
+        raise ValueError(f"keep must be None, 'largest' or a non-negative integer, got {keep!r}")
+    if min_faces < 0 or not 0.0 <= min_face_ratio <= 1.0:
+        raise ValueError(f'min_faces must be >= 0 and min_face_ratio in [0, 1], got {min_faces} and {min_face_ratio}')
+    flags = torch.ones(n_faces.shape[0], dtype=torch.bool, device=n_faces.device)
+    if n_faces.shape[0] == 0:
+        return flags
+    if keep is not None:
+        order = torch.sort(n_faces, descending=True, stable=True).indices
+        flags = torch.zeros_like(flags)
+        flags[order[:keep]] = True
+    if min_faces:
+        flags &= n_faces >= int(min_faces)
+    if min_face_ratio:
+        flags &= n_faces.double() >= float(min_face_ratio) * n_faces.max().double()
+    return flags
+
+
+def clean_mesh_device(verts, tris, keep=None, min_faces=0, min_face_ratio=0.0):
+    """verts CUDA float32 [V,3], tris CUDA int32 [T,3] -> (verts', tris', CleanInfo): the mesh without the components the rules reject
+    (select_components) and without unreferenced vertices, the survivors in their original relative order.  With no rule only the
+    unreferenced vertices go."""
+    cc = connected_components_device(verts, tris)
+    verts, tris = verts.contiguous(), tris.contiguous()
+    V, T, K = verts.shape[0], tris.shape[0], cc.K
+    dev = verts.device
+    flags = select_components(cc.n_faces, keep, min_faces, min_face_ratio)
+    need = int(L.lib.nero_mesh_compact_workspace_bytes(V, T))
+    L.check_workspace_fits(need, dev, what='mesh-compaction workspace')
+    with torch.cuda.device(dev):
+        s = L.stream_ptr()
+        keep_u8 = flags.to(torch.uint8)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(L.lib.nero_mesh_compact_count(L.ptr(tris) if T else None, T, V, L.ptr(cc.comp) if V else None, L.ptr(keep_u8) if K else None,
+                                              K, L.ptr(ws), L.ptr(totals), s))
+        V2, T2 = (int(x) for x in totals.tolist())
+        L.check_workspace_fits(12 * (V2 + T2) + 4 * V, dev, what='cleaned mesh')
+        v2 = torch.empty((V2, 3), dtype=torch.float32, device=dev)
+        f2 = torch.empty((T2, 3), dtype=torch.int32, device=dev)
+        vmap = torch.empty(V, dtype=torch.int32, device=dev)
+        L.check(L.lib.nero_mesh_compact_emit(L.ptr(verts) if V else None, L.ptr(tris) if T else None, T, V, L.ptr(ws), L.ptr(v2) if V2 else None,
+                                             V2, L.ptr(f2) if T2 else None, T2, L.ptr(vmap) if V else None, s))
+    return v2, f2, CleanInfo(cc, flags, vmap)
+
+
+def clean_mesh(v, f, **rules):
+    """clean_mesh_device on numpy arrays (e.g. what read_ply returns), computed on the current CUDA device: -> (vertices float64 [V',3],
+    triangles int64 [T',3], CleanInfo).  The device works on a float32 copy of the vertices (statistics only: the clean-up selects, it
+    computes no coordinate); the vertices returned are the caller's own rows, so float64 input keeps its bits."""
+    v = np.asarray(v).reshape(-1, 3)
+    f = np.asarray(f).reshape(-1, 3)
+    if f.size and (f.min() < -_INT31 or f.max() >= _INT31):
+        raise ValueError('clean_mesh: a face index does not fit int32')
+    vd = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
+    fd = torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32)).cuda()
+    _, f2, info = clean_mesh_device(vd, fd, **rules)
+    kept = np.nonzero(info.vmap.cpu().numpy() >= 0)[0]
+    return v[kept].astype(np.float64), f2.cpu().numpy().astype(np.int64), info
 
 
 # ---- PLY --------------------------------------------------------------------------------------------------------------------------------
