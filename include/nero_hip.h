@@ -277,7 +277,13 @@ int nero_pe_vjp(const float* x, int ldx, const float* e0, int ld0, const float* 
 int nero_pe_jvp(const float* x, int ldx, const float* t, int ldt, int n_freq, int n, float* out, int ldo, void* stream);
 
 /* ---- hierarchical sampling (NeROShapeRenderer.sample_ray / upsample / cat_z_vals, network/renderer.py:355-443;
- *      sample_pdf, network/field.py:399-429).  Per-ray tables: z [R, ldz], sdf [R, lds]. ------------------------------- */
+ *      sample_pdf, network/field.py:399-429).  Per-ray tables: z [R, ldz], sdf [R, lds].
+ *      Argument ranges (anything else: NERO_ERR_ARG before a launch, nothing written; R == 0 returns NERO_OK):
+ *        nero_coarse_z      1 <= n <= 160, ldz >= n;           nero_background_z  n_bg >= 0, col0 >= 0, ldz >= col0 + n_bg
+ *        nero_upsample / nero_sample_pdf   2 <= n <= 160, 0 <= m <= 32  (n <= 128: one wavefront per ray, else one thread per ray)
+ *        nero_merge_sorted  n >= 1, m >= 0, n + m <= 160          (n <= 128 and m <= 64: one wavefront per ray, else one thread per ray)
+ *      Row pitches (ldz, lds, ldb, ldw) may exceed the row length; columns beyond it are neither read nor written.
+ *      z_new / w_out / inds_out / index_out are dense: [R,m], [R,n-1], [R,m], [R,n+m]. ----------------------------------------- */
 int nero_coarse_z(const float* near, const float* far, const float* rand1 /*[R] or NULL*/, int R, int n, float* z, int ldz, void* stream);
 int nero_background_z(const float* far, const float* rand_bg /*[R,n_bg] or NULL*/, int R, int n_bg, float* z, int ldz, int col0, void* stream);
 /* PE-6 rows (ld 40) of the points o + d*z[r, col0+j], row = r*ncols + j */
@@ -288,10 +294,12 @@ int nero_upsample(const float* o, const float* d, const float* z, int ldz, const
                   const float* variance, float inv_s_cap, int m, int R, float* z_new, float* w_out, int* inds_out, void* stream);
 /* deterministic inverse-CDF sampling from given bins/weights; inds = searchsorted(cdf, u, right=True) (bit-exact contract) */
 int nero_sample_pdf(const float* bins, int ldb, const float* w, int ldw, int n, int m, int R, float* out, int* inds_out, void* stream);
-/* stable in-place merge of sorted z[r,0..n) with sorted z_new[r,0..m); sdf permuted alike (sdf/sdf_new may be NULL);
- * sdf_new is read with stride ldsn; index_out int32 [R,n+m] optional = position in the concatenation [z, z_new] */
+/* stable in-place merge of sorted z[r,0..n) with sorted z_new[r,0..m), ties: z first; z[r,0..n+m) is written.  sdf[r,0..n+m) is permuted
+ * alike when BOTH sdf and sdf_new are given (either NULL: the table is left alone); sdf_new is dense [R,m] read with element stride ldsn
+ * (column 0 of a head output [rows,4] -> ldsn = 4); index_out int32 [R,n+m] optional = position in the concatenation [z, z_new] */
 int nero_merge_sorted(float* z, int ldz, int n, float* sdf, int lds, const float* z_new, int m, const float* sdf_new, int ldsn,
                       int R, int* index_out, void* stream);
+/* sdf[r, i] = src[(r*n + i) * ld_src], i < n  (column 0 of a head output [rows,4] -> ld_src = 4) */
 int nero_scatter_sdf(const float* src, int ld_src, int R, int n, float* sdf, int lds, void* stream);
 
 /* ---- occlusion-loss march along the reflected rays (compute_occ_loss, network/renderer.py:522-548; get_intersection /
@@ -299,12 +307,15 @@ int nero_scatter_sdf(const float* src, int ld_src, int R, int n, float* sdf, int
 int nero_occ_candidates(const float* x4, const float* sdf4, const float* grad, const int* idx, const float* d, int T, float thresh,
                         int n, unsigned char* flag, void* stream);
 int nero_occ_z(const float* o, const float* d, int P, int n, float* z /*[P,n]*/, void* stream);
-/* sdf is read as sdf[(p*n+i)*lds] (column 0 of a head output [rows,4] -> lds = 4); w_out [P,n-1] and/or wsum [P] */
+/* sdf is read as sdf[(p*n+i)*lds] (column 0 of a head output [rows,4] -> lds = 4); w_out [P,n-1] and/or wsum [P] (at least one);
+ * z is dense [P,n], n >= 1.  All three calls: every pointer but w_out / wsum is required (NULL: NERO_ERR_ARG); n == 0 / P == 0: NERO_OK. */
 int nero_section_weights(const float* z, const float* sdf, int lds, int n, const float* variance, int P, float* w_out, float* wsum,
                          void* stream);
 
 /* ---- render preparation (render_core, network/renderer.py:550-565): mid points, section lengths, inner/outer split ---- */
-/* pts4 [R*T,4] = (x,y,z,dist); ray_counts/ray_off int32 [R]; counts int32 [2] = (#inner, #outer) */
+/* pts4 [R*T,4] = (x,y,z,dist); ray_counts/ray_off int32 [R]; counts int32 [2] = (#inner, #outer).  T >= 1 (2 <= T <= 192: one
+ * wavefront per ray, else one thread per ray); z is dense [R,T].  nero_compact: inner_idx [#inner] / outer_idx [#outer] = the flat sample
+ * indices r*T + i in ascending order.  nero_gather_*: rows n .. NERO_ROW_PAD(n)-1 of every output are written as zeros; n == 0: NERO_OK. */
 int nero_render_prep(const float* o, const float* d, const float* z, int R, int T, float* pts4, int* ray_counts, int* ray_off,
                      int* counts, void* stream);
 int nero_compact(const float* pts4, const int* ray_off, int R, int T, int* inner_idx, int* outer_idx, void* stream);

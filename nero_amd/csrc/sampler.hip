@@ -16,7 +16,9 @@ namespace {
 
 constexpr int MAXS = 160;   // max z-values per ray handled by the per-thread buffers
 
-// torch.linspace(start, end, steps)[i] in float32 (ATen: symmetric evaluation around the midpoint)
+// torch.linspace(start, end, steps)[i] in float32, stated element by element (ATen's definition: symmetric evaluation around the midpoint, every
+// operation rounded on its own) = oracle.nero_oracle.linspace_sym bit for bit.  ATen's vectorised CPU kernel itself differs from this in the last
+// bit where the step is inexact (not at the power-of-two sample counts of the YAMLs).
 __device__ __forceinline__ float linspace_f32(float start, float end, int steps, int i) {
     if (steps == 1) return start;
     const float step = (end - start) / (float)(steps - 1);
@@ -602,14 +604,14 @@ __global__ void ray_scan_kernel(const int* __restrict__ ray_counts, int R, int T
 extern "C" {
 
 int nero_coarse_z(const float* near, const float* far, const float* rand1, int R, int n, float* z, int ldz, void* stream) {
-    if (!near || !far || !z || n > MAXS) return nero_fail(NERO_ERR_ARG, "nero_coarse_z: bad argument");
+    if (!near || !far || !z || n < 1 || n > MAXS || ldz < n) return nero_fail(NERO_ERR_ARG, "nero_coarse_z: bad argument");
     if (R == 0) return NERO_OK;
     hipLaunchKernelGGL(coarse_z_kernel, GRID1D(R * n), near, far, rand1, R, n, z, ldz);
     return nero_check_launch("nero_coarse_z");
 }
 
 int nero_background_z(const float* far, const float* rand_bg, int R, int n_bg, float* z, int ldz, int col0, void* stream) {
-    if (!far || !z) return nero_fail(NERO_ERR_ARG, "nero_background_z: bad argument");
+    if (!far || !z || n_bg < 0 || col0 < 0 || ldz < col0 + n_bg) return nero_fail(NERO_ERR_ARG, "nero_background_z: bad argument");
     if (R == 0 || n_bg == 0) return NERO_OK;
     hipLaunchKernelGGL(background_z_kernel, GRID1D(R * n_bg), far, rand_bg, R, n_bg, z, ldz, col0);
     return nero_check_launch("nero_background_z");
@@ -625,9 +627,9 @@ int nero_ray_points_pe(const float* o, const float* d, const float* z, int ldz, 
 
 int nero_upsample(const float* o, const float* d, const float* z, int ldz, const float* sdf, int lds, int n,
                   const float* variance, float inv_s_cap, int m, int R, float* z_new, float* w_out, int* inds_out, void* stream) {
-    if (!o || !d || !z || !sdf || !z_new || n > MAXS || n < 2 || m > 32) return nero_fail(NERO_ERR_ARG, "nero_upsample: bad argument");
+    if (!o || !d || !z || !sdf || !z_new || n > MAXS || n < 2 || m < 0 || m > 32) return nero_fail(NERO_ERR_ARG, "nero_upsample: bad argument");
     if (R == 0) return NERO_OK;
-    if (n <= 128 && m <= 64) {                          // one wave per ray (lane i <-> samples i, i + 64)
+    if (n <= 128) {                                     // one wave per ray (lane i <-> samples i, i + 64; lane j <-> new sample j: m <= 32)
         hipLaunchKernelGGL(upsample_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, o, d, z, ldz, sdf, lds, n, variance, inv_s_cap, m, R, z_new, w_out, inds_out);
         return nero_check_launch("nero_upsample");
     }
@@ -637,9 +639,9 @@ int nero_upsample(const float* o, const float* d, const float* z, int ldz, const
 }
 
 int nero_sample_pdf(const float* bins, int ldb, const float* w, int ldw, int n, int m, int R, float* out, int* inds_out, void* stream) {
-    if (!bins || !w || !out || n > MAXS || n < 2 || m > 32) return nero_fail(NERO_ERR_ARG, "nero_sample_pdf: bad argument");
+    if (!bins || !w || !out || n > MAXS || n < 2 || m < 0 || m > 32) return nero_fail(NERO_ERR_ARG, "nero_sample_pdf: bad argument");
     if (R == 0) return NERO_OK;
-    if (n <= 128 && m <= 64) {
+    if (n <= 128) {
         hipLaunchKernelGGL(sample_pdf_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, bins, ldb, w, ldw, n, m, R, out, inds_out);
         return nero_check_launch("nero_sample_pdf");
     }
@@ -650,7 +652,7 @@ int nero_sample_pdf(const float* bins, int ldb, const float* w, int ldw, int n, 
 
 int nero_merge_sorted(float* z, int ldz, int n, float* sdf, int lds, const float* z_new, int m, const float* sdf_new, int ldsn,
                       int R, int* index_out, void* stream) {
-    if (!z || !z_new || n + m > MAXS) return nero_fail(NERO_ERR_ARG, "nero_merge_sorted: bad argument");
+    if (!z || !z_new || n < 1 || m < 0 || n + m > MAXS) return nero_fail(NERO_ERR_ARG, "nero_merge_sorted: bad argument");
     if (R == 0) return NERO_OK;
     if (n <= 128 && m <= 64) {
         hipLaunchKernelGGL(merge_sorted_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, z, ldz, n, sdf, lds, z_new, m, sdf_new, ldsn, R, index_out);
@@ -670,7 +672,7 @@ int nero_scatter_sdf(const float* src, int ld_src, int R, int n, float* sdf, int
 
 int nero_render_prep(const float* o, const float* d, const float* z, int R, int T, float* pts4, int* ray_counts, int* ray_off,
                      int* counts, void* stream) {
-    if (!o || !d || !z || !pts4 || !ray_counts || !ray_off || !counts) return nero_fail(NERO_ERR_ARG, "nero_render_prep: bad argument");
+    if (!o || !d || !z || !pts4 || !ray_counts || !ray_off || !counts || T < 1) return nero_fail(NERO_ERR_ARG, "nero_render_prep: bad argument");
     if (R == 0) return NERO_OK;
     if (T >= 2 && T <= 192) hipLaunchKernelGGL(render_prep_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, o, d, z, R, T, pts4, ray_counts);
     else hipLaunchKernelGGL(render_prep_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, o, d, z, R, T, pts4, ray_counts);
@@ -679,7 +681,7 @@ int nero_render_prep(const float* o, const float* d, const float* z, int R, int 
 }
 
 int nero_compact(const float* pts4, const int* ray_off, int R, int T, int* inner_idx, int* outer_idx, void* stream) {
-    if (!pts4 || !ray_off || !inner_idx || !outer_idx) return nero_fail(NERO_ERR_ARG, "nero_compact: bad argument");
+    if (!pts4 || !ray_off || !inner_idx || !outer_idx || T < 1) return nero_fail(NERO_ERR_ARG, "nero_compact: bad argument");
     if (R == 0) return NERO_OK;
     hipLaunchKernelGGL(compact_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, pts4, ray_off, R, T, inner_idx, outer_idx);
     return nero_check_launch("nero_compact");
@@ -767,12 +769,14 @@ extern "C" {
 int nero_occ_candidates(const float* x4, const float* sdf4, const float* grad, const int* idx, const float* d, int T, float thresh,
                         int n, unsigned char* flag, void* stream) {
     if (n == 0) return NERO_OK;
+    if (!x4 || !sdf4 || !grad || !idx || !d || !flag || T < 1 || n < 0) return nero_fail(NERO_ERR_ARG, "nero_occ_candidates: bad argument");
     hipLaunchKernelGGL(occ_candidates_kernel, GRID1D(n), x4, sdf4, grad, idx, d, T, thresh, n, flag);
     return nero_check_launch("nero_occ_candidates");
 }
 
 int nero_occ_z(const float* o, const float* d, int P_, int n, float* z, void* stream) {
     if (P_ * n == 0) return NERO_OK;
+    if (!o || !d || !z || P_ < 0 || n < 0) return nero_fail(NERO_ERR_ARG, "nero_occ_z: bad argument");
     hipLaunchKernelGGL(occ_z_kernel, GRID1D(P_ * n), o, d, P_, n, z);
     return nero_check_launch("nero_occ_z");
 }
@@ -780,6 +784,7 @@ int nero_occ_z(const float* o, const float* d, int P_, int n, float* z, void* st
 int nero_section_weights(const float* z, const float* sdf, int lds, int n, const float* variance, int P_, float* w_out, float* wsum,
                          void* stream) {
     if (P_ == 0) return NERO_OK;
+    if (!z || !sdf || !variance || (!w_out && !wsum) || lds < 1 || n < 1 || P_ < 0) return nero_fail(NERO_ERR_ARG, "nero_section_weights: bad argument");
     hipLaunchKernelGGL(section_weights_kernel, dim3((P_ + 63) / 64), dim3(64), 0, (hipStream_t)stream, z, sdf, lds, n, variance, P_, w_out, wsum);
     return nero_check_launch("nero_section_weights");
 }

@@ -16,6 +16,8 @@ Differences from the reference that are deliberate (all documented in DESIGN.md)
     float32 per element (this is what torch-CPU does for float32 tensors), and the pdf normaliser is the last
     element of that cumsum rather than an order-unspecified torch.sum;
   * the concat-sort in cat_z_vals is stable (ties keep the original position);
+  * the sample positions u of the deterministic inverse-CDF sampling are stated element by element (linspace_sym): torch.linspace's
+    last bits depend on the host's vector width where the step is inexact;
   * IDE uses repeated complex multiplication with z**0 == 1, so it has no NaN at the poles (the reference's
     complex pow gives NaN at x=y=0, utils/ref_utils.py:104);
   * the occ-loss subset is "the occ_loss_max_pn smallest keys" of a per-candidate uniform key tensor (the reference
@@ -326,13 +328,30 @@ def transmittance_weights(alpha):
     return alpha * t
 
 
+def linspace_sym(start, end, steps, dtype, device=None):
+    """torch.linspace stated element by element in `dtype`: step = (end - start) / (steps - 1), element i = start + step * i in the first
+    half and end - step * (steps - 1 - i) in the second, every operation rounded on its own (ATen's definition of linspace).  ATen's
+    vectorised CPU kernel chooses the branch once per vector and evaluates base + lane * step, so its last bits depend on the host's vector
+    width wherever the step is not exact (measured: 6 of the 31 elements of linspace(0.5/31, 1 - 0.5/31, 31) differ by one float32 ulp from
+    this statement, none where steps is a power of two) -- and one ulp of u, divided by a cdf step of 1e-5 .. 1e-4, moves a sample by 1e-6."""
+    start, end = torch.as_tensor(start, dtype=dtype, device=device), torch.as_tensor(end, dtype=dtype, device=device)
+    if steps == 1:
+        return start.reshape(1)
+    step = (end - start) / (steps - 1)
+    i = torch.arange(steps, device=device)
+    return torch.where(i < steps // 2, start + step * i.to(dtype), end - step * (steps - 1 - i).to(dtype))
+
+
 def sample_pdf_det(bins, weights, n_samples):
     """Deterministic inverse-CDF sampling (network/field.py:399-429, det=True).  -> samples [R,n], inds int64 [R,n]"""
     w = weights + 1e-5
     c = seq_cumsum(w)
     pdf_norm = c[..., -1:]
     cdf = torch.cat([torch.zeros_like(c[..., :1]), seq_cumsum(w / pdf_norm)], -1)           # [R, nb]
-    u = torch.linspace(0.5 / n_samples, 1.0 - 0.5 / n_samples, n_samples, dtype=bins.dtype, device=bins.device)
+    # u = linspace(0.5/m, 1 - 0.5/m, m) with an explicit evaluation order (every step in bins.dtype): the searchsorted indices below are
+    # part of the bit-exact contract, so u must not depend on the host (for the YAML m = 16 and the golden m = 4 every form gives the same bits)
+    u0 = torch.as_tensor(0.5, dtype=bins.dtype, device=bins.device) / n_samples
+    u = linspace_sym(u0, 1.0 - u0, n_samples, bins.dtype, bins.device)
     u = u.expand(list(cdf.shape[:-1]) + [n_samples]).contiguous()
     inds = torch.searchsorted(cdf, u, right=True)
     below = torch.clamp(inds - 1, min=0)
