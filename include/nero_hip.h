@@ -708,6 +708,40 @@ int nero_mesh_compact_count(const int* tris, int64_t T, int64_t V, const int* co
 int nero_mesh_compact_emit(const float* verts, const int* tris, int64_t T, int64_t V, void* ws, float* verts_out, int64_t v_cap, int* tris_out,
                            int64_t t_cap, int* vmap /*or NULL*/, void* stream);
 
+/* ---- mesh simplification: vertex clustering with quadric-error placement (nero_amd/csrc/mesh_simplify.hip) ------------------------------
+ * The mesh as dense as the extraction grid (a 512^3 grid: one to three million triangles) reduced to one vertex per occupied cell of a
+ * uniform grid, directly behind the clean-up.  The definition is DESIGN.md's ("Mesh simplification"); tests/mesh_simplify_ref.py restates
+ * it in numpy.  Host counterpart: nero_amd/mesh.py.
+ *   verts [V,3] fp32, tris [T,3] int32; 0 <= V < 2^31 and 0 <= 3 T < 2^31 (else NERO_ERR_UNSUPPORTED); V = 0 and T = 0 are valid.
+ *   cell > 0 and finite, origin [3] finite: HOST doubles (else NERO_ERR_ARG; NULL pointers likewise).  Cell of a vertex: i_a = floor((double(x_a)
+ *   - origin_a) / cell) in IEEE float64, a true division; key = i_x << 42 | i_y << 21 | i_z.  A vertex that is non-finite or has an i_a outside
+ *   [0, 2^21), and a triangle with an index outside [0, V), are counted and never followed.  A triangle survives when its three keys are
+ *   pairwise different; the cells that hold a corner of a survivor are the output vertices, in ascending key order.
+ *   No floating-point atomics and no atomics that decide a position: every output is bit-identical run to run.
+ * nero_mesh_simplify_count -- totals [4] (device int32, 16 bytes) = {V', survivors (before de-duplication), refused vertices, refused
+ *   triangles}, also kept in the workspace.  faces_only != 0: only the survivors are counted (no sort; V' = -1), for the search of a cell
+ *   that meets a face budget; the workspace then does not serve nero_mesh_simplify_emit.  Never synchronises.
+ * nero_mesh_simplify_emit -- same mesh, cell, origin and workspace as the complete count before it.  placement: NERO_SIMPLIFY_MEAN (the mean
+ *   of the cell's vertices, referenced or not) or NERO_SIMPLIFY_QUADRIC (mean + (A + 1e-3 tr(A)/3 I)^-1 r over the 3T corner contributions
+ *   with unnormalised normals, pivot-free LDL^T, clamped to the cell's closed box; the mean where tr(A) = 0).  Sums in float64, in a fixed
+ *   order: vertices by ascending id, contributions by ascending 3 t + corner, cut into pieces of 2048 that a wave sums (lane-strided, then a
+ *   butterfly) and adds in ascending order.  -> positions [V',3] float64, verts_out [V',3] = their fp32 rounding, cell_key [V'] int64;
+ *   tris_out [T',3]: the survivors renumbered, winding and relative order kept; dedup != 0: of several survivors with the same unordered
+ *   vertex set only the first stays.  n_tris (device int64, may be NULL) = T' <= survivors.  vmap [V] (may be NULL) = the output vertex of
+ *   each vertex's cell or -1; fmap [T] (may be NULL) = the output index of each triangle or -1.  As nero_mesh_compact_emit it first reads
+ *   the totals back on `stream`, its one synchronisation, and fails with nothing written when V' > v_cap or survivors > t_cap, or when the
+ *   count refused a vertex or a triangle (NERO_ERR_ARG).
+ * ws: nero_mesh_simplify_workspace_bytes(V, T): non-decreasing in V and in T (about 72 V + 136 T bytes + 4 MiB); 0 for sizes the calls
+ *   refuse. */
+enum { NERO_SIMPLIFY_MEAN = 0, NERO_SIMPLIFY_QUADRIC = 1 };
+size_t nero_mesh_simplify_workspace_bytes(int64_t V, int64_t T);
+int nero_mesh_simplify_count(const float* verts, const int* tris, int64_t T, int64_t V, double cell, const double* origin /*host [3]*/,
+                             int faces_only, void* ws, int* totals /*device [4]*/, void* stream);
+int nero_mesh_simplify_emit(const float* verts, const int* tris, int64_t T, int64_t V, double cell, const double* origin /*host [3]*/,
+                            int placement, int dedup, void* ws, double* positions, float* verts_out, int64_t* cell_key, int64_t v_cap,
+                            int* tris_out, int64_t t_cap, int* vmap /*or NULL*/, int* fmap /*or NULL*/, int64_t* n_tris /*device, or NULL*/,
+                            void* stream);
+
 /* ---- geometry evaluation: Chamfer distance of the extracted mesh (nero_amd/csrc/geom_eval.hip) --------------------------------------------
  * The reference's only geometry metric (eval_synthetic_shape.py, eval_real_shape.py, eval.md) without nvdiffrast / open3d / trimesh.  No
  * atomics decide a value or a position: every result is bit-identical run to run.  Host counterpart: nero_amd/eval_shape.py.

@@ -9,6 +9,9 @@ reads it with trimesh (extract_mesh.py:34-37, network/renderer.py:704).  This mo
   * connected_components_device / clean_mesh_device / clean_mesh: the connected components of a mesh, their statistics, and the mesh without
     the unwanted ones (floaters, inner shells, scraps of the support surface), on the device (nero_mesh_*).  The reference has no
     counterpart: its users delete the debris in a mesh editor.
+  * simplify_mesh_device / simplify_mesh / simplify_cells: the mesh reduced to one vertex per occupied cell of a uniform grid, placed by the
+    cell's quadric (nero_mesh_simplify_*), for the ray tracer and the texture atlas of Stage II.  Deterministic and exactly specified
+    (DESIGN.md, "Mesh simplification").
 Conventions (include/nero_hip.h): a corner is inside when u < threshold; vertices are index-space, one per crossing grid edge, ordered by
 (linear grid index, axis x<y<z); triangles are ordered by (cell, table position) and wound so that their normals point into u < threshold --
 inward for an SDF, which NeROMaterialRenderer.trace flips to outward shading normals."""
@@ -37,6 +40,13 @@ L.lib.nero_mesh_compact_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_
                                           C.c_void_p]
 L.lib.nero_mesh_compact_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p]
+L.lib.nero_mesh_simplify_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mesh_simplify_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+L.lib.nero_mesh_simplify_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+L.lib.nero_mesh_simplify_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def workspace_bytes(shape):
@@ -224,6 +234,153 @@ def clean_mesh(v, f, **rules):
     _, f2, info = clean_mesh_device(vd, fd, **rules)
     kept = np.nonzero(info.vmap.cpu().numpy() >= 0)[0]
     return v[kept].astype(np.float64), f2.cpu().numpy().astype(np.int64), info
+
+
+# ---- simplification ---------------------------------------------------------------------------------------------------------------------
+SIMPLIFY_FACTORS = (1.0, 0.8408964152537145, 0.7071067811865476, 0.5946035575013605)      # 2^(-j/4)
+SIMPLIFY_K_MAX = 80
+_PLACEMENTS = {'mean': 0, 'quadric': 1}
+
+
+def simplify_cells(D, k):
+    """the cell sizes the face-budget search of simplify_mesh_device chooses from: D 2^-(k // 4) c[k % 4] in float64, k in [0, 80] (D: the
+    longest side of the bounding box); four steps halve the cell"""
+    k = int(k)
+    if not 0 <= k <= SIMPLIFY_K_MAX:
+        raise ValueError(f'simplify_cells: k must be in [0, {SIMPLIFY_K_MAX}], got {k}')
+    return float(D) * 2.0 ** -(k // 4) * SIMPLIFY_FACTORS[k % 4]
+
+
+class SimplifyInfo:
+    """what simplify_mesh_device did: cell and origin (float, three floats) of the grid, k (the step of simplify_cells a face budget chose,
+    else None), and on the mesh's device cell_key int64 [V'] (i_x << 42 | i_y << 21 | i_z of every output vertex, ascending), positions64
+    float64 [V',3] (the positions as computed; the mesh carries their float32 rounding), vmap int32 [V] (the output vertex of each input
+    vertex's cell, -1 when the cell is unused), fmap int32 [T] (the output index of each triangle that was kept, else -1), n_survivors (the
+    triangles whose corners lie in three different cells), n_duplicates (the survivors the de-duplication removed)"""
+    __slots__ = ('cell', 'origin', 'k', 'cell_key', 'positions64', 'vmap', 'fmap', 'n_survivors', 'n_duplicates')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+class _Simplifier:
+    """one mesh, one workspace: the count calls of the face-budget search and the emit call share them"""
+
+    def __init__(self, verts, tris, origin):
+        self.verts, self.tris = verts, tris
+        self.V, self.T = verts.shape[0], tris.shape[0]
+        self.dev = verts.device
+        self.origin = (C.c_double * 3)(*origin)
+        need = int(L.lib.nero_mesh_simplify_workspace_bytes(self.V, self.T))
+        if need == 0:
+            raise L.NeroHipError(f'simplify_mesh_device: {self.V} vertices / {self.T} triangles: 2^31 or more vertices or corners')
+        L.check_workspace_fits(need, self.dev, what='mesh-simplification workspace')
+        self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self.totals = torch.empty(4, dtype=torch.int32, device=self.dev)
+
+    def count(self, cell, faces_only):
+        """-> (V' or -1, survivors); one readback of 16 bytes.  Refused input raises ValueError"""
+        V, T = self.V, self.T
+        L.check(L.lib.nero_mesh_simplify_count(L.ptr(self.verts) if V else None, L.ptr(self.tris) if T else None, T, V, cell, self.origin,
+                                               int(faces_only), L.ptr(self.ws), L.ptr(self.totals), L.stream_ptr()))
+        v2, n, bad_v, bad_t = (int(x) for x in self.totals.tolist())
+        if bad_v or bad_t:
+            raise ValueError(f'simplify_mesh_device: {bad_v} of {V} vertices are non-finite or lie outside the 2^21 cells of size {cell} an '
+                             f'axis holds from the origin {list(self.origin)}; {bad_t} of {T} triangles hold a vertex index outside [0, {V})')
+        return v2, n
+
+
+def simplify_mesh_device(verts, tris, cell=None, target_faces=None, origin=None, placement='quadric', dedup=True):
+    """verts CUDA float32 [V,3], tris CUDA int32 [T,3] -> (verts', tris', SimplifyInfo): vertex clustering on the uniform grid of cells of
+    size `cell` (in the units of verts; for the marching-cubes output: grid indices) from `origin` (default: the per-axis minimum of verts).
+    A triangle survives when its corners lie in three different cells; the cells that hold a corner of a survivor become the vertices, in
+    ascending cell order; the survivors keep their winding and relative order.  placement: 'quadric' puts a vertex where the planes of the
+    triangles that touch the cell meet best (regularised towards the mean of the cell's vertices, clamped to the cell), 'mean' at that
+    mean.  dedup: of several survivors with the same three vertices, in either winding, only the first stays.  target_faces=N instead of
+    cell: the smallest cell of simplify_cells(D, k) that leaves at most N survivors, found by bisection over k with at most 8 counting
+    passes (the survivor count is taken as non-decreasing in k); N below the count of k = 0 raises ValueError.
+    Non-finite vertices, vertices more than 2^21 cells from the origin and triangle indices outside [0, V) raise ValueError naming their
+    number (the kernels count them and never follow them).  Everything is bit-identical run to run."""
+    verts, tris = _check_mesh('simplify_mesh_device', verts, tris)
+    if (cell is None) == (target_faces is None):
+        raise ValueError('simplify_mesh_device: give exactly one of cell and target_faces')
+    if placement not in _PLACEMENTS:
+        raise ValueError(f"simplify_mesh_device: placement must be 'quadric' or 'mean', got {placement!r}")
+    if cell is not None and not (np.isfinite(float(cell)) and float(cell) > 0):
+        raise ValueError(f'simplify_mesh_device: cell must be positive and finite, got {cell}')
+    if target_faces is not None and (isinstance(target_faces, bool) or int(target_faces) != target_faces or target_faces < 0):
+        raise ValueError(f'simplify_mesh_device: target_faces must be a non-negative integer, got {target_faces!r}')
+    V, T = verts.shape[0], tris.shape[0]
+    dev = verts.device
+    with torch.cuda.device(dev):
+        empty = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        if V == 0 or T == 0:
+            o = [0.0] * 3 if origin is None else [float(x) for x in origin]
+            info = SimplifyInfo(cell=None if cell is None else float(cell), origin=o, k=None, cell_key=empty(0, dtype=torch.int64),
+                                positions64=empty(0, 3, dtype=torch.float64), vmap=torch.full((V,), -1, dtype=torch.int32, device=dev),
+                                fmap=torch.full((T,), -1, dtype=torch.int32, device=dev), n_survivors=0, n_duplicates=0)
+            return empty(0, 3, dtype=torch.float32), empty(0, 3, dtype=torch.int32), info
+        box = torch.stack([verts.amin(dim=0), verts.amax(dim=0)]).double().cpu()              # (float32 extrema are exact)
+        finite = bool(torch.isfinite(box).all())
+        if origin is None:
+            origin = box[0].tolist() if finite else [0.0] * 3                                 # (the count below names the bad vertices)
+        origin = [float(x) for x in origin]
+        if len(origin) != 3 or not all(np.isfinite(origin)):
+            raise ValueError(f'simplify_mesh_device: origin must be three finite numbers, got {origin}')
+        job = _Simplifier(verts, tris, origin)
+        k = None
+        if target_faces is not None:
+            if not finite:
+                job.count(1.0, True)                                                          # raises, naming the count
+            D = float((box[1] - box[0]).max())
+            if not D > 0:
+                raise ValueError('simplify_mesh_device: target_faces needs a mesh with a bounding box of positive size')
+            n_of = lambda q: job.count(simplify_cells(D, q), True)[1]
+            n0 = n_of(0)
+            if n0 > target_faces:
+                raise ValueError(f'simplify_mesh_device: target_faces = {target_faces} is below the {n0} faces the coarsest cell '
+                                 f'({simplify_cells(D, 0)}) leaves')
+            lo, hi = 0, SIMPLIFY_K_MAX + 1
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                if n_of(mid) <= target_faces:
+                    lo = mid
+                else:
+                    hi = mid
+            k = lo
+            cell = simplify_cells(D, k)
+        cell = float(cell)
+        V2, S = job.count(cell, False)
+        L.check_workspace_fits(44 * V2 + 12 * S + 4 * (V + T), dev, what='simplified mesh')
+        pos = empty(V2, 3, dtype=torch.float64)
+        v2 = empty(V2, 3, dtype=torch.float32)
+        key = empty(V2, dtype=torch.int64)
+        f2 = empty(S, 3, dtype=torch.int32)
+        vmap = empty(V, dtype=torch.int32)
+        fmap = empty(T, dtype=torch.int32)
+        n_out = empty(1, dtype=torch.int64)
+        L.check(L.lib.nero_mesh_simplify_emit(L.ptr(verts), L.ptr(tris), T, V, cell, job.origin, _PLACEMENTS[placement], int(bool(dedup)),
+                                              L.ptr(job.ws), L.ptr(pos) if V2 else None, L.ptr(v2) if V2 else None, L.ptr(key) if V2 else None,
+                                              V2, L.ptr(f2) if S else None, S, L.ptr(vmap), L.ptr(fmap), L.ptr(n_out), L.stream_ptr()))
+        T2 = int(n_out.item())
+        if T2 < S:
+            f2 = f2[:T2].clone()                                                              # (releases the survivors' capacity)
+    return v2, f2, SimplifyInfo(cell=cell, origin=origin, k=k, cell_key=key, positions64=pos, vmap=vmap, fmap=fmap, n_survivors=S,
+                                n_duplicates=S - T2)
+
+
+def simplify_mesh(v, f, **kw):
+    """simplify_mesh_device on numpy arrays (e.g. what read_ply returns), computed on the current CUDA device on a float32 copy of the
+    vertices: -> (vertices float64 [V',3]: the float64 positions as computed, triangles int64 [T',3], SimplifyInfo)"""
+    v = np.asarray(v).reshape(-1, 3)
+    f = np.asarray(f).reshape(-1, 3)
+    if f.size and (f.min() < -_INT31 or f.max() >= _INT31):
+        raise ValueError('simplify_mesh: a face index does not fit int32')
+    vd = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
+    fd = torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32)).cuda()
+    _, f2, info = simplify_mesh_device(vd, fd, **kw)
+    return info.positions64.cpu().numpy(), f2.cpu().numpy().astype(np.int64), info
 
 
 # ---- PLY --------------------------------------------------------------------------------------------------------------------------------

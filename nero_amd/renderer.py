@@ -223,19 +223,23 @@ class NeROShapeRenderer(nn.Module):
         return self._sdf_grid(bound_min, bound_max, resolution, chunk, outside_val).cpu().numpy()
 
     def extract_geometry(self, bound_min=(-1., -1., -1.), bound_max=(1., 1., 1.), resolution=512, threshold=0.0, outside_val=1.0,
-                         clean=None):
+                         clean=None, simplify=None):
         """the Stage-I mesh (extract_geometry, network/field.py:1110-1117; extract_mesh.py:24-31): the extract_fields grid, kept on the
         device, through the HIP marching cubes (nero_amd.mesh), mapped to the box in float64 as the reference does.  Only the mesh is copied
         to the host.  -> (vertices float64 [V,3], triangles int64 [T,3]), wound inward (normals towards sdf < threshold), the winding
         NeROMaterialRenderer(cfg, mesh=...) expects.  clean: None (the reference's mesh, debris included) or a dict of the rules of
         nero_amd.mesh.clean_mesh_device (keep, min_faces, min_face_ratio; {} drops only unreferenced vertices): the connected-component
-        clean-up runs on the device mesh, and only the cleaned mesh is copied"""
+        clean-up runs on the device mesh, and only the cleaned mesh is copied.  simplify: None or a dict of the arguments of
+        nero_amd.mesh.simplify_mesh_device (cell in grid-index units, or target_faces; origin, placement, dedup): vertex clustering on the
+        device mesh, after the clean-up and before the copy"""
         from . import mesh as M
         u = self._sdf_grid(bound_min, bound_max, resolution, 2 ** 21, outside_val)
         v, f = M.marching_cubes_device(u, threshold)
         del u
         if clean is not None:
             v, f, _ = M.clean_mesh_device(v, f, **clean)
+        if simplify is not None:
+            v, f, _ = M.simplify_mesh_device(v, f, **simplify)
         return M.index_to_world(v.cpu().numpy(), resolution, bound_min, bound_max), f.cpu().numpy().astype(np.int64)
 
     def _sdf_grid(self, bound_min, bound_max, resolution, chunk, outside_val):

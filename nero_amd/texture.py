@@ -171,7 +171,7 @@ def simple_atlas(verts, tris, size):
 
     A FALLBACK, not xatlas: every triangle becomes a right-angled chart of its own, so texture space is used poorly, texel density follows
     nothing, and every edge is a seam.  A full-resolution marching-cubes mesh needs decimation first or a real unwrapper (pass its vt / ft to
-    bake_materials).  Layout: G = ceil(sqrt(ceil(T / 2))) cells per side, each s = size // G texels wide, origins on texel corners; triangles 2k
+    bake_materials): nero_amd.mesh.simplify_mesh_device(target_faces=N) is that decimation (N = 2 (size // 4)^2 triangles fit at `size`).  Layout: G = ceil(sqrt(ceil(T / 2))) cells per side, each s = size // G texels wide, origins on texel corners; triangles 2k
     and 2k + 1 share cell k (row-major), one in the low corner, one in the high corner.  With n = s - 1 the first chart covers the texels
     i + j <= p of the cell and the second those with i + j >= p + 3, i, j <= n - 1 (p = (2n - 5) // 2); the last row and column of a cell stay
     empty.  So at `size` every chart covers at least one texel centre, and texels of two different charts are never 8-neighbours: at least

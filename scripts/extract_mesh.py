@@ -1,10 +1,12 @@
 #!/usr/bin/env python
 """Extract the Stage-I mesh of a checkpoint as a PLY (the reference's extract_mesh.py), optionally without its debris, or clean an existing PLY:
-the connected components of the marching-cubes surface, selected by face count, on the device (nero_amd.mesh, nero_amd/csrc/mesh_clean.hip).
+the connected components of the marching-cubes surface, selected by face count, on the device (nero_amd.mesh, nero_amd/csrc/mesh_clean.hip);
+and optionally simplified by vertex clustering (nero_amd/csrc/mesh_simplify.hip), in both modes, after the clean-up.
 
     python scripts/extract_mesh.py --cfg configs/shape/syn/bell.yaml --model data/model/bell_shape/model.pth --resolution 512 \\
         --keep-largest --out data/meshes/bell.ply
     python scripts/extract_mesh.py --in data/meshes/bell.ply --min-face-ratio 0.01 --out data/meshes/bell_clean.ply
+    python scripts/extract_mesh.py --in data/meshes/bell_clean.ply --target-faces 100000 --out data/meshes/bell_100k.ply
 
 Extract mode (--cfg, --model): the steps of NeROShapeRenderer.extract_geometry on the box [-1, 1]^3 (SDF grid, marching cubes, the clean-up
 when a rule is given), all on the device; only the final mesh is copied to the host.  Without --model the mesh is that of the freshly
@@ -14,6 +16,10 @@ Rules (they intersect; with none of them extract mode writes the mesh as marchin
 vertices only): --keep-largest [K] keeps the K (default 1) components with the most faces, ties towards the component that holds the smaller
 vertex index; --min-faces N drops components with fewer faces; --min-face-ratio R drops those below that fraction of the largest component's
 face count.
+Simplification: --simplify-cell C clusters the vertices on a grid of cells of size C, in the units of the mesh the device holds (grid
+indices in extract mode, the PLY's units in clean-only mode); --target-faces N chooses the smallest cell of the ladder
+nero_amd.mesh.simplify_cells that leaves at most N faces.  One or the other.  The JSON line then holds `simplify`: the vertex and face
+counts before and after, the chosen cell, its step k, and the number of duplicate faces removed.
 Prints one JSON line: the per-component table (vertices, faces, area, bounding box) before and after; --table-limit caps the rows listed
 per table (largest first), the counts are always complete."""
 import argparse
@@ -43,13 +49,26 @@ def parse_args(argv=None):
     ap.add_argument('--keep-largest', type=int, nargs='?', const=1, default=None, metavar='K')
     ap.add_argument('--min-faces', type=int, default=0, metavar='N')
     ap.add_argument('--min-face-ratio', type=float, default=0.0, metavar='R')
+    ap.add_argument('--simplify-cell', type=float, default=None, metavar='C')
+    ap.add_argument('--target-faces', type=int, default=None, metavar='N')
     ap.add_argument('--table-limit', type=int, default=32)
     args = ap.parse_args(argv)
     if args.inp and (args.cfg or args.model):
         ap.error('--in cleans an existing PLY; --cfg / --model extract one: give one or the other')
     if not args.inp and not args.cfg:
         ap.error('give --cfg (and --model) to extract a mesh, or --in to clean an existing PLY')
+    if args.simplify_cell is not None and args.target_faces is not None:
+        ap.error('--simplify-cell and --target-faces both choose the cell: give one or the other')
     return args
+
+
+def simplify_of(args):
+    """the simplify_mesh_device arguments the command line asks for, None when it asks for none"""
+    if args.simplify_cell is not None:
+        return {'cell': args.simplify_cell}
+    if args.target_faces is not None:
+        return {'target_faces': args.target_faces}
+    return None
 
 
 def rules_of(args):
@@ -103,6 +122,12 @@ def main(argv=None):
         out['before'] = report(info.components, args.table_limit)
         out['kept_components'] = [int(c) for c in torch.nonzero(info.keep)[:, 0].tolist()][:args.table_limit]
         out['after'] = report(M.connected_components_device(v2, f2), args.table_limit)
+    simplify = simplify_of(args)
+    if simplify is not None:
+        n_before = {'n_verts': int(v2.shape[0]), 'n_faces': int(f2.shape[0])}
+        v2, f2, sinfo = M.simplify_mesh_device(v2, f2, **simplify)
+        out['simplify'] = {**simplify, 'before': n_before, 'after': {'n_verts': int(v2.shape[0]), 'n_faces': int(f2.shape[0])},
+                           'cell': sinfo.cell, 'k': sinfo.k, 'n_survivors': sinfo.n_survivors, 'n_duplicates': sinfo.n_duplicates}
     if not args.inp:
         out['resolution'] = args.resolution
         out['table_space'] = 'grid index'
