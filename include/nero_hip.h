@@ -742,6 +742,58 @@ int nero_mesh_simplify_emit(const float* verts, const int* tris, int64_t T, int6
                             int* tris_out, int64_t t_cap, int* vmap /*or NULL*/, int* fmap /*or NULL*/, int64_t* n_tris /*device, or NULL*/,
                             void* stream);
 
+/* ---- chart atlas: the UV unwrap of the Stage-II asset export (nero_amd/csrc/mesh_atlas.hip) ------------------------------------------------
+ * The reference unwraps with xatlas (extract_materials_texture_map.py:83-85).  This is a PROJECTION atlas: charts are edge-connected sets of
+ * faces whose normals share a dominant signed axis, each projected along that axis at one common world-to-texel scale, the chart rectangles
+ * shelf-packed into the square map on the host.  The definition is DESIGN.md 9.7.1; tests/mesh_atlas_ref.py restates it in numpy.  Host
+ * counterparts: nero_amd/mesh.py (face_adjacency_device, face_charts_device), nero_amd/texture.py (chart_atlas).
+ *   verts [V,3] fp32, tris [T,3] int32; 0 <= V < 2^31 and 0 <= 3 T < 2^31 (else NERO_ERR_UNSUPPORTED); T = 0 and V = 0 are valid and launch
+ *   nothing.  NULL pointers are NERO_ERR_ARG.  A face is VALID when its three indices lie in [0, V) and are pairwise different; any other
+ *   face is chartless: counted, never dereferenced.  No floating-point atomics and no atomic that decides a position or a label: every
+ *   output is bit-identical run to run.
+ * nero_mesh_face_adjacency -- every valid face contributes the edges e = (v_e, v_(e+1)%3) with the key min << 32 | max; a stable radix sort of
+ *   the (key, 3 t + e) pairs groups them.  A key held by exactly two entries, of two different faces, makes the two faces neighbours across
+ *   that edge; a key held once is a boundary edge, three times or more a non-manifold edge: no neighbour.  -> nbr [T,3] int32 (-1 = none),
+ *   counts [2] (device int64) = {boundary edges, non-manifold edges}.  Never synchronises.  ws: nero_mesh_face_adjacency_workspace_bytes(T)
+ *   (72 T bytes + the sort's scratch).
+ * nero_mesh_chart_label -- face_class [T] int32: n = (b - a) x (c - a) in float64 from the fp32 vertices (every product and difference rounded
+ *   on its own), k = argmax |n_k| with ties to the lowest axis, class 2 k + (n_k < 0); 6 = chartless: a face that is not valid, or whose n
+ *   is not finite or is zero.  Two faces belong to one chart when they are neighbours in nbr and have the same class below 6.  A concurrent
+ *   union-find over the faces (chart doubles as the parent array; every change of it is an agent-scope compare-and-swap or minimum, the
+ *   larger root goes under the smaller, a launch of its own flattens it).  -> chart [T] int32: charts numbered 0..K-1 in ascending order of
+ *   their smallest face, -1 for a chartless face; info [2] (device int64) = {K, chartless faces}.  Never synchronises: the caller reads info.
+ *   ws: nero_mesh_chart_label_workspace_bytes(T) (8 T bytes + the scan's scratch).
+ * nero_mesh_chart_stats -- chart, face_class and K as nero_mesh_chart_label gave them -> per chart chart_class [K], n_faces [K] and box [K,4]
+ *   fp32 = {min_p, min_q, max_p, max_q} of the projected coordinates of the chart's vertices, where class 2 k + s projects onto the axes
+ *   p = (k + 1) % 3, q = (k + 2) % 3.  Exact: integer atomics on order-preserving bit images (-0 orders below +0).  Never synchronises.
+ * nero_mesh_chart_corners_count / _emit -- the UV vertices: one per distinct (chart, mesh vertex) pair among the corners of charted faces, in
+ *   ascending (chart, vertex) order (a stable sort of the 3T corner keys chart << 32 | vertex, head flags, a scan).  When a face is chartless
+ *   one more UV vertex comes last and all three corners of every chartless face point at it.  count: totals [2] (device int64) = {n_vt,
+ *   corners of chartless faces}, also kept in the workspace; never synchronises.  emit: same T and workspace as the count before it -> ft
+ *   [T,3] int32, vt_vertex [n_vt] (the mesh vertex, -1 for the last one of a mesh with chartless faces: xatlas's vmapping), vt_chart [n_vt]
+ *   (-1 likewise).  As nero_mesh_compact_emit it first reads the totals back on `stream`, its one synchronisation, and fails with nothing
+ *   written when n_vt > vt_cap (NERO_ERR_ARG).  ws of both: nero_mesh_chart_corners_workspace_bytes(T) (96 T bytes + scratch).
+ * nero_mesh_chart_uv -- origin [K,2] int32: the texel (ox, oy) of each chart's rectangle; scale: texels per world unit, a HOST double, finite
+ *   and >= 0; size in [1, 16384] (else NERO_ERR_ARG).  For a UV vertex of chart c (class 2 k + s) at mesh vertex x:
+ *   U = ox + 0.5 + (s ? max_p - x_p : x_p - min_p) * scale, V = oy + 0.5 + (x_q - min_q) * scale, vt = (U / size, V / size): float64, the
+ *   difference, one product, the two sums left to right, one true division, each rounded on its own (no fused multiply-add), the result
+ *   rounded once to fp32.  The mirror of the odd classes gives every UV triangle a positive area.  The vertex without a chart is (0, 0).  A
+ *   call of its own, so that a search of the scale repeats no sort.  Never synchronises. */
+size_t nero_mesh_face_adjacency_workspace_bytes(int64_t T);
+int nero_mesh_face_adjacency(const int* tris, int64_t T, int64_t V, void* ws, int* nbr, int64_t* counts /*device, {boundary, non-manifold}*/,
+                             void* stream);
+size_t nero_mesh_chart_label_workspace_bytes(int64_t T);
+int nero_mesh_chart_label(const float* verts, const int* tris, int64_t T, int64_t V, const int* nbr, void* ws, int* face_class, int* chart,
+                          int64_t* info /*device, {K, chartless}*/, void* stream);
+int nero_mesh_chart_stats(const float* verts, const int* tris, int64_t T, int64_t V, const int* chart, const int* face_class, int64_t K,
+                          int* chart_class, int* n_faces, float* box, void* stream);
+size_t nero_mesh_chart_corners_workspace_bytes(int64_t T);
+int nero_mesh_chart_corners_count(const int* tris, int64_t T, int64_t V, const int* chart, int64_t K, void* ws,
+                                  int64_t* totals /*device, {n_vt, chartless corners}*/, void* stream);
+int nero_mesh_chart_corners_emit(int64_t T, void* ws, int* ft, int* vt_vertex, int* vt_chart, int64_t vt_cap, void* stream);
+int nero_mesh_chart_uv(const float* verts, int64_t V, const int* vt_vertex, const int* vt_chart, int64_t n_vt, const int* chart_class,
+                       const float* box, const int* origin, int64_t K, double scale /*host*/, int size, float* vt, void* stream);
+
 /* ---- geometry evaluation: Chamfer distance of the extracted mesh (nero_amd/csrc/geom_eval.hip) --------------------------------------------
  * The reference's only geometry metric (eval_synthetic_shape.py, eval_real_shape.py, eval.md) without nvdiffrast / open3d / trimesh.  No
  * atomics decide a value or a position: every result is bit-identical run to run.  Host counterpart: nero_amd/eval_shape.py.
@@ -789,8 +841,8 @@ int nero_depth_points(const float* depth, const unsigned char* mask, const doubl
                       float unproject_offset, void* ws, float* pts, int64_t pts_cap, int64_t* n_pts /*device*/, void* stream);
 
 /* ---- texture baking: the Stage-II materials as UV maps (nero_amd/csrc/texture.hip) --------------------------------------------------------
- * The device steps of extract_materials_texture_map.py without nvdiffrast / scipy / sklearn / cv2 (the unwrapping itself, xatlas, stays with
- * the caller: any vt / ft will do).  Maps are row-major [h][w], texel (row y, column x) has index y w + x and its centre at u = (x + 0.5) / w,
+ * The device steps of extract_materials_texture_map.py without nvdiffrast / scipy / sklearn / cv2 (the unwrapping: the chart atlas above, or any vt / ft of
+ * the caller's, xatlas's for one).  Maps are row-major [h][w], texel (row y, column x) has index y w + x and its centre at u = (x + 0.5) / w,
  * v = (y + 0.5) / h; h and w in [1, 16384], anything else is NERO_ERR_ARG.  Host counterpart: nero_amd/texture.py.  No floating-point
  * atomics, no atomics that decide a position: every result is bit-identical run to run.
  *
@@ -806,6 +858,10 @@ int nero_depth_points(const float* depth, const unsigned char* mask, const doubl
  *   Work is binned by bounding-box size: boxes of at most 16 texel centres are finished by the lane that set the triangle up, the others are
  *   cut into blocks of 8 x 8 texels that a fixed grid of waves shares.  ws: nero_uv_raster_workspace_bytes(nt) (16 bytes per triangle + the
  *   scan's scratch; 0 = a refused count).
+ * nero_uv_overlap_count -- count (device int64) = the texel centres that more than one triangle covers, by the same rule and the same walk as
+ *   nero_uv_raster (an integer count per texel instead of the minimum), so an edge two triangles share never counts twice.  For any vt / ft,
+ *   an external unwrapper's too; a triangle with an index outside [0, nvt) covers nothing.  Never synchronises.
+ *   ws: nero_uv_overlap_count_workspace_bytes(nt, h, w) (the raster's workspace + 4 bytes per texel).
  * nero_uv_interp -- `dr.interpolate(v, rast, f)`, the mask and `xyzs[mask]` (:100-113).  attr [nv,C] fp32 with its own face array fa [nt,3]
  *   (the reference rasterises with the UV faces and interpolates with the position faces) -> the covered texels compacted in ascending
  *   row-major order: texel [n] int32, out [n,C] = (e0 a0 + e1 a1 + e2 a2) / A with e_k the edge function opposite vertex k at the centre,
@@ -832,6 +888,8 @@ int nero_depth_points(const float* depth, const unsigned char* mask, const doubl
  *   2 x 2 block (cv2's rounding of ties is not verified: cv2 is not available to this project).  2h, 2w <= 16384. */
 size_t nero_uv_raster_workspace_bytes(int64_t nt);
 int nero_uv_raster(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int* tri_id, void* stream);
+size_t nero_uv_overlap_count_workspace_bytes(int64_t nt, int h, int w);
+int nero_uv_overlap_count(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int64_t* count /*device*/, void* stream);
 size_t nero_uv_interp_workspace_bytes(int h, int w);
 int nero_uv_interp(const int* tri_id, const float* vt, int64_t nvt, const int* ft, int64_t nt, const float* attr, int64_t nv, int C, const int* fa,
                    int h, int w, void* ws, int* texel, float* out, int64_t cap, unsigned char* mask /*or NULL*/, int64_t* n_out /*device, or NULL*/,

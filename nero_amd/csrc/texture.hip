@@ -102,6 +102,14 @@ __global__ __launch_bounds__(256) void tx_index_check_kernel(const int* __restri
 }
 
 // one lane per triangle: small boxes are rasterised here, the others counted in blocks of UV_BLOCK^2 texels (cnt[nt] = 0 for the scan)
+// COUNT: the same walk adds one to the texel's cover count instead (nero_uv_overlap_count; sums of integers do not depend on arrival order)
+template <bool COUNT>
+__device__ __forceinline__ void uv_cover(unsigned* __restrict__ map, int64_t texel, int64_t t) {
+    if (COUNT) atomicAdd(map + texel, 1u);
+    else atomicMin(map + texel, (unsigned)t);
+}
+
+template <bool COUNT>
 __global__ __launch_bounds__(256) void uv_small_kernel(const float* __restrict__ vt, int64_t nvt, const int* __restrict__ ft, int64_t nt, int h,
                                                        int w, unsigned* __restrict__ tri_id, int64_t* __restrict__ cnt) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -114,7 +122,7 @@ __global__ __launch_bounds__(256) void uv_small_kernel(const float* __restrict__
             for (int y = s.y_lo; y <= s.y_hi; ++y)
                 for (int x = s.x_lo; x <= s.x_hi; ++x) {
                     int64_t e[3];
-                    if (uv_inside(s, x, y, e)) atomicMin(tri_id + (int64_t)y * w + x, (unsigned)t);
+                    if (uv_inside(s, x, y, e)) uv_cover<COUNT>(tri_id, (int64_t)y * w + x, t);
                 }
         } else {
             blocks = (int64_t)((bw + UV_BLOCK - 1) / UV_BLOCK) * ((bh + UV_BLOCK - 1) / UV_BLOCK);
@@ -125,6 +133,7 @@ __global__ __launch_bounds__(256) void uv_small_kernel(const float* __restrict__
 
 // base: exclusive scan of cnt over nt + 1 entries.  Wave g takes the blocks g, g + waves, ...; block b belongs to the last triangle whose
 // base is <= b (an upper bound search: the triangles without blocks in between share the base of the next one and are skipped by it).
+template <bool COUNT>
 __global__ __launch_bounds__(256) void uv_walk_kernel(const float* __restrict__ vt, int64_t nvt, const int* __restrict__ ft, int64_t nt, int h,
                                                       int w, const int64_t* __restrict__ base, unsigned* __restrict__ tri_id) {
     const int lane = threadIdx.x & 63;
@@ -144,7 +153,22 @@ __global__ __launch_bounds__(256) void uv_walk_kernel(const float* __restrict__ 
         const int x = s.x_lo + (int)(k % nbx) * UV_BLOCK + (lane & (UV_BLOCK - 1));
         const int y = s.y_lo + (int)(k / nbx) * UV_BLOCK + (lane >> 3);
         int64_t e[3];
-        if (x <= s.x_hi && y <= s.y_hi && uv_inside(s, x, y, e)) atomicMin(tri_id + (int64_t)y * w + x, (unsigned)t);
+        if (x <= s.x_hi && y <= s.y_hi && uv_inside(s, x, y, e)) uv_cover<COUNT>(tri_id, (int64_t)y * w + x, t);
+    }
+}
+
+// texels whose cover count exceeds one: a sum per workgroup, then one integer atomic
+__global__ __launch_bounds__(256) void uv_overlap_sum_kernel(const unsigned* __restrict__ cover, int64_t n, unsigned long long* count) {
+    __shared__ int part[4];
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int v = p < n && cover[p] > 1u ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int tot = part[0] + part[1] + part[2] + part[3];
+        if (tot) atomicAdd(count, (unsigned long long)tot);
     }
 }
 
@@ -445,13 +469,44 @@ int nero_uv_raster(const float* vt, int64_t nvt, const int* ft, int64_t nt, int 
     const RasterLayout L = raster_layout(nt);
     int64_t* cnt = (int64_t*)(b + L.cnt);
     int64_t* base = (int64_t*)(b + L.base);
-    hipLaunchKernelGGL(uv_small_kernel, dim3(blocks_of(nt + 1)), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (unsigned*)tri_id, cnt);
+    hipLaunchKernelGGL(uv_small_kernel<false>, dim3(blocks_of(nt + 1)), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (unsigned*)tri_id, cnt);
     if (int rc = nero_check_launch("nero_uv_raster: small-triangle pass")) return rc;
     size_t tb = L.temp_bytes;
     if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int64_t*)cnt, base, (int)(nt + 1), s) != hipSuccess)
         return nero_fail(NERO_ERR_LAUNCH, "nero_uv_raster: block scan failed");
-    hipLaunchKernelGGL(uv_walk_kernel, dim3(UV_WALK_BLOCKS), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (const int64_t*)base, (unsigned*)tri_id);
+    hipLaunchKernelGGL(uv_walk_kernel<false>, dim3(UV_WALK_BLOCKS), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (const int64_t*)base, (unsigned*)tri_id);
     return nero_check_launch("nero_uv_raster: block walk");
+}
+
+size_t nero_uv_overlap_count_workspace_bytes(int64_t nt, int h, int w) {
+    if (!count_ok(nt) || !size_ok(h, w)) return 0;
+    return raster_layout(nt).total + align256((size_t)h * w * sizeof(unsigned));
+}
+
+int nero_uv_overlap_count(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int64_t* count, void* stream) {
+    if (int rc = check_size("nero_uv_overlap_count", h, w)) return rc;
+    if (!count_ok(nt) || !count_ok(nvt)) return nero_fail(NERO_ERR_ARG, "nero_uv_overlap_count: a count is negative or 2^31 - 1 or more");
+    if (!count || !ws || (nt > 0 && (!ft || (nvt > 0 && !vt)))) return nero_fail(NERO_ERR_ARG, "nero_uv_overlap_count: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(count, 0, sizeof(int64_t), s) != hipSuccess) return nero_fail(NERO_ERR_LAUNCH, "nero_uv_overlap_count: hipMemsetAsync failed");
+    if (nt == 0) return NERO_OK;
+    uint8_t* b = (uint8_t*)ws;
+    const int64_t n = (int64_t)h * w;
+    const RasterLayout L = raster_layout(nt);
+    int64_t* cnt = (int64_t*)(b + L.cnt);
+    int64_t* base = (int64_t*)(b + L.base);
+    unsigned* cover = (unsigned*)(b + L.total);
+    if (hipMemsetAsync(cover, 0, (size_t)n * sizeof(unsigned), s) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_overlap_count: hipMemsetAsync failed");
+    hipLaunchKernelGGL(uv_small_kernel<true>, dim3(blocks_of(nt + 1)), dim3(256), 0, s, vt, nvt, ft, nt, h, w, cover, cnt);
+    if (int rc = nero_check_launch("nero_uv_overlap_count: small-triangle pass")) return rc;
+    size_t tb = L.temp_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int64_t*)cnt, base, (int)(nt + 1), s) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_overlap_count: block scan failed");
+    hipLaunchKernelGGL(uv_walk_kernel<true>, dim3(UV_WALK_BLOCKS), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (const int64_t*)base, cover);
+    if (int rc = nero_check_launch("nero_uv_overlap_count: block walk")) return rc;
+    hipLaunchKernelGGL(uv_overlap_sum_kernel, dim3(blocks_of(n)), dim3(256), 0, s, (const unsigned*)cover, n, (unsigned long long*)count);
+    return nero_check_launch("nero_uv_overlap_count: sum");
 }
 
 size_t nero_uv_interp_workspace_bytes(int h, int w) { return size_ok(h, w) ? interp_layout((int64_t)h * w).total : 0; }

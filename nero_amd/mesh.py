@@ -12,6 +12,8 @@ reads it with trimesh (extract_mesh.py:34-37, network/renderer.py:704).  This mo
   * simplify_mesh_device / simplify_mesh / simplify_cells: the mesh reduced to one vertex per occupied cell of a uniform grid, placed by the
     cell's quadric (nero_mesh_simplify_*), for the ray tracer and the texture atlas of Stage II.  Deterministic and exactly specified
     (DESIGN.md, "Mesh simplification").
+  * face_adjacency_device / face_charts_device: the neighbours of every face across its edges and the charts of the projection atlas
+    (nero_mesh_face_adjacency / nero_mesh_chart_*), which nero_amd.texture.chart_atlas turns into UV coordinates.
 Conventions (include/nero_hip.h): a corner is inside when u < threshold; vertices are index-space, one per crossing grid edge, ordered by
 (linear grid index, axis x<y<z); triangles are ordered by (cell, table position) and wound so that their normals point into u < threshold --
 inward for an SDF, which NeROMaterialRenderer.trace flips to outward shading normals."""
@@ -47,6 +49,13 @@ L.lib.nero_mesh_simplify_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.
 L.lib.nero_mesh_simplify_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+L.lib.nero_mesh_face_adjacency_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mesh_face_adjacency_workspace_bytes.argtypes = [C.c_int64]
+L.lib.nero_mesh_face_adjacency.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+L.lib.nero_mesh_chart_label_workspace_bytes.restype = C.c_size_t
+L.lib.nero_mesh_chart_label_workspace_bytes.argtypes = [C.c_int64]
+L.lib.nero_mesh_chart_label.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6
+L.lib.nero_mesh_chart_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
 
 
 def workspace_bytes(shape):
@@ -234,6 +243,76 @@ def clean_mesh(v, f, **rules):
     _, f2, info = clean_mesh_device(vd, fd, **rules)
     kept = np.nonzero(info.vmap.cpu().numpy() >= 0)[0]
     return v[kept].astype(np.float64), f2.cpu().numpy().astype(np.int64), info
+
+
+# ---- adjacency and charts ---------------------------------------------------------------------------------------------------------------
+class ChartInfo:
+    """the charts of a mesh (face_charts_device): K, and on the mesh's device chart_class int32 [K] (2 k + s: projected along axis k, onto the
+    axes (k + 1) % 3 and (k + 2) % 3, mirrored when s = 1), n_faces int32 [K], box float32 [K,4] (min_p, min_q, max_p, max_q of the projected
+    coordinates); n_boundary / n_nonmanifold (edges held by one face / by three or more), n_chartless (faces without a chart)"""
+    __slots__ = ('K', 'chart_class', 'n_faces', 'box', 'n_boundary', 'n_nonmanifold', 'n_chartless')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _face_adjacency(tris, V):
+    T = tris.shape[0]
+    dev = tris.device
+    need = int(L.lib.nero_mesh_face_adjacency_workspace_bytes(T))
+    if T and need == 0:
+        raise L.NeroHipError(f'face_adjacency_device: {T} triangles: 2^31 or more corners')
+    L.check_workspace_fits(need + 12 * T, dev, what='face-adjacency workspace')
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        nbr = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(L.lib.nero_mesh_face_adjacency(L.ptr(tris) if T else None, T, int(V), L.ptr(ws), L.ptr(nbr) if T else None, L.ptr(counts),
+                                               L.stream_ptr()))
+    return nbr, counts
+
+
+def face_adjacency_device(tris, n_verts):
+    """tris CUDA int32 [T,3] over n_verts vertices -> (nbr int32 [T,3], n_boundary, n_nonmanifold): nbr[t, e] = the face on the other side of
+    the edge (v_e, v_(e+1)%3) of face t when exactly two faces hold that edge, else -1; the edges held by one face and by three or more.  A
+    face with an index outside [0, n_verts) or with a repeated index has no edges.  One readback of 16 bytes (the two counts)."""
+    if not (torch.is_tensor(tris) and tris.is_cuda and tris.dtype == torch.int32 and tris.dim() == 2 and tris.shape[1] == 3):
+        raise TypeError('face_adjacency_device wants CUDA int32 [T,3] triangles')
+    if not 0 <= int(n_verts) < _INT31:
+        raise L.NeroHipError(f'face_adjacency_device: {n_verts} vertices: negative, or 2^31 or more')
+    nbr, counts = _face_adjacency(tris.contiguous(), n_verts)
+    nb, nm = (int(x) for x in counts.tolist())
+    return nbr, nb, nm
+
+
+def face_charts_device(verts, tris):
+    """verts CUDA float32 [V,3], tris CUDA int32 [T,3] -> (chart int32 [T], face_class int32 [T], nbr int32 [T,3], ChartInfo): the charts of
+    the projection atlas.  A face's class is 2 k + (n_k < 0) for the largest component k of its float64 normal (6: no chart -- an index out
+    of range or repeated, a normal that is zero or not finite); a chart is a set of faces of one class joined edge by edge (nbr as
+    face_adjacency_device gives it); charts are numbered in ascending order of their smallest face, chartless faces get -1.  One readback
+    of 32 bytes (K and the counts) sizes the per-chart arrays."""
+    verts, tris = _check_mesh('face_charts_device', verts, tris)
+    V, T = verts.shape[0], tris.shape[0]
+    dev = verts.device
+    nbr, counts = _face_adjacency(tris, V)
+    need = int(L.lib.nero_mesh_chart_label_workspace_bytes(T))
+    L.check_workspace_fits(need + 8 * T, dev, what='chart-label workspace')
+    with torch.cuda.device(dev):
+        s = L.stream_ptr()
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        cls = torch.empty(T, dtype=torch.int32, device=dev)
+        chart = torch.empty(T, dtype=torch.int32, device=dev)
+        info = torch.empty(2, dtype=torch.int64, device=dev)
+        p = lambda x: L.ptr(x) if x.numel() else None
+        L.check(L.lib.nero_mesh_chart_label(p(verts), p(tris), T, V, p(nbr), L.ptr(ws), p(cls), p(chart), L.ptr(info), s))
+        K, chartless, nb, nm = (int(x) for x in torch.cat([info, counts]).tolist())
+        out = ChartInfo(K=K, chart_class=torch.empty(K, dtype=torch.int32, device=dev), n_faces=torch.empty(K, dtype=torch.int32, device=dev),
+                        box=torch.empty((K, 4), dtype=torch.float32, device=dev), n_boundary=nb, n_nonmanifold=nm, n_chartless=chartless)
+        if K:
+            L.check(L.lib.nero_mesh_chart_stats(L.ptr(verts), L.ptr(tris), T, V, L.ptr(chart), L.ptr(cls), K, L.ptr(out.chart_class),
+                                                L.ptr(out.n_faces), L.ptr(out.box), s))
+    return chart, cls, nbr, out
 
 
 # ---- simplification ---------------------------------------------------------------------------------------------------------------------

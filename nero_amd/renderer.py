@@ -801,7 +801,8 @@ class NeROMaterialRenderer(nn.Module):
 
     def extract_texture_maps(self, **kw):
         """albedo / metallic / roughness baked into UV texture maps on the device (extract_materials_texture_map.py): nero_amd.texture.
-        bake_materials(self, **kw) -- vt / ft of any unwrapper, or the built-in simple_atlas"""
+        bake_materials(self, **kw) -- vt / ft of any unwrapper, or atlas='triangles' (the built-in simple_atlas, the default) / atlas='charts'
+        (the projection atlas, nero_amd.texture.chart_atlas)"""
         from .texture import bake_materials
         return bake_materials(self, **kw)
 

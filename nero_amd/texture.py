@@ -1,13 +1,15 @@
 """Baking the Stage-II materials into UV texture maps on the device (libnero_hip.so, nero_uv_* / nero_tex_*), and the textured OBJ.
 
 The reference does this in extract_materials_texture_map.py with xatlas (unwrap), nvdiffrast (rasterise / interpolate in UV space), scipy
-(dilation / erosion), sklearn (kd-tree gutter fill) and cv2 (resize, images), copying every 640 k-texel chunk to the host.  Only the unwrapping
-needs xatlas; every other step is a kernel of nero_amd/csrc/texture.hip here:
+(dilation / erosion), sklearn (kd-tree gutter fill) and cv2 (resize, images), copying every 640 k-texel chunk to the host.  Every
+step is a kernel of nero_amd/csrc/texture.hip or mesh_atlas.hip here:
   * rasterize_uv / interpolate: coverage in UV space by an exact integer rule, positions interpolated in float64 and compacted by prefix sum;
   * quantize: linear_to_srgb, 8 bits;
   * gutter_regions / fill_gutter: the 32-texel gutter filled from the nearest chart-border texel;
   * downsample2: the 2 x 2 mean of the supersampled maps;
   * bake_materials: all of it around NeROMaterialRenderer.predict_materials, the only host traffic being the count readbacks;
+  * chart_atlas: the projection atlas in place of xatlas: charts of faces that look along one signed axis, projected at one
+    texel density and shelf-packed; uv_overlap measures what such an atlas (or anyone's) covers twice;
   * simple_atlas: a dependency-free one-chart-per-triangle atlas for when no unwrapper is at hand; any (vt, ft) can be passed instead;
   * write_textured_obj / read_textured_obj: the reference's OBJ / MTL layout with lossless PNG maps.
 Conventions (include/nero_hip.h): maps are [h, w] row-major, texel (row y, column x) has its centre at u = (x + 0.5) / w, v = (y + 0.5) / h."""
@@ -25,6 +27,15 @@ _lib = L.lib
 _lib.nero_uv_raster_workspace_bytes.restype = C.c_size_t
 _lib.nero_uv_raster_workspace_bytes.argtypes = [C.c_int64]
 _lib.nero_uv_raster.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_uv_overlap_count_workspace_bytes.restype = C.c_size_t
+_lib.nero_uv_overlap_count_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
+_lib.nero_uv_overlap_count.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_mesh_chart_corners_workspace_bytes.restype = C.c_size_t
+_lib.nero_mesh_chart_corners_workspace_bytes.argtypes = [C.c_int64]
+_lib.nero_mesh_chart_corners_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.nero_mesh_chart_corners_emit.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+_lib.nero_mesh_chart_uv.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
+                                    C.c_int, C.c_void_p, C.c_void_p]
 _lib.nero_uv_interp_workspace_bytes.restype = C.c_size_t
 _lib.nero_uv_interp_workspace_bytes.argtypes = [C.c_int, C.c_int]
 _lib.nero_uv_interp.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -165,6 +176,179 @@ def downsample2(tex):
     return out
 
 
+# ---- the chart atlas ------------------------------------------------------------------------------------------------------------------------
+def uv_overlap(vt, ft, h, w):
+    """the number of texel centres of an h x w map that more than one triangle of (vt, ft) covers, by the coverage rule of rasterize_uv (an
+    edge two triangles share never counts twice): nero_uv_overlap_count.  For any atlas, an external unwrapper's too.  One readback of the count."""
+    dev = _dev(vt, ft)
+    vt, ft = _to(vt, torch.float32, dev, 2), _to(ft, torch.int32, dev, 3)
+    h, w = int(h), int(w)
+    with torch.cuda.device(dev):
+        ws = _ws(_lib.nero_uv_overlap_count_workspace_bytes(ft.shape[0], h, w), dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        L.check(_lib.nero_uv_overlap_count(L.ptr(vt), vt.shape[0], L.ptr(ft), ft.shape[0], h, w, L.ptr(ws), L.ptr(count), L.stream_ptr()))
+        return int(count)
+
+
+def pack_charts(box, scale, size, gutter):
+    """the rectangles of the charts at `scale` texels per world unit, shelf-packed into a size x size map: box float [K,4] (min_p, min_q, max_p,
+    max_q) -> rects int64 [K,4] = (ox, oy, w, h), or None when they do not fit.  w = ceil(extent_p scale) + 1, h likewise (float64); charts in
+    the order (-h, -w, chart), left to right on shelves, `gutter` texels between rectangles and between shelves, gutter // 2 texels at the
+    four map edges; a new shelf starts when x + w > size - margin; the last shelf must end at or before size - margin."""
+    b = np.asarray(box, dtype=np.float64).reshape(-1, 4)
+    K = len(b)
+    size, gutter = int(size), int(gutter)
+    m = gutter // 2
+    with np.errstate(invalid='ignore', over='ignore'):
+        wf, hf = np.ceil((b[:, 2] - b[:, 0]) * scale) + 1, np.ceil((b[:, 3] - b[:, 1]) * scale) + 1
+    if K and not (np.all(wf <= size) and np.all(hf <= size)):        # (NaN and infinity too)
+        return None
+    w, h = wf.astype(np.int64), hf.astype(np.int64)
+    order = np.lexsort((np.arange(K), -w, -h))
+    wo, ho = w[order], h[order]
+    P = np.concatenate([[0], np.cumsum(wo + gutter)])                # chart j of a shelf that starts at chart s lies at x = m + P[j] - P[s]
+    x, y = np.zeros(K, np.int64), np.zeros(K, np.int64)
+    s_, top = 0, m
+    while s_ < K:
+        e = int(np.searchsorted(P, P[s_] + size - 2 * m + gutter, side='right')) - 1      # the charts s_ .. e - 1 end at or before size - m
+        if e == s_:
+            return None                                             # wider than the map
+        x[s_:e] = m + P[s_:e] - P[s_]
+        y[s_:e] = top
+        top += int(ho[s_]) + gutter                                 # (the first chart of a shelf is its tallest)
+        s_ = e
+    if K and top - gutter > size - m:
+        return None
+    rects = np.zeros((K, 4), np.int64)
+    rects[order] = np.stack([x, y, wo, ho], -1)
+    return rects
+
+
+def _min_cell_size(K, gutter):
+    size = 1
+    while pack_charts(np.zeros((K, 4)), 0.0, size, gutter) is None:
+        size += 1
+    return size
+
+
+def choose_scale(box, size, gutter=4, texels_per_unit=None):
+    """-> (scale, rects, bisection steps): the texel density of chart_atlas.  texels_per_unit is used as it is (ValueError when it does not
+    fit).  Otherwise hi = (size - 2 (gutter // 2) - 1) / the largest extent of a chart (1 when that is 0) is taken when it fits; else 32
+    bisection steps between lo = 0 and hi (mid = 0.5 (lo + hi); a mid that fits becomes lo) and the result is lo.  Scale 0 makes every
+    rectangle one texel; when even that does not fit, ValueError names the smallest size that holds the cells."""
+    b = np.asarray(box, dtype=np.float64).reshape(-1, 4)
+    if texels_per_unit is not None:
+        scale = float(texels_per_unit)
+        if not (np.isfinite(scale) and scale >= 0):
+            raise ValueError(f'chart_atlas: texels_per_unit must be finite and >= 0, got {texels_per_unit}')
+        rects = pack_charts(b, scale, size, gutter)
+        if rects is None:
+            raise ValueError(f'chart_atlas: {len(b)} charts at {scale} texels per unit do not fit a map of {size} texels with gutter {gutter}')
+        return scale, rects, 0
+    ext = float(max((b[:, 2] - b[:, 0]).max(), (b[:, 3] - b[:, 1]).max())) if len(b) else 0.0
+    if not np.isfinite(ext):
+        raise ValueError('chart_atlas: a chart has a box that is not finite')
+    hi = max(0.0, (size - 2 * (gutter // 2) - 1) / ext) if ext > 0 else 1.0
+    rects = pack_charts(b, hi, size, gutter)
+    if rects is not None:
+        return hi, rects, 0
+    if pack_charts(b, 0.0, size, gutter) is None:
+        raise ValueError(f'chart_atlas: {len(b)} charts of one texel each do not fit a map of {size} texels with gutter {gutter}: the smallest '
+                         f'size that works is {_min_cell_size(len(b), gutter)}')
+    lo, steps = 0.0, 0
+    for _ in range(32):
+        mid = 0.5 * (lo + hi)
+        steps += 1
+        if pack_charts(b, mid, size, gutter) is not None:
+            lo = mid
+        else:
+            hi = mid
+    return lo, pack_charts(b, lo, size, gutter), steps
+
+
+class AtlasInfo:
+    """what chart_atlas made: n_charts, scale (texels per world unit), rects int64 [K,4] (ox, oy, w, h in texels, host), fill (the area of the
+    rectangles over size^2), overlap_texels (texel centres at `size` that more than one triangle covers: 0 unless a chart folds over itself
+    in its projection), bisection_steps, charts (nero_amd.mesh.ChartInfo); and on the device chart int32 [T] (-1: no chart), face_class
+    int32 [T], nbr int32 [T,3], vt_vertex int32 [n_vt] (the mesh vertex of each UV vertex, xatlas's vmapping; -1 for the last one when a
+    face has no chart), vt_chart int32 [n_vt]"""
+    __slots__ = ('n_charts', 'scale', 'rects', 'fill', 'overlap_texels', 'bisection_steps', 'charts', 'chart', 'face_class', 'nbr', 'vt_vertex',
+                 'vt_chart', 'size', 'gutter')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def chart_corners_device(tris, n_verts, chart, K):
+    """tris CUDA int32 [T,3], chart CUDA int32 [T] (face_charts_device) -> (ft int32 [T,3], vt_vertex int32 [n_vt], vt_chart int32 [n_vt]):
+    one UV vertex per (chart, mesh vertex) pair in ascending order, plus a last one (-1, -1) for the corners of chartless faces
+    (nero_mesh_chart_corners_count / _emit).  One readback of the totals sizes the outputs."""
+    dev = tris.device
+    T = tris.shape[0]
+    need = int(_lib.nero_mesh_chart_corners_workspace_bytes(T))
+    if T and need == 0:
+        raise L.NeroHipError(f'chart_corners_device: {T} triangles: 2^31 or more corners')
+    L.check_workspace_fits(need + 12 * T, dev, what='chart-corner workspace')
+    with torch.cuda.device(dev):
+        s = L.stream_ptr()
+        ws = _ws(need, dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(_lib.nero_mesh_chart_corners_count(L.ptr(tris) if T else None, T, int(n_verts), L.ptr(chart) if T else None, int(K), L.ptr(ws),
+                                                   L.ptr(totals), s))
+        n_vt = int(totals[0])
+        ft = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        vv = torch.empty(n_vt, dtype=torch.int32, device=dev)
+        vc = torch.empty(n_vt, dtype=torch.int32, device=dev)
+        L.check(_lib.nero_mesh_chart_corners_emit(T, L.ptr(ws), L.ptr(ft) if T else None, L.ptr(vv) if n_vt else None, L.ptr(vc) if n_vt else None,
+                                                  n_vt, s))
+    return ft, vv, vc
+
+
+def chart_uv_device(verts, vt_vertex, vt_chart, chart_class, box, rects, scale, size):
+    """the UV coordinates of the UV vertices for packed rectangles rects [K,4] (host) at `scale`: float32 [n_vt, 2] (nero_mesh_chart_uv)"""
+    dev = verts.device
+    n_vt, K = vt_vertex.shape[0], chart_class.shape[0]
+    with torch.cuda.device(dev):
+        origin = torch.from_numpy(np.ascontiguousarray(np.asarray(rects).reshape(-1, 4)[:, :2], dtype=np.int32)).to(dev)
+        vt = torch.empty((n_vt, 2), dtype=torch.float32, device=dev)
+        p = lambda x: L.ptr(x) if x.numel() else None
+        L.check(_lib.nero_mesh_chart_uv(p(verts), verts.shape[0], p(vt_vertex), p(vt_chart), n_vt, p(chart_class), p(box), p(origin), K, float(scale),
+                                        int(size), p(vt), L.stream_ptr()))
+    return vt
+
+
+def chart_atlas(verts, tris, size, gutter=4, texels_per_unit=None):
+    """The projection atlas of a mesh: -> (vt float32 [n_vt, 2], ft int32 [T, 3], AtlasInfo), vt and ft on the device, as bake_materials and
+    write_textured_obj take them.
+
+    Charts are edge-connected sets of faces whose normals share a dominant signed axis (nero_amd.mesh.face_charts_device); each chart is
+    projected along that axis at ONE world-to-texel scale for the whole mesh, so texel density is uniform up to the projection (a factor of
+    at most sqrt(3) in length); vertices are duplicated only along the seams between charts.  The chart rectangles are shelf-packed on the
+    host (pack_charts), `gutter` texels apart and gutter // 2 from the map edges; the scale is texels_per_unit, or the largest the packing
+    admits (choose_scale).  With U = ox + 0.5 + (x_p - min_p) scale a chart covers only texel centres of its own rectangle, at `size` and
+    at 2 * size, so charts stay `gutter` texels apart.  Faces with a repeated or out-of-range index, a zero or non-finite
+    normal have no chart: their corners share one UV vertex at (0, 0) and the raster covers nothing for them.  Not built: chart merging,
+    LSCM-style flattening, rotation when packing.  Same-class faces joined edge by edge can still overlap in projection (a helical ramp
+    does; scanned objects ordinarily do not): info.overlap_texels measures it.  Deterministic: the same mesh gives the same atlas bit for
+    bit.  Raises ValueError when texels_per_unit does not fit or when the map cannot hold one texel per chart."""
+    from . import mesh as M
+    dev = _dev(verts, tris)
+    size, gutter = int(size), int(gutter)
+    if not 1 <= size <= 16384 or gutter < 0:
+        raise ValueError(f'chart_atlas: size must be in [1, 16384] and gutter >= 0, got {size} and {gutter}')
+    v_d, f_d = _to(verts, torch.float32, dev, 3), _to(tris, torch.int32, dev, 3)
+    chart, cls, nbr, ci = M.face_charts_device(v_d, f_d)
+    ft, vv, vc = chart_corners_device(f_d, v_d.shape[0], chart, ci.K)
+    box = ci.box.cpu().numpy()                                       # K rows: the packing is host work
+    scale, rects, steps = choose_scale(box, size, gutter, texels_per_unit)
+    vt = chart_uv_device(v_d, vv, vc, ci.chart_class, ci.box, rects, scale, size)
+    info = AtlasInfo(n_charts=ci.K, scale=scale, rects=rects, fill=float((rects[:, 2] * rects[:, 3]).sum()) / float(size * size),
+                     overlap_texels=uv_overlap(vt, ft, size, size), bisection_steps=steps, charts=ci, chart=chart, face_class=cls, nbr=nbr,
+                     vt_vertex=vv, vt_chart=vc, size=size, gutter=gutter)
+    return vt, ft, info
+
+
 # ---- the built-in atlas ---------------------------------------------------------------------------------------------------------------------
 def simple_atlas(verts, tris, size):
     """A deterministic atlas with one chart per triangle and no dependencies: -> (vt float32 [3T, 2], ft int32 [T, 3]).
@@ -201,15 +385,16 @@ def simple_atlas(verts, tris, size):
 
 
 # ---- the pipeline ---------------------------------------------------------------------------------------------------------------------------
-def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=1 << 19, border=3, return_intermediates=False):
+def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=1 << 19, border=3, return_intermediates=False, atlas='triangles'):
     """NeROMaterialRenderer -> {'albedo' [size, size, 3], 'metallic' [size, size], 'roughness' [size, size]: uint8 device tensors, 'mask'
     [size, size] bool (a chart covers the texel), 'vt', 'ft'}: extract_materials_texture_map.py:89-160 on the device.
 
     Rasterise the UV triangles at size * ssaa, interpolate the mesh vertices at the covered texels, evaluate predict_materials there in chunks
     of `chunk` rows with the packed kernels cached (as predict_materials_of_vertices does), quantise, fill the `pad`-texel gutter at the
     supersampled size, halve.  Channels follow predict_materials_n2m (network/field.py:925-932): albedo, metallic, roughness -- the network's
-    roughness WITHOUT the square root predict_materials_of_vertices applies.  vt / ft default to simple_atlas of the renderer's mesh at `size`;
-    pass an unwrapper's (xatlas) for a real asset.  The only host traffic is the count readbacks of rasterize_uv / interpolate.  The MLPs run
+    roughness WITHOUT the square root predict_materials_of_vertices applies.  Without vt / ft the atlas is made here: atlas='triangles' (the
+    default) is simple_atlas of the renderer's mesh at `size`, atlas='charts' is chart_atlas at `size` (the result then also holds
+    'atlas_info'); or pass an unwrapper's vt / ft (xatlas).  The only host traffic is the count readbacks of rasterize_uv / interpolate.  The MLPs run
     on this project's fp32-grade engine (the reference: fp16 autocast), so single 8-bit levels can differ from the reference's maps.
     return_intermediates: also 'tri_id', 'texel', 'points', 'values' [n, 5], 'region', 'source' and 'texture' (the filled maps [H, W, 5])
     at the supersampled size."""
@@ -221,7 +406,13 @@ def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=
         raise RuntimeError('bake_materials runs on the GPU: move the renderer to a CUDA device first')
     if (vt is None) != (ft is None):
         raise ValueError('bake_materials: pass both vt and ft, or neither')
-    if vt is None:
+    if atlas not in ('triangles', 'charts'):
+        raise ValueError(f"bake_materials: atlas must be 'triangles' or 'charts', got {atlas!r}")
+    atlas_info = None
+    if vt is None and atlas == 'charts':
+        with torch.cuda.device(dev):
+            vt, ft, atlas_info = chart_atlas(_to(verts, torch.float32, dev, 3), _to(tris, torch.int32, dev, 3), size)
+    elif vt is None:
         vt, ft = simple_atlas(verts, tris, size)
     if np.asarray(ft.cpu() if torch.is_tensor(ft) else ft).shape[0] != tris.shape[0]:
         raise ValueError(f'bake_materials: ft has {len(ft)} faces, the mesh {tris.shape[0]}')
@@ -251,6 +442,8 @@ def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=
             mask_out = mask > 0
         out = {'albedo': tex[..., 0:3].contiguous(), 'metallic': tex[..., 3].contiguous(), 'roughness': tex[..., 4].contiguous(), 'mask': mask_out,
                'vt': vt, 'ft': ft}
+        if atlas_info is not None:
+            out['atlas_info'] = atlas_info
         if return_intermediates:
             out.update(tri_id=tri_id, texel=texel, points=pts, values=values, region=region, source=src, texture=tex_ss)
     return out

@@ -4,11 +4,16 @@ extract_materials_texture_map.py) through nero_amd.texture -- no xatlas / nvdiff
 
     python scripts/extract_texture_maps.py --cfg configs/material/syn/bell.yaml --ckpt data/model/bell_material/model.pth --out data/materials/bell
     python scripts/extract_texture_maps.py --mesh mesh.ply --ckpt model.pth --uv atlas.npz --size 2048 --out out_dir
+    python scripts/extract_texture_maps.py --mesh mesh.ply --ckpt model.pth --atlas charts --size 2048 --out out_dir
 
 --cfg: the material YAML (or JSON); its `mesh` entry names the Stage-I mesh unless --mesh does.  --ckpt: a trainer checkpoint (the
 `network_state_dict` entry) or a bare state dict; without it the maps show the freshly initialised network (a dry run of the pipeline).
 --uv: an .npz with `vt` [nvt, 2] in [0, 1] and `ft` [T, 3] from any unwrapper (xatlas: `vmapping, ft, vt = xatlas.parametrize(v, f)`); without it
-the built-in one-chart-per-triangle atlas is used, which needs size >= 4 * ceil(sqrt(T / 2)) -- a fallback for small or decimated meshes."""
+--atlas chooses the built-in one: `triangles` (the default), one chart per triangle, which needs size >= 4 * ceil(sqrt(T / 2)) -- a fallback for
+small or decimated meshes; `charts`, the projection atlas of nero_amd.texture.chart_atlas (--gutter texels between charts), for a mesh as it
+comes from the clean-up.  With `charts` the number of charts, the scale (texels per world unit), the fill and the texels covered twice are
+printed, a warning is given when any texel is covered twice, and the atlas is saved as <name>_atlas.npz next to the OBJ (vt, ft, vt_vertex,
+vt_chart, chart, rects, scale)."""
 import argparse
 import json
 import os
@@ -29,7 +34,7 @@ def load_cfg(path):
     return yaml.safe_load(text)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--cfg')
     ap.add_argument('--ckpt')
@@ -38,9 +43,11 @@ def main():
     ap.add_argument('--ssaa', type=int, default=2, choices=(1, 2))
     ap.add_argument('--pad', type=int, default=32)
     ap.add_argument('--uv', help='.npz holding vt and ft')
+    ap.add_argument('--atlas', choices=('triangles', 'charts'), default='triangles', help='the built-in atlas used without --uv')
+    ap.add_argument('--gutter', type=int, default=4, help='texels between the charts of --atlas charts')
     ap.add_argument('--out', required=True)
     ap.add_argument('--name', default='mesh_0')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if not (args.cfg or args.mesh):
         ap.error('give --cfg (with a mesh entry) or --mesh')
     from nero_amd import texture as TX
@@ -60,10 +67,26 @@ def main():
     if args.uv:
         z = np.load(args.uv)
         vt, ft = z['vt'], z['ft']
+    info = None
+    if vt is None and args.atlas == 'charts':
+        vt, ft, info = TX.chart_atlas(net.mesh_vertices, net.mesh_triangles, args.size, gutter=args.gutter)
     maps = net.extract_texture_maps(vt=vt, ft=ft, size=args.size, ssaa=args.ssaa, pad=args.pad)
     obj = TX.write_textured_obj(args.out, net.mesh_vertices, net.mesh_triangles, maps['vt'], maps['ft'], maps, name=args.name)
-    print(json.dumps({'obj': obj, 'size': args.size, 'ssaa': args.ssaa, 'pad': args.pad, 'triangles': int(len(f)),
-                      'covered_texels': int(maps['mask'].sum()), 'atlas': 'given' if args.uv else 'simple_atlas'}))
+    report = {'obj': obj, 'size': args.size, 'ssaa': args.ssaa, 'pad': args.pad, 'triangles': int(len(f)),
+              'covered_texels': int(maps['mask'].sum()), 'atlas': 'given' if args.uv else ('chart_atlas' if info else 'simple_atlas')}
+    if info is not None:
+        npz = os.path.join(args.out, args.name + '_atlas.npz')
+        host = lambda x: x.cpu().numpy()
+        np.savez(npz, vt=host(vt), ft=host(ft), vt_vertex=host(info.vt_vertex), vt_chart=host(info.vt_chart), chart=host(info.chart),
+                 rects=info.rects, scale=np.float64(info.scale))
+        report.update(charts=info.n_charts, scale=info.scale, fill=round(info.fill, 4), overlap_texels=info.overlap_texels,
+                      chartless_faces=info.charts.n_chartless, gutter=args.gutter, atlas_npz=npz)
+        print(f'chart atlas: {info.n_charts} charts, {info.scale:.6g} texels per unit, fill {info.fill:.3f}, {info.overlap_texels} texels '
+              f'covered twice', file=sys.stderr)
+        if info.overlap_texels > 0:
+            print(f'warning: {info.overlap_texels} texel centres are covered by more than one triangle: a chart folds over itself in its '
+                  f'projection, and the lowest face wins there', file=sys.stderr)
+    print(json.dumps(report))
 
 
 if __name__ == '__main__':
