@@ -322,8 +322,29 @@ int nero_compact(const float* pts4, const int* ray_off, int R, int T, int* inner
 int nero_gather_inner(const float* pts4, const int* idx, int n, float* x4 /*[rows,4]*/, float* pe /*[rows,40]*/, void* stream);
 int nero_gather_outer(const float* pts4, const float* d, const int* idx, int T, int n, float* pe88, float* pev32, float* dist, void* stream);
 
+/* ---- Stage-I shading and compositing (everything from here to the mesh ray tracer), and nero_pe_vjp / nero_pe_jvp above.
+ *      Argument ranges (anything else: NERO_ERR_ARG before a launch, nothing written; n == 0 / R == 0 returns NERO_OK):
+ *        n >= 0, R >= 0, T >= 1 (T divides the flat sample index: sample k belongs to ray idx[k] / T);
+ *        nero_composite_*: T <= 192: one wavefront per ray, else one thread per ray;
+ *        every pointer is required except:  d_gerr, d_geo (nero_sdf_alpha_bwd: a NULL one contributes nothing);  d_occ (nero_shade_combine_bwd);
+ *        the d_geo argument of nero_shade_combine_bwd (unused);  extra (nero_shade_encode_bwd);  x4 of nero_shade_encode_bwd unless
+ *        sphere_direction;  e1 (nero_pe_vjp);  Lh / hmask, given together or not at all, and dLh, given exactly when Lh is.
+ *      Rows.  "rows" below is NERO_ROW_PAD(n); the MLP chains read whole 64-row blocks, so these outputs get their pad rows
+ *      n .. NERO_ROW_PAD(n)-1 written as ZEROS, every column of the row:
+ *        nero_sdf_alpha_bwd      d_sdf4 [rows,4], dinv [rows]                 (d_grad [n,3]: live rows only)
+ *        nero_shade_encode       Xd, Xs [rows,72|144], Xi [rows,128], Xo [rows,96]      (mat [n,8]: live rows only)
+ *        nero_human_encode       Xh [rows,24], hmask [rows]
+ *        nero_shade_combine_bwd  dLd, dLs, dLi, dLo, dLh [rows,4]             (dmat [n,8]: live rows only)
+ *        nero_shade_encode_bwd   d_geo [rows,8], dm_raw, dr_raw, da_raw [rows,4]
+ *        nero_nerf_head_bwd      d_sig4, d_rgb4 [rows,4]
+ *        nero_pe_jvp / nero_encode_pe   out [rows,ldo] (and columns beyond the encoding of the live rows)
+ *      Every other output is written for the n live rows (R rays) only and nothing behind them is touched: alpha, geo, gerr, color,
+ *      occ_prob, rec, extra, the nerf head's alpha / color, weights, rgb, d_alphaRT, d_colorRT, d_a, d_c; nero_pe_vjp writes out[r,0:3]
+ *      and leaves the columns up to ldo alone; nero_scatter_samples writes exactly the slots idx names.  Gradient rows [.,4] carry their
+ *      values in the leading columns (d_sdf4: 1, dm_raw / dr_raw: 1, da_raw: 3, dL*: 3, dLo: 1, dLh: 4) and zeros behind. ---- */
 /* ---- inner samples: NeuS alpha + shading frame + eikonal term (compute_sdf_alpha, network/renderer.py:484-512, 574) ---- */
-/* geo [rows,8] = { nhat(3), NoV, refl(3), |grad| };  variance: device pointer to deviation_network.variance */
+/* geo [rows,8] = { nhat(3), NoV, refl(3), |grad| };  variance: device pointer to deviation_network.variance.  nhat = grad / max(|grad|, 1e-12)
+ * (F.normalize): on a row with grad == 0 d_grad still receives d_nhat / 1e-12, the norm itself carries no gradient there */
 int nero_sdf_alpha_fwd(const float* sdf4, const float* grad, const float* x4, const int* idx, const float* d, int T,
                        const float* variance, float anneal, int n, float* alpha, float* geo, float* gerr, void* stream);
 int nero_sdf_alpha_bwd(const float* sdf4, const float* grad, const float* x4, const int* idx, const float* d, int T,

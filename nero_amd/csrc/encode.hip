@@ -99,7 +99,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void pe_jvp_kernel(const float* __restri
 extern "C" {
 
 int nero_encode_pe(const float* x, int ldx, int dim, int n_freq, int n, float* out, int ldo, void* stream) {
-    if (!x || !out || dim < 1 || dim > 4 || dim * (1 + 2 * n_freq) > ldo) return nero_fail(NERO_ERR_ARG, "nero_encode_pe: bad argument");
+    if (!x || !out || n < 0 || n_freq < 0 || dim < 1 || dim > 4 || dim * (1 + 2 * n_freq) > ldo) return nero_fail(NERO_ERR_ARG, "nero_encode_pe: bad argument");
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(encode_pe_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, ldx, dim, n_freq, n, n_pad, out, ldo);
@@ -108,14 +108,14 @@ int nero_encode_pe(const float* x, int ldx, int dim, int n_freq, int n, float* o
 
 int nero_pe_vjp(const float* x, int ldx, const float* e0, int ld0, const float* e1, int ld1, int n_freq, int n,
                 float* out, int ldo, void* stream) {
-    if (!x || !e0 || !out || n_freq < 0 || n_freq > 6) return nero_fail(NERO_ERR_ARG, "nero_pe_vjp: bad argument (n_freq <= 6)");
+    if (!x || !e0 || !out || n_freq < 0 || n_freq > 6 || n < 0) return nero_fail(NERO_ERR_ARG, "nero_pe_vjp: bad argument (n_freq <= 6)");
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(pe_vjp_kernel, dim3((n + ROW_BLOCK - 1) / ROW_BLOCK), dim3(ROW_BLOCK), 0, (hipStream_t)stream, x, ldx, e0, ld0, e1, ld1, n_freq, n, out, ldo);
     return nero_check_launch("nero_pe_vjp");
 }
 
 int nero_pe_jvp(const float* x, int ldx, const float* t, int ldt, int n_freq, int n, float* out, int ldo, void* stream) {
-    if (!x || !t || !out || n_freq < 0 || n_freq > 6 || 3 * (1 + 2 * n_freq) > ldo || ldo > 40)
+    if (!x || !t || !out || n < 0 || n_freq < 0 || n_freq > 6 || 3 * (1 + 2 * n_freq) > ldo || ldo > 40)
         return nero_fail(NERO_ERR_ARG, "nero_pe_jvp: bad argument (n_freq <= 6, 3 (1 + 2 n_freq) <= ldo <= 40)");
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;

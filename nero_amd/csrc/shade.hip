@@ -189,8 +189,8 @@ __global__ void sdf_alpha_bwd_kernel(const float* __restrict__ sdf4, const float
         float dn[3];
         for (int c = 0; c < 3; ++c) dn[c] = q[c] + q[4 + c] * 2.f * nov + (q[3] + 2.f * drn) * v[c];
         const float dot = dn[0] * nh[0] + dn[1] * nh[1] + dn[2] * nh[2];
-        if (gn >= 1e-12f)
-            for (int c = 0; c < 3; ++c) dg[c] += (dn[c] - nh[c] * dot) / gd;
+        // nhat = g / max(|g|, 1e-12) (F.normalize): on a zero gradient row the norm carries no gradient, the quotient still does (d_nhat / 1e-12)
+        for (int c = 0; c < 3; ++c) dg[c] += (gn >= 1e-12f ? dn[c] - nh[c] * dot : dn[c]) / gd;
     }
     for (int c = 0; c < 3; ++c) d_grad[k * 3 + c] = dg[c];
 }
@@ -818,12 +818,15 @@ __global__ void gather_sample_grads_kernel(const float* __restrict__ d_alphaRT, 
 }  // namespace
 
 #define GRID1D(n) dim3(((n) + 127) / 128), dim3(128), 0, (hipStream_t)stream
+// argument contract of every entry point below (include/nero_hip.h): refused before any launch, nothing written
+#define REQUIRE(fn, cond) do { if (!(cond)) return nero_fail(NERO_ERR_ARG, fn ": bad argument (" #cond ")"); } while (0)
 #define CHECK_IDE() do { if (init_ide_tables() != 0) return nero_fail(NERO_ERR_LAUNCH, "IDE coefficient table of ide.h differs from the libm one"); } while (0)
 
 extern "C" {
 
 int nero_sdf_alpha_fwd(const float* sdf4, const float* grad, const float* x4, const int* idx, const float* d, int T,
                        const float* variance, float anneal, int n, float* alpha, float* geo, float* gerr, void* stream) {
+    REQUIRE("nero_sdf_alpha_fwd", sdf4 && grad && x4 && idx && d && variance && alpha && geo && gerr && n >= 0 && T >= 1);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(sdf_alpha_fwd_kernel, GRID1D(n), sdf4, grad, x4, idx, d, T, variance, anneal, n, alpha, geo, gerr);
     return nero_check_launch("nero_sdf_alpha_fwd");
@@ -832,6 +835,7 @@ int nero_sdf_alpha_fwd(const float* sdf4, const float* grad, const float* x4, co
 int nero_sdf_alpha_bwd(const float* sdf4, const float* grad, const float* x4, const int* idx, const float* d, int T,
                        const float* variance, float anneal, int n, const float* d_alpha, const float* d_gerr, const float* d_geo,
                        float* d_sdf4, float* d_grad, float* dinv, void* stream) {
+    REQUIRE("nero_sdf_alpha_bwd", sdf4 && grad && x4 && idx && d && variance && d_alpha && d_sdf4 && d_grad && dinv && n >= 0 && T >= 1);
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(sdf_alpha_bwd_kernel, GRID1D(n_pad), sdf4, grad, x4, idx, d, T, variance, anneal, n, n_pad, d_alpha, d_gerr, d_geo, d_sdf4, d_grad, dinv);
@@ -840,6 +844,7 @@ int nero_sdf_alpha_bwd(const float* sdf4, const float* grad, const float* x4, co
 
 int nero_shade_encode(const float* x4, const float* geo, const float* m_raw, const float* r_raw, const float* a_raw, int n,
                       float* mat, float* Xd, float* Xs, float* Xi, float* Xo, int sphere_direction, void* stream) {
+    REQUIRE("nero_shade_encode", x4 && geo && m_raw && r_raw && a_raw && mat && Xd && Xs && Xi && Xo && n >= 0);
     CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
@@ -850,6 +855,7 @@ int nero_shade_encode(const float* x4, const float* geo, const float* m_raw, con
 int nero_shade_combine_fwd(const float* geo, const float* mat, const float* Ld, const float* Ls, const float* Li, const float* Lo,
                            const float* lut, float exp_max, int n, float* color, float* occ_prob, const float* Lh, const float* hmask,
                            void* stream) {
+    REQUIRE("nero_shade_combine_fwd", geo && mat && Ld && Ls && Li && Lo && lut && color && occ_prob && n >= 0 && !Lh == !hmask);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(shade_combine_fwd_kernel, GRID1D(n), geo, mat, Ld, Ls, Li, Lo, lut, exp_max, n, color, occ_prob, Lh, hmask);
     return nero_check_launch("nero_shade_combine_fwd");
@@ -857,6 +863,7 @@ int nero_shade_combine_fwd(const float* geo, const float* mat, const float* Ld, 
 
 int nero_shade_inter_results(const float* geo, const float* mat, const float* Ld, const float* Ls, const float* Li, const float* Lo,
                              const float* lut, float exp_max, int n, const float* Lh, const float* hmask, float* rec, void* stream) {
+    REQUIRE("nero_shade_inter_results", geo && mat && Ld && Ls && Li && Lo && lut && rec && n >= 0 && !Lh == !hmask);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(shade_inter_kernel, GRID1D(n), geo, mat, Ld, Ls, Li, Lo, lut, exp_max, n, Lh, hmask, rec);
     return nero_check_launch("nero_shade_inter_results");
@@ -866,6 +873,7 @@ int nero_shade_combine_bwd(const float* geo, const float* mat, const float* Ld, 
                            const float* lut, float exp_max, int n, const float* d_color, const float* d_occ, float* dLd, float* dLs,
                            float* dLi, float* dLo, float* dmat, float* d_geo, const float* Lh, const float* hmask, float* dLh,
                            void* stream) {
+    REQUIRE("nero_shade_combine_bwd", geo && mat && Ld && Ls && Li && Lo && lut && d_color && dLd && dLs && dLi && dLo && dmat && n >= 0 && !Lh == !hmask && !Lh == !dLh);
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(shade_combine_bwd_kernel, GRID1D(n_pad), geo, mat, Ld, Ls, Li, Lo, lut, exp_max, n, n_pad, d_color, d_occ, dLd, dLs, dLi, dLo, dmat, d_geo, Lh, hmask, dLh);
@@ -875,10 +883,10 @@ int nero_shade_combine_bwd(const float* geo, const float* mat, const float* Ld, 
 int nero_shade_encode_bwd(const float* geo, const float* mat, const float* dXd, const float* dXs, const float* dXi, const float* dmat,
                           int n, float* d_geo, float* dm_raw, float* dr_raw, float* da_raw, const float* extra, const float* x4,
                           int sphere_direction, void* stream) {
+    REQUIRE("nero_shade_encode_bwd", geo && mat && dXd && dXs && dXi && dmat && d_geo && dm_raw && dr_raw && da_raw && n >= 0 && (x4 || !sphere_direction));
     CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
-    if (sphere_direction && !x4) return nero_fail(NERO_ERR_ARG, "nero_shade_encode_bwd: sphere_direction needs x4");
     hipLaunchKernelGGL(shade_encode_bwd_kernel, GRID1D(n_pad), geo, mat, dXd, dXs, dXi, dmat, n, n_pad, d_geo, dm_raw, dr_raw, da_raw, extra, x4,
                        sphere_direction);
     return nero_check_launch("nero_shade_encode_bwd");
@@ -886,6 +894,7 @@ int nero_shade_encode_bwd(const float* geo, const float* mat, const float* dXd, 
 
 int nero_human_encode(const float* x4, const float* geo, const float* mat, const int* idx, int T, const float* poses, int n,
                       float* Xh, float* hmask, void* stream) {
+    REQUIRE("nero_human_encode", x4 && geo && mat && idx && poses && Xh && hmask && n >= 0 && T >= 1);
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(human_encode_kernel, GRID1D(n_pad), x4, geo, mat, idx, T, poses, n, n_pad, Xh, hmask);
@@ -894,12 +903,14 @@ int nero_human_encode(const float* x4, const float* geo, const float* mat, const
 
 int nero_human_encode_bwd(const float* x4, const float* geo, const float* mat, const int* idx, int T, const float* poses, int n,
                           const float* dXh, float* extra, void* stream) {
+    REQUIRE("nero_human_encode_bwd", x4 && geo && mat && idx && poses && dXh && extra && n >= 0 && T >= 1);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(human_encode_bwd_kernel, GRID1D(n), x4, geo, mat, idx, T, poses, n, dXh, extra);
     return nero_check_launch("nero_human_encode_bwd");
 }
 
 int nero_nerf_head_fwd(const float* sig4, const float* rgb4, const float* dist, int n, float* alpha, float* color, void* stream) {
+    REQUIRE("nero_nerf_head_fwd", sig4 && rgb4 && dist && alpha && color && n >= 0);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(nerf_head_fwd_kernel, GRID1D(n), sig4, rgb4, dist, n, alpha, color);
     return nero_check_launch("nero_nerf_head_fwd");
@@ -907,6 +918,7 @@ int nero_nerf_head_fwd(const float* sig4, const float* rgb4, const float* dist, 
 
 int nero_nerf_head_bwd(const float* sig4, const float* rgb4, const float* dist, int n, const float* d_alpha, const float* d_color,
                        float* d_sig4, float* d_rgb4, void* stream) {
+    REQUIRE("nero_nerf_head_bwd", sig4 && rgb4 && dist && d_alpha && d_color && d_sig4 && d_rgb4 && n >= 0);
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(nerf_head_bwd_kernel, GRID1D(n_pad), sig4, rgb4, dist, n, n_pad, d_alpha, d_color, d_sig4, d_rgb4);
@@ -914,12 +926,14 @@ int nero_nerf_head_bwd(const float* sig4, const float* rgb4, const float* dist, 
 }
 
 int nero_scatter_samples(const float* a, const float* c, const int* idx, int n, float* alphaRT, float* colorRT, void* stream) {
+    REQUIRE("nero_scatter_samples", a && c && idx && alphaRT && colorRT && n >= 0);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(scatter_samples_kernel, GRID1D(n), a, c, idx, n, alphaRT, colorRT);
     return nero_check_launch("nero_scatter_samples");
 }
 
 int nero_composite_fwd(const float* alphaRT, const float* colorRT, int R, int T, float* weights, float* rgb, void* stream) {
+    REQUIRE("nero_composite_fwd", alphaRT && colorRT && weights && rgb && R >= 0 && T >= 1);
     if (R == 0) return NERO_OK;
     if (T <= 192) hipLaunchKernelGGL(composite_fwd_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, alphaRT, colorRT, R, T, weights, rgb);
     else hipLaunchKernelGGL(composite_fwd_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, alphaRT, colorRT, R, T, weights, rgb);
@@ -928,6 +942,7 @@ int nero_composite_fwd(const float* alphaRT, const float* colorRT, int R, int T,
 
 int nero_composite_bwd(const float* alphaRT, const float* colorRT, const float* weights, const float* d_rgb, int R, int T,
                        float* d_alphaRT, float* d_colorRT, void* stream) {
+    REQUIRE("nero_composite_bwd", alphaRT && colorRT && weights && d_rgb && d_alphaRT && d_colorRT && R >= 0 && T >= 1);
     if (R == 0) return NERO_OK;
     if (T <= 192) hipLaunchKernelGGL(composite_bwd_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, alphaRT, colorRT, weights, d_rgb, R, T, d_alphaRT, d_colorRT);
     else hipLaunchKernelGGL(composite_bwd_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, alphaRT, colorRT, weights, d_rgb, R, T, d_alphaRT, d_colorRT);
@@ -935,6 +950,7 @@ int nero_composite_bwd(const float* alphaRT, const float* colorRT, const float* 
 }
 
 int nero_gather_sample_grads(const float* d_alphaRT, const float* d_colorRT, const int* idx, int n, float* d_a, float* d_c, void* stream) {
+    REQUIRE("nero_gather_sample_grads", d_alphaRT && d_colorRT && idx && d_a && d_c && n >= 0);
     if (n == 0) return NERO_OK;
     hipLaunchKernelGGL(gather_sample_grads_kernel, GRID1D(n), d_alphaRT, d_colorRT, idx, n, d_a, d_c);
     return nero_check_launch("nero_gather_sample_grads");
