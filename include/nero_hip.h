@@ -9,8 +9,9 @@
  * row-major with an explicit leading dimension; every row count `n` may be any value >= 0 but all row buffers must be
  * allocated for NERO_ROW_PAD(n) rows; every call is asynchronous on `stream` (a hipStream_t passed as void*); every
  * function returns 0 on success or a negative error code, with a message available from nero_last_error().
- * Nothing here allocates device memory or synchronises, except nero_bvh_create / nero_bvh_destroy (the library owns BVH
- * handles) and the one-time upload of the IDE coefficient table.
+ * Nothing here allocates device memory or synchronises, except nero_bvh_create / nero_bvh_create_device / nero_bvh_destroy (the
+ * library owns BVH handles), nero_bvh_export (a synchronous copy to the host), the one-time upload of the IDE coefficient table, and
+ * the calls that say they read a count back (one synchronisation each, on `stream`).
  */
 #ifndef NERO_HIP_H
 #define NERO_HIP_H
@@ -424,6 +425,33 @@ int nero_bvh_destroy(void* handle);
  * deeper than the 24-entry LDS stack), 0 = private stack, one request after the other.  Same visit order and arithmetic per ray:
  * bit-identical outputs. */
 int nero_bvh_set_traversal(void* handle, int mode);
+/* ---- the same tree built ON THE DEVICE from a device-resident mesh (bvh_build.hip; DESIGN.md, "BVH build on the device").
+ *      nero_bvh_create splits a range of n > 4 triangles at lo + n / 2, so node indices, ranges, leaf references and depth depend on nT alone;
+ *      the device build sorts where the host partitions (stable, ascending, -0 == +0: equal centroids keep their order) and so produces the
+ *      host tree -- the same node bytes and the same triangles per leaf wherever no two centroids tie at a median -- bit-reproducibly.
+ * nero_bvh_build_workspace_bytes: host arithmetic, no device needed; 0 = unsupported (nV < 3, nT < 1 or nT >= 2^27).  About 84 nT bytes plus
+ *   the radix sort's scratch.  Non-decreasing in nT.
+ * nero_bvh_build_lds_capacity: S, the largest range the finishing kernel sorts in LDS; ranges above it are sorted globally, level by level.
+ * nero_bvh_create_device: d_verts [nV,3] float32 / d_tris [nT,3] int32 are DEVICE arrays, read only; ws: nero_bvh_build_workspace_bytes(nV, nT)
+ *   bytes of device memory, free for reuse once the work queued on `stream` has run.  All work runs on `stream`; the library allocates the
+ *   node and triangle buffers (as nero_bvh_create).  ONE synchronisation: the count of bad triangles (a vertex index outside [0, nV) or a
+ *   non-finite coordinate) is read back on `stream` before anything is allocated; a non-zero count returns NERO_ERR_ARG with the count in
+ *   nero_last_error(), nothing stays allocated and *handle is untouched.  nT < 1, nV < 3, a null pointer or ws_bytes too small:
+ *   NERO_ERR_ARG; nT >= 2^27: NERO_ERR_UNSUPPORTED (leaf references must stay above the no-node sentinel).  The handle has the traversal
+ *   mode and depth nero_bvh_create would have set and serves every nero_bvh_trace*, nero_bvh_set_traversal and nero_bvh_destroy.
+ * nero_bvh_info: any of the four outputs may be NULL.  max_depth = level of the deepest inner node, root = level 1 (0: the root reference is
+ *   a leaf).  root = the root reference (0, or a leaf reference -(n) - 1 when nT <= 4).  Never synchronises.
+ * nero_bvh_export: synchronous copy of the tree to HOST arrays -- n_nodes records of 64 bytes {lmin[3], lmax[3], rmin[3], rmax[3] float32,
+ *   left, right, pad[2] int32} and n_tris records of 48 bytes {v0[3], e1[3], e2[3], pad[3] float32} in leaf order; waits for the device
+ *   first.  Works for handles of either builder. */
+size_t nero_bvh_build_workspace_bytes(int nV, int nT);
+int nero_bvh_build_lds_capacity(void);
+int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int nT, void* ws, size_t ws_bytes, void* stream, void** handle);
+/* time of the calling process's LAST successful nero_bvh_create_device by phase, from HIP events the build records on its stream:
+ * ms [4] (host) = prep, wide levels, finishing kernel, emit.  Waits for that build to finish.  For scripts/bench_bvh_build.py. */
+int nero_bvh_build_last_phase_ms(float* ms);
+int nero_bvh_info(void* handle, int* n_nodes, int* n_tris, int* max_depth, int* root);
+int nero_bvh_export(void* handle, void* nodes_host, void* tris_host);
 
 /* ---- Stage-II Monte-Carlo shading glue (MCShadingNetwork.shade_mixed and helpers, network/field.py:756-1012).
  *      Row r = p*D + j, D = Dd + Ds (j < Dd cosine-weighted diffuse samples, then GGX specular samples).

@@ -19,25 +19,13 @@
 #include <cstring>
 #include <vector>
 #include "../../include/nero_hip.h"
+#include "bvh_types.h"
 #include "common.h"
 
 namespace {
 
 constexpr float MISS_DEPTH = 10.0f;
-constexpr int NONE = -(1 << 30);          // "no node" sentinel (leaf references are > -2^28)
-
-struct Node {                 // 64 bytes
-    float lmin[3], lmax[3], rmin[3], rmax[3];
-    int left, right;          // >= 0: node index; < 0: leaf, -(start*8 + count) - 1
-    int pad[2];
-};
-struct Tri { float v0[3], e1[3], e2[3], pad[3]; };   // 48 bytes, leaf order
-
-struct Bvh {
-    Node* d_nodes = nullptr;
-    Tri* d_tris = nullptr;
-    int n_nodes = 0, n_tris = 0;
-};
+using namespace nero_bvh;                 // Node, Tri, Bvh, Handle, NONE, PL_STACK (bvh_types.h: shared with the device build)
 
 struct Builder {
     const float* V; const int* F;
@@ -232,7 +220,6 @@ __device__ __forceinline__ void leaf_test_batched(const Tri* __restrict__ tris, 
 // 0.57 ms per 1 M synthetic rays against 0.51, 0.83 against 0.73 on the rays of a training step.
 struct ChunkOrder { int n; unsigned char c[32]; };            // n = 0: no explicit order
 constexpr int PL_THREADS = 64;
-constexpr int PL_STACK = 24;               // LDS stack entries per ray (6 KB per workgroup); deeper trees take trace_kernel
 
 // LAUNCH ORDER (round 5, nero_bvh_trace_grouped): the secondary rays of Stage II come as [point][direction] with the cosine-weighted
 // diffuse directions first and the GGX specular ones behind them.  Every ray that points below the geometric surface -- it crosses the
@@ -307,8 +294,6 @@ __global__ __launch_bounds__(PL_THREADS) void trace_overlap_kernel(const Node* _
     }
     write_hit(tris, r, o, d, tbest, best, pos, nrm, depth);
 }
-
-struct Handle { Bvh b; int root; int max_depth; int mode; };
 
 }  // namespace
 

@@ -135,8 +135,9 @@ def voxel_down_sample(points, voxel_size, capacity=None):
 
 
 # ---- depth maps and eval points --------------------------------------------------------------------------------------------------------------
-def _tracer(mesh_or_tracer):
-    """-> (RayTracer, vertices float32 numpy).  Accepts a RayTracer, a (vertices, triangles) pair, or an object with .vertices / .faces"""
+def _tracer(mesh_or_tracer, bvh_build='host'):
+    """-> (RayTracer, vertices float32 numpy).  Accepts a RayTracer, a (vertices, triangles) pair, or an object with .vertices / .faces.
+    bvh_build: where a tracer made here builds its tree (RayTracer(build=...))"""
     m = mesh_or_tracer
     if isinstance(m, RayTracer):
         return m, m._v
@@ -146,7 +147,7 @@ def _tracer(mesh_or_tracer):
         v, f = np.asarray(m.vertices), np.asarray(m.faces)
     else:
         raise TypeError('expected a RayTracer, a (vertices, triangles) pair or a mesh with .vertices and .faces')
-    rt = RayTracer(v, f)
+    rt = RayTracer(v, f, build=bvh_build)
     return rt, rt._v
 
 
@@ -198,11 +199,11 @@ def _view(rt, verts, pose, K, shape, unproject_offset, want_points):
     return depth, mask, pts
 
 
-def render_depth(mesh_or_tracer, pose, K, shape, as_numpy=True):
+def render_depth(mesh_or_tracer, pose, K, shape, as_numpy=True, bvh_build='host'):
     """rasterize_depth_map's contract (eval_synthetic_shape.py:39-60): -> (depth float32 [h,w] camera-space z, mask bool [h,w]), by casting one
     ray through every pixel centre with the BVH tracer.  Pass a RayTracer to reuse one BVH across views.  Raises ValueError when the mesh
     reaches the tracer's miss distance (10) from the camera."""
-    rt, verts = _tracer(mesh_or_tracer)
+    rt, verts = _tracer(mesh_or_tracer, bvh_build)
     depth, mask, _ = _view(rt, verts, pose, K, shape, 0.0, False)
     mask = mask.bool()
     return (depth.cpu().numpy(), mask.cpu().numpy()) if as_numpy else (depth, mask)
@@ -236,11 +237,11 @@ def _down(parts, voxel_size, dev):
     return cloud if voxel_size is None else voxel_down_sample(cloud, voxel_size)
 
 
-def mesh_eval_points(vertices, triangles, poses, Ks, shapes, voxel_size=0.01, unproject_offset=0.0):
+def mesh_eval_points(vertices, triangles, poses, Ks, shapes, voxel_size=0.01, unproject_offset=0.0, bvh_build='host'):
     """get_mesh_eval_points (eval_synthetic_shape.py:62-84): the mesh's depth map in every view, back-projected, concatenated on the device
     and voxel-down-sampled once -> float32 [m,3] device tensor.  shapes: one (h, w) for all views or one per view; voxel_size None: the
-    raw concatenated cloud."""
-    rt = RayTracer(vertices, triangles)
+    raw concatenated cloud.  bvh_build='device': the tracer's tree is built on the GPU (the mesh may be CUDA tensors)."""
+    rt = RayTracer(vertices, triangles, build=bvh_build)
     shapes = np.asarray(shapes).reshape(-1, 2)
     parts = []
     for i, (pose, K) in enumerate(zip(poses, Ks)):
@@ -254,12 +255,13 @@ def depth_eval_points(depths, masks, poses, Ks, voxel_size=0.01, unproject_offse
     return _down(parts, voxel_size, _device())
 
 
-def eval_mesh(vertices, triangles, poses, Ks, shapes, gt_points=None, gt_depths=None, gt_masks=None, voxel_size=0.01, unproject_offset=0.0):
+def eval_mesh(vertices, triangles, poses, Ks, shapes, gt_points=None, gt_depths=None, gt_masks=None, voxel_size=0.01, unproject_offset=0.0,
+              bvh_build='host'):
     """the synthetic procedure (eval_synthetic_shape.py main): Chamfer distance between the mesh's eval points and the ground truth, given
     either as points (the data set's eval_pts.ply) or as per-view depth maps + masks"""
     if (gt_points is None) == (gt_depths is None):
         raise ValueError('eval_mesh: give the ground truth either as gt_points or as gt_depths + gt_masks')
-    pr = mesh_eval_points(vertices, triangles, poses, Ks, shapes, voxel_size, unproject_offset)
+    pr = mesh_eval_points(vertices, triangles, poses, Ks, shapes, voxel_size, unproject_offset, bvh_build)
     if gt_points is None:
         if gt_masks is None:
             raise ValueError('eval_mesh: gt_depths needs gt_masks')

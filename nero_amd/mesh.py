@@ -110,6 +110,16 @@ def index_to_world(verts, resolution, bound_min, bound_max):
     return v / (resolution - 1.0) * (bmax - bmin)[None, :] + bmin[None, :]
 
 
+def index_to_world_device(verts, resolution, bound_min, bound_max):
+    """index_to_world for a mesh that stays on the device: the same float64 expression, operation by operation, on the tensor's device,
+    rounded to float32 -- the bits index_to_world(...).astype(float32) gives, which is what write_ply stores.  verts: CUDA tensor [V,3]"""
+    bmin = np.asarray(bound_min.detach().cpu().numpy() if torch.is_tensor(bound_min) else bound_min)
+    bmax = np.asarray(bound_max.detach().cpu().numpy() if torch.is_tensor(bound_max) else bound_max)
+    span = torch.from_numpy(np.asarray(bmax - bmin, dtype=np.float64)).to(verts.device)
+    base = torch.from_numpy(np.asarray(bmin, dtype=np.float64)).to(verts.device)
+    return (verts.double() / (resolution - 1.0) * span[None, :] + base[None, :]).float().contiguous()
+
+
 # ---- connected components and clean-up ---------------------------------------------------------------------------------------------------
 class MeshComponents:
     """the connected components of a mesh (connected_components_device): K, and on the mesh's device label int32 [V] (the smallest vertex

@@ -9,23 +9,77 @@ from . import _lib as L
 
 
 class RayTracer:
-    def __init__(self, vertices, triangles):
+    """build='host' (default): the tree is built by the library's host builder from numpy arrays (nero_bvh_create).  build='device': the mesh
+    stays (or is put) on the GPU and the same tree is built there (nero_bvh_create_device); `_v` / `_f` remain available as host arrays,
+    copied on first access."""
+
+    def __init__(self, vertices, triangles, build='host'):
+        assert build in ('host', 'device'), build
+        assert triangles.shape[0] > 8, "BVH needs at least 8 triangles."          # same guard as the reference wrapper (:16)
+        self.build = build
+        self._h = None                       # the device BVH is built on first use (construction works without a GPU)
+        self._dv = self._df = None           # build='device': the mesh as CUDA tensors, from first use (or from the caller) on
+        if build == 'device':
+            self._src = (vertices.detach() if torch.is_tensor(vertices) else vertices,
+                         triangles.detach() if torch.is_tensor(triangles) else triangles)
+            self._host = None
+            return
         if torch.is_tensor(vertices):
             vertices = vertices.detach().cpu().numpy()
         if torch.is_tensor(triangles):
             triangles = triangles.detach().cpu().numpy()
-        assert triangles.shape[0] > 8, "BVH needs at least 8 triangles."          # same guard as the reference wrapper (:16)
-        self._v = np.ascontiguousarray(vertices, dtype=np.float32)
-        self._f = np.ascontiguousarray(triangles, dtype=np.int32)
-        self._h = None                       # the device BVH is built on first use (construction works without a GPU)
+        self._host = (np.ascontiguousarray(vertices, dtype=np.float32), np.ascontiguousarray(triangles, dtype=np.int32))
+
+    def _host_arrays(self):
+        if self._host is None:               # build='device': one copy, on first access
+            v, f = self._src
+            v = v.cpu().numpy() if torch.is_tensor(v) else v
+            f = f.cpu().numpy() if torch.is_tensor(f) else f
+            self._host = (np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int32))
+        return self._host
+
+    @property
+    def _v(self):
+        return self._host_arrays()[0]
+
+    @property
+    def _f(self):
+        return self._host_arrays()[1]
+
+    def _device_arrays(self):
+        if self._dv is None:
+            v, f = self._src
+            v = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            f = f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f, dtype=np.int32))
+            self._dv = v.to(device='cuda', dtype=torch.float32).contiguous()
+            self._df = f.to(device='cuda', dtype=torch.int32).contiguous()
+        return self._dv, self._df
 
     def _handle(self):
         if self._h is None:
             h = C.c_void_p()
-            L.check(L.lib.nero_bvh_create(self._v.ctypes.data_as(C.c_void_p), self._v.shape[0], self._f.ctypes.data_as(C.c_void_p),
-                                          self._f.shape[0], C.byref(h)))
+            if self.build == 'device':
+                v, f = self._device_arrays()
+                L.lib.nero_bvh_build_workspace_bytes.restype = C.c_size_t
+                need = int(L.lib.nero_bvh_build_workspace_bytes(int(v.shape[0]), int(f.shape[0])))
+                if need == 0:
+                    raise NotImplementedError(f'RayTracer(build="device"): no device build for {v.shape[0]} vertices, {f.shape[0]} triangles')
+                with torch.cuda.device(v.device):
+                    ws = torch.empty(need, dtype=torch.uint8, device=v.device)
+                    L.check(L.lib.nero_bvh_create_device(C.c_void_p(v.data_ptr()), int(v.shape[0]), C.c_void_p(f.data_ptr()), int(f.shape[0]),
+                                                         C.c_void_p(ws.data_ptr()), C.c_size_t(need), L.stream_ptr(), C.byref(h)))
+                    ws.record_stream(torch.cuda.current_stream())         # (the build's kernels may still be using it when it is released)
+            else:
+                L.check(L.lib.nero_bvh_create(self._v.ctypes.data_as(C.c_void_p), self._v.shape[0], self._f.ctypes.data_as(C.c_void_p),
+                                              self._f.shape[0], C.byref(h)))
             self._h = h
         return self._h
+
+    def info(self):
+        """{'n_nodes', 'n_tris', 'max_depth', 'root'} of the tree (nero_bvh_info); builds it if need be"""
+        out = [C.c_int() for _ in range(4)]
+        L.check(L.lib.nero_bvh_info(self._handle(), *[C.byref(x) for x in out]))
+        return dict(zip(('n_nodes', 'n_tris', 'max_depth', 'root'), (int(x.value) for x in out)))
 
     def __del__(self):
         try:

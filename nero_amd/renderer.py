@@ -223,7 +223,7 @@ class NeROShapeRenderer(nn.Module):
         return self._sdf_grid(bound_min, bound_max, resolution, chunk, outside_val).cpu().numpy()
 
     def extract_geometry(self, bound_min=(-1., -1., -1.), bound_max=(1., 1., 1.), resolution=512, threshold=0.0, outside_val=1.0,
-                         clean=None, simplify=None):
+                         to_host=True, clean=None, simplify=None):
         """the Stage-I mesh (extract_geometry, network/field.py:1110-1117; extract_mesh.py:24-31): the extract_fields grid, kept on the
         device, through the HIP marching cubes (nero_amd.mesh), mapped to the box in float64 as the reference does.  Only the mesh is copied
         to the host.  -> (vertices float64 [V,3], triangles int64 [T,3]), wound inward (normals towards sdf < threshold), the winding
@@ -231,7 +231,9 @@ class NeROShapeRenderer(nn.Module):
         nero_amd.mesh.clean_mesh_device (keep, min_faces, min_face_ratio; {} drops only unreferenced vertices): the connected-component
         clean-up runs on the device mesh, and only the cleaned mesh is copied.  simplify: None or a dict of the arguments of
         nero_amd.mesh.simplify_mesh_device (cell in grid-index units, or target_faces; origin, placement, dedup): vertex clustering on the
-        device mesh, after the clean-up and before the copy"""
+        device mesh, after the clean-up and before the copy.  to_host=False: nothing is copied -> (vertices float32 CUDA [V,3] in world
+        coordinates, triangles int32 CUDA [T,3]): the same float64 mapping evaluated on the device and rounded to fp32, the bits write_ply
+        would store -- what NeROMaterialRenderer(cfg with 'bvh_build': 'device', mesh=...) and RayTracer(build='device') take"""
         from . import mesh as M
         u = self._sdf_grid(bound_min, bound_max, resolution, 2 ** 21, outside_val)
         v, f = M.marching_cubes_device(u, threshold)
@@ -240,6 +242,8 @@ class NeROShapeRenderer(nn.Module):
             v, f, _ = M.clean_mesh_device(v, f, **clean)
         if simplify is not None:
             v, f, _ = M.simplify_mesh_device(v, f, **simplify)
+        if not to_host:
+            return M.index_to_world_device(v, resolution, bound_min, bound_max), f.to(torch.int32).contiguous()
         return M.index_to_world(v.cpu().numpy(), resolution, bound_min, bound_max), f.cpu().numpy().astype(np.int64)
 
     def _sdf_grid(self, bound_min, bound_max, resolution, chunk, outside_val):
@@ -533,6 +537,7 @@ class NeROMaterialRenderer(nn.Module):
         'train_ray_num': 512, 'test_ray_num': 1024, 'database_name': 'real/bear/raw_1024', 'rgb_loss': 'charbonier',
         'mesh': 'data/meshes/bear_shape-300000.ply', 'shader_cfg': {}, 'reg_mat': True, 'reg_diffuse_light': True,
         'reg_diffuse_light_lambda': 0.1, 'fixed_camera': False,
+        'bvh_build': 'host',          # 'device': the tracer's tree is built on the GPU (RayTracer(build='device')); mesh= may then be CUDA tensors
     }
 
     def __init__(self, cfg, is_train=True, mesh=None):
@@ -552,12 +557,20 @@ class NeROMaterialRenderer(nn.Module):
             else:
                 tm = trimesh.load(self.cfg['mesh'], force='mesh', skip_material=True, process=False)
                 mesh = (np.asarray(tm.vertices), np.asarray(tm.faces))
-        self.ray_tracer = RayTracer(mesh[0], mesh[1])
-        # the mesh itself, for what works on its surface rather than on rays (extract_texture_maps)
-        self.mesh_vertices, self.mesh_triangles = self.ray_tracer._v.reshape(-1, 3), self.ray_tracer._f.reshape(-1, 3)   # float32 / int32, host
+        self.ray_tracer = RayTracer(mesh[0], mesh[1], build=self.cfg['bvh_build'])
         self.cfg['shader_cfg'] = dict(self.cfg['shader_cfg'])
         self.cfg['shader_cfg']['is_real'] = self.cfg['database_name'].startswith('real')
         self.shader_network = MCShadingNetwork(self.cfg['shader_cfg'], lambda o, d: self.trace(o, d))
+
+    # the mesh itself, for what works on its surface rather than on rays (extract_texture_maps): float32 / int32, host (with
+    # 'bvh_build': 'device' copied from the GPU on first access)
+    @property
+    def mesh_vertices(self):
+        return self.ray_tracer._v.reshape(-1, 3)
+
+    @property
+    def mesh_triangles(self):
+        return self.ray_tracer._f.reshape(-1, 3)
 
     def trace(self, rays_o, rays_d):
         """network/renderer.py:719-729: flipped + normalised face normals, hit <=> depth < 10"""

@@ -4,7 +4,7 @@ the search), on the marching-cubes mesh of the model bench.py's inference_bench 
 variance 0.5), at cell = 2 grid steps and at a budget of 100 000 faces.  Beside them the numpy restatement tests/mesh_simplify_ref.py on
 the host of the same box in the same run, mesh copies included.  Prints one JSON line and writes it to profiles/bench_mesh_simplify.json.
 
-    python scripts/bench_mesh_simplify.py [--res 256 512] [--reps 20] [--rays 1048576] [--no-write]
+    python scripts/bench_mesh_simplify.py [--res 256 512] [--reps 20] [--rays 1048576] [--bvh-build {host,device}] [--no-write]
 
 Bytes of the kernels, from the shapes (V vertices, T triangles, C occupied cells, V' / S / T' output vertices, survivors, output faces):
 count reads the vertices and writes keys and ids (24 V), reads tris and the keys of their corners and writes the flags (40 T), scans them
@@ -110,12 +110,13 @@ def host_route(verts, tris, cell):
     return torch.from_numpy(o['verts32']).to(verts.device), torch.from_numpy(o['tris']).to(verts.device)
 
 
-def trace_cost(verts, tris, res, rays_o, rays_d, reps):
-    """BVH build (first use) and the trace of the fixed ray set, on the mesh mapped to the box [-1, 1]^3 -> dict"""
+def trace_cost(verts, tris, res, rays_o, rays_d, reps, bvh_build='host'):
+    """BVH build (first use; bvh_build: by the host builder or on the device) and the trace of the fixed ray set, on the mesh mapped to the
+    box [-1, 1]^3 -> dict"""
     from nero_amd.raytracing import RayTracer
     world = (verts / (res - 1.0) * 2.0 - 1.0).contiguous()
     t0 = time.perf_counter()
-    tracer = RayTracer(world, tris)
+    tracer = RayTracer(world, tris, build=bvh_build)
     _, _, t = tracer.trace(rays_o[:64], rays_d[:64])                  # (the device BVH is built on first use)
     torch.cuda.synchronize()
     build = time.perf_counter() - t0
@@ -129,7 +130,7 @@ def trace_cost(verts, tris, res, rays_o, rays_d, reps):
         if it >= 2:
             ms.append(ev[0].elapsed_time(ev[1]))
     t = t.reshape(-1)
-    return {'faces': int(tris.shape[0]), 'bvh_build_ms': round(build * 1e3, 3), 'trace_ms': round(statistics.median(ms), 4),
+    return {'faces': int(tris.shape[0]), 'bvh_build': bvh_build, 'bvh_build_ms': round(build * 1e3, 3), 'trace_ms': round(statistics.median(ms), 4),
             'rays': int(rays_o.shape[0]), 'hit_fraction': round(float((t < 10).float().mean()), 5),
             'mean_hit_depth': round(float(t[t < 10].double().mean()), 6)}
 
@@ -142,6 +143,7 @@ def main():
     ap.add_argument('--cell', type=float, default=2.0)
     ap.add_argument('--target-faces', type=int, default=100000)
     ap.add_argument('--rays', type=int, default=1 << 20)
+    ap.add_argument('--bvh-build', choices=('host', 'device'), default='host', help='where trace_cost builds the tracer\'s tree')
     ap.add_argument('--no-write', action='store_true')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'this benchmark measures the GPU; there is none'
@@ -175,9 +177,9 @@ def main():
         rb = kernels(verts, tris, info_b.cell, args.reps)
         rb.update(k=info_b.k, simplify_mesh_device_ms=round(d_budget * 1e3, 4), n_duplicates=info_b.n_duplicates)
         row[f'target_{args.target_faces}'] = rb
-        row['trace'] = {'original': trace_cost(verts, tris, res, rays_o, rays_d, 5),
-                        f'cell_{args.cell:g}': trace_cost(v2, f2, res, rays_o, rays_d, 5),
-                        f'target_{args.target_faces}': trace_cost(vb, fb, res, rays_o, rays_d, 5)}
+        row['trace'] = {'original': trace_cost(verts, tris, res, rays_o, rays_d, 5, args.bvh_build),
+                        f'cell_{args.cell:g}': trace_cost(v2, f2, res, rays_o, rays_d, 5, args.bvh_build),
+                        f'target_{args.target_faces}': trace_cost(vb, fb, res, rays_o, rays_d, 5, args.bvh_build)}
         out[f'{res}^3'] = row
         del verts, tris, v2, f2, vb, fb
         torch.cuda.empty_cache()

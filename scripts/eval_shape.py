@@ -29,6 +29,8 @@ def parse(argv=None):
     ap.add_argument('--voxel-size', type=float, default=0.01)
     ap.add_argument('--unproject-offset', type=float, default=0.0,
                     help='0 = the reference (integer pixel coordinates), 0.5 = through the pixel centres')
+    ap.add_argument('--bvh-build', choices=('host', 'device'), default='host',
+                    help='--mesh/--views: where the ray tracer builds its tree (device: on the GPU, same tree)')
     ap.add_argument('--batch_size', type=int, default=None, help='accepted for compatibility with the reference; nothing is batched')
     a = ap.parse_args(argv)
     real, syn = a.pr is not None or a.gt is not None, a.mesh is not None or a.views is not None
@@ -58,7 +60,7 @@ def main(argv=None):
         stem = Path(a.mesh).stem
         v, f = M.read_ply(a.mesh)
         views = np.load(a.views)
-        kw = dict(voxel_size=a.voxel_size, unproject_offset=a.unproject_offset)
+        kw = dict(voxel_size=a.voxel_size, unproject_offset=a.unproject_offset, bvh_build=a.bvh_build)
         if a.gt_points is not None:
             kw['gt_points'] = E.read_ply_points(a.gt_points)
         else:
