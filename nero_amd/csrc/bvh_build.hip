@@ -16,18 +16,22 @@
 //   finish        one workgroup per range of the first level whose ranges fit S: all remaining levels in LDS (finish_kernel, the hot path);
 //   emit          boxes and nodes level by level, bottom-up, then the triangle records in leaf order.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <cstdint>
 #include <cstdio>
 #include "../../include/nero_hip.h"
 #include "bvh_build_plan.h"
 #include "bvh_types.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
 
 namespace {
 
 using namespace nero_bvh;
 using namespace nero_bvh_plan;
+using namespace nero_cub;
+using namespace nero_prims;
+using nero_ws::blocks_of;
 typedef unsigned long long u64;
 
 // S, the LDS capacity of finish_kernel, in triangles.  34 bytes of LDS per triangle (key 8, two slot buffers 2 + 2, centroid 12, triangle 4,
@@ -50,13 +54,7 @@ constexpr int POS_BITS = 12;                           // key of the LDS sort: r
 static_assert(S_CAP >= 256 && S_CAP <= (1 << POS_BITS) && (S_CAP & (S_CAP - 1)) == 0, "S: a power of two in [256, 4096]");
 static_assert(FIN_THREADS % 64 == 0 && FIN_THREADS <= 1024, "whole wavefronts");
 
-// order-preserving image of a float in the unsigned integers (-0 below +0)
-__device__ __forceinline__ unsigned f2o(float f) {
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float o2f(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-// min and max in that order: exact, and defined where the C library's are not (-0 is the smaller zero), so boxes are bit-reproducible
+// min and max in the order of f2o (-0 below +0): exact, and defined where the C library's are not (-0 is the smaller zero), so boxes are bit-reproducible
 __device__ __forceinline__ float tmin(float a, float b) { return f2o(b) < f2o(a) ? b : a; }
 __device__ __forceinline__ float tmax(float a, float b) { return f2o(b) > f2o(a) ? b : a; }
 // the sort key of a centroid coordinate: the two zeros are one value
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(256) void prep_kernel(const float* __restrict__ V, 
     if (t >= nT) return;
     order[t] = (unsigned)t;
     const int i0 = F[t * 3], i1 = F[t * 3 + 1], i2 = F[t * 3 + 2];
-    bool ok = i0 >= 0 && i0 < nV && i1 >= 0 && i1 < nV && i2 >= 0 && i2 < nV;
+    bool ok = in_range(i0, nV) && in_range(i1, nV) && in_range(i2, nV);
     float c[3] = {0.f, 0.f, 0.f}, mn[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
     if (ok) {
 #pragma unroll
@@ -112,17 +110,6 @@ __global__ __launch_bounds__(256) void prep_kernel(const float* __restrict__ V, 
 __global__ __launch_bounds__(256) void ext_init_kernel(unsigned* __restrict__ ext, int n_ranges) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_ranges * 6) ext[i] = (i % 6) < 3 ? 0xFFFFFFFFu : 0u;
-}
-
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
 }
 
 // extents of the centroids of every range of level `l`.  A wavefront's 64 positions lie in one range almost always (ranges here hold more
@@ -322,8 +309,6 @@ __global__ __launch_bounds__(256) void emit_tris_kernel(const float* __restrict_
     out[i] = r;
 }
 
-inline dim3 blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // phase marks of the last build (nero_bvh_build_last_phase_ms): start | prep done || wide levels start | done | finish done | emit done
 enum { EV_START = 0, EV_PREP, EV_WIDE0, EV_WIDE1, EV_FINISH, EV_EMIT, EV_COUNT };
 hipEvent_t g_ev[EV_COUNT];
@@ -372,13 +357,12 @@ int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int 
     g_ev_valid = false;
     mark(EV_START, s);
     if (hipMemsetAsync(bad, 0, sizeof(int), s) != hipSuccess) return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: hipMemsetAsync failed");
-    hipLaunchKernelGGL(prep_kernel, blocks(nT), dim3(256), 0, s, d_verts, nV, d_tris, nT, cen, bmin, bmax, ord, bad);
+    hipLaunchKernelGGL(prep_kernel, dim3(blocks_of(nT)), dim3(256), 0, s, d_verts, nV, d_tris, nT, cen, bmin, bmax, ord, bad);
     if (nero_check_launch("nero_bvh_create_device (prep)") != NERO_OK) return NERO_ERR_LAUNCH;
     mark(EV_PREP, s);
     // the one synchronisation: a mesh with an index out of range or a non-finite coordinate is an error code, not a tree
     int n_bad = -1;
-    if (hipMemcpyAsync(&n_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: reading the bad-triangle count failed");
+    if (int rc = read_back(&n_bad, bad, sizeof(int), s, "nero_bvh_create_device: reading the bad-triangle count failed")) return rc;
     if (n_bad != 0) {
         char msg[160];
         snprintf(msg, sizeof(msg), "nero_bvh_create_device: %d triangle(s) with a vertex index out of range or a non-finite coordinate", n_bad);
@@ -398,26 +382,22 @@ int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int 
         delete h;
         return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: hipMalloc failed");
     }
-    auto fail = [h](const char* msg) {
+    auto drop = [h](int rc) {                                  // (the message is nero_fail's already)
         (void)hipFree(h->b.d_nodes);
         (void)hipFree(h->b.d_tris);
         delete h;
-        return nero_fail(NERO_ERR_LAUNCH, msg);
+        return rc;
     };
 
     mark(EV_WIDE0, s);
     for (int l = 0; l < plan.hand_off; ++l) {
         const int n_ranges = 1 << l;
-        hipLaunchKernelGGL(ext_init_kernel, blocks((size_t)n_ranges * 6), dim3(256), 0, s, ext, n_ranges);
-        hipLaunchKernelGGL(wide_extent_kernel, blocks(nT), dim3(256), 0, s, cen, ord, nT, l, ext);
-        hipLaunchKernelGGL(wide_key_kernel, blocks(nT), dim3(256), 0, s, cen, ord, nT, l, ext, key);
-        size_t need = 0;
-        if (hipcub::DeviceRadixSort::SortPairs((void*)nullptr, need, (const u64*)key, key_alt, (const unsigned*)ord, ord_alt, nT, 0, 32 + l, s) != hipSuccess ||
-            need > L.temp_bytes)
-            return fail("nero_bvh_create_device: the radix sort's temporary storage exceeds the workspace bound");
-        size_t have = L.temp_bytes;
-        if (hipcub::DeviceRadixSort::SortPairs((void*)(w + L.temp), have, (const u64*)key, key_alt, (const unsigned*)ord, ord_alt, nT, 0, 32 + l, s) != hipSuccess)
-            return fail("nero_bvh_create_device: radix sort failed");
+        hipLaunchKernelGGL(ext_init_kernel, dim3(blocks_of((size_t)n_ranges * 6)), dim3(256), 0, s, ext, n_ranges);
+        hipLaunchKernelGGL(wide_extent_kernel, dim3(blocks_of(nT)), dim3(256), 0, s, cen, ord, nT, l, ext);
+        hipLaunchKernelGGL(wide_key_kernel, dim3(blocks_of(nT)), dim3(256), 0, s, cen, ord, nT, l, ext, key);
+        if (int rc = sort_pairs<u64>(w + L.temp, L.temp_bytes, key, key_alt, ord, ord_alt, nT, 32 + l, s,
+                                     "nero_bvh_create_device: radix sort failed"))
+            return drop(rc);
         unsigned* const t = ord; ord = ord_alt; ord_alt = t;
     }
     mark(EV_WIDE1, s);
@@ -425,10 +405,10 @@ int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int 
         hipLaunchKernelGGL(finish_kernel<S_CAP>, dim3(1u << plan.hand_off), dim3(FIN_THREADS), 0, s, cen, ord, plan);
     mark(EV_FINISH, s);
     for (int l = plan.n_levels; l >= 0; --l)
-        hipLaunchKernelGGL(emit_level_kernel, blocks((size_t)1 << l), dim3(256), 0, s, plan, l, ord, bmin, bmax, heap, h->b.d_nodes);
-    hipLaunchKernelGGL(emit_tris_kernel, blocks(nT), dim3(256), 0, s, d_verts, d_tris, ord, nT, h->b.d_tris);
+        hipLaunchKernelGGL(emit_level_kernel, dim3(blocks_of((size_t)1 << l)), dim3(256), 0, s, plan, l, ord, bmin, bmax, heap, h->b.d_nodes);
+    hipLaunchKernelGGL(emit_tris_kernel, dim3(blocks_of(nT)), dim3(256), 0, s, d_verts, d_tris, ord, nT, h->b.d_tris);
     mark(EV_EMIT, s);
-    if (hipGetLastError() != hipSuccess) return fail("nero_bvh_create_device: a kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return drop(nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: a kernel launch failed"));
     g_ev_valid = g_ev_made;
     *handle = h;
     return NERO_OK;

@@ -12,6 +12,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "ws_plan.h"
 
 #if defined(__HIPCC__)
 #define NERO_BVH_HD __host__ __device__
@@ -98,11 +99,6 @@ inline bool make_plan(int nT, int lds_capacity, Plan* out) {
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-// temporary storage of a device radix sort of `items` pairs of `bytes_per_item` bytes: a bound that the build checks against the sort's own
-// query before it sorts (the same bound as mesh_simplify.hip)
-inline size_t sort_temp_bound(int64_t items, size_t bytes_per_item) { return align256((size_t)items * (bytes_per_item + 4) + ((size_t)4 << 20)); }
-
 struct Layout {
     size_t hdr, cen, bmin, bmax, order_a, order_b, key_a, key_b, ext, heap, temp, temp_bytes, total;
     size_t ext_ranges, heap_boxes;
@@ -110,28 +106,23 @@ struct Layout {
 
 inline Layout layout(const Plan& p) {
     Layout w = {};
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += align256(bytes);
-        return here;
-    };
+    nero_ws::Carve c;
     const size_t T = (size_t)p.nT;
-    w.hdr = take(256);                                        // the bad-triangle counter
-    w.cen = take(T * 3 * sizeof(float));                      // [3][nT]
-    w.bmin = take(T * 3 * sizeof(float));                     // [nT][3]
-    w.bmax = take(T * 3 * sizeof(float));
-    w.order_a = take(T * sizeof(uint32_t));
-    w.order_b = take(T * sizeof(uint32_t));
-    w.key_a = take(T * sizeof(uint64_t));
-    w.key_b = take(T * sizeof(uint64_t));
+    w.hdr = c.take(256);                                        // the bad-triangle counter
+    w.cen = c.take(T * 3 * sizeof(float));                      // [3][nT]
+    w.bmin = c.take(T * 3 * sizeof(float));                     // [nT][3]
+    w.bmax = c.take(T * 3 * sizeof(float));
+    w.order_a = c.take(T * sizeof(uint32_t));
+    w.order_b = c.take(T * sizeof(uint32_t));
+    w.key_a = c.take(T * sizeof(uint64_t));
+    w.key_b = c.take(T * sizeof(uint64_t));
     w.ext_ranges = (size_t)1 << (p.hand_off > 0 ? p.hand_off - 1 : 0);          // the widest globally sorted level
-    w.ext = take(w.ext_ranges * 6 * sizeof(uint32_t));
+    w.ext = c.take(w.ext_ranges * 6 * sizeof(uint32_t));
     w.heap_boxes = (size_t)2 << p.n_levels;                   // box of range k of level l at (1 << l) - 1 + k, levels 0 .. n_levels
-    w.heap = take(w.heap_boxes * 6 * sizeof(float));
-    w.temp_bytes = sort_temp_bound((int64_t)T, 12);
-    w.temp = take(w.temp_bytes);
-    w.total = at + 256;                                       // (+ 256: the caller's pointer is aligned up)
+    w.heap = c.take(w.heap_boxes * 6 * sizeof(float));
+    w.temp_bytes = nero_ws::sort_temp_bound((int64_t)T, 12);
+    w.temp = c.take(w.temp_bytes);
+    w.total = c.at + 256;                                       // (+ 256: the caller's pointer is aligned up)
     return w;
 }
 

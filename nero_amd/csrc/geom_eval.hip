@@ -14,16 +14,20 @@
 //                          prefix sum.
 // No atomics decide a value or a position anywhere in this file: two runs are bit-identical.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
+#include "ws_plan.h"
 
 namespace {
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 // ---- nearest neighbour ---------------------------------------------------------------------------------------------------------------------
 constexpr int NN_THREADS = 256;
@@ -133,45 +137,23 @@ struct VxLayout {
     // after the sort: head flags live in keys_a, their exclusive scan in vals_a
 };
 
-size_t vx_sort_temp(int64_t n) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (int)n, 0, 3 * VX_AXIS_BITS);
-    return bytes;
-}
-
-size_t scan_temp_i32(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int*)nullptr, (int*)nullptr, (int)items);
-    return bytes;
-}
-
-VxLayout vx_layout(int64_t n) {
-    VxLayout w{};
-    size_t at = 256;
-    w.partial = at; at += align256((size_t)VX_MAX_PARTIALS * 6 * sizeof(float));
+int vx_layout(int64_t n, VxLayout* w) {
+    *w = VxLayout{};
+    size_t a = 0, b = 0;
+    if (n > 0 && (sort_pairs_temp<uint64_t>(n, 3 * VX_AXIS_BITS, &a) != hipSuccess || scan_temp<int>(n + 1, &b) != hipSuccess))
+        return nero_fail(NERO_ERR_LAUNCH, "nero_voxel_downsample: the scratch-size query of the radix sort or the scan failed");
+    Carve c{256};
+    w->partial = c.take((size_t)VX_MAX_PARTIALS * 6 * sizeof(float));
     if (n > 0) {
-        w.keys_a = at; at += align256((size_t)(n + 1) * sizeof(uint64_t));
-        w.keys_b = at; at += align256((size_t)n * sizeof(uint64_t));
-        w.vals_a = at; at += align256((size_t)(n + 1) * sizeof(uint32_t));
-        w.vals_b = at; at += align256((size_t)n * sizeof(uint32_t));
-        const size_t a = vx_sort_temp(n), b = scan_temp_i32(n + 1);
-        w.temp_bytes = a > b ? a : b;
-        w.temp = at; at += align256(w.temp_bytes);
+        w->keys_a = c.take((size_t)(n + 1) * sizeof(uint64_t));
+        w->keys_b = c.take((size_t)n * sizeof(uint64_t));
+        w->vals_a = c.take((size_t)(n + 1) * sizeof(uint32_t));
+        w->vals_b = c.take((size_t)n * sizeof(uint32_t));
+        w->temp_bytes = a > b ? a : b;
+        w->temp = c.take(w->temp_bytes);
     }
-    w.total = at;
-    return w;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
+    w->total = c.at;
+    return NERO_OK;
 }
 
 // block-wide {min x, y, z, max x, y, z} of m[6] -> thread 0's m (minimum / maximum do not depend on the order they are taken in)
@@ -374,15 +356,15 @@ struct ViewLayout {
     size_t flag, rank, temp, temp_bytes, total;
 };
 
-ViewLayout view_layout(int64_t n) {
-    ViewLayout w{};
-    size_t at = 0;
-    w.flag = at; at += align256((size_t)(n + 1) * sizeof(int));
-    w.rank = at; at += align256((size_t)(n + 1) * sizeof(int));
-    w.temp_bytes = scan_temp_i32(n + 1);
-    w.temp = at; at += align256(w.temp_bytes);
-    w.total = at;
-    return w;
+int view_layout(int64_t n, ViewLayout* w) {
+    if (scan_temp<int>(n + 1, &w->temp_bytes) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_view_points, nero_depth_points: the scratch-size query of the scan of the mask failed");
+    Carve c;
+    w->flag = c.take((size_t)(n + 1) * sizeof(int));
+    w->rank = c.take((size_t)(n + 1) * sizeof(int));
+    w->temp = c.take(w->temp_bytes);
+    w->total = c.at;
+    return NERO_OK;
 }
 
 int check_view(const char* fn, const double* K, const double* pose, int h, int w, ViewCam* cam) {
@@ -405,16 +387,15 @@ int check_view(const char* fn, const double* K, const double* pose, int h, int w
 int depth_points(const char* fn, const float* depth, const unsigned char* mask, const ViewCam& cam, int h, int w, float offset, void* ws,
                  float* pts, int64_t cap, int64_t* n_pts, hipStream_t s) {
     const int n = h * w;
-    const ViewLayout L = view_layout(n);
+    ViewLayout L;
+    if (int rc = view_layout(n, &L)) return rc;
     uint8_t* b = (uint8_t*)ws;
     int* flag = (int*)(b + L.flag);
     int* rank = (int*)(b + L.rank);
     const unsigned blocks = (unsigned)((n + 1 + 255) / 256);
     hipLaunchKernelGGL(view_flag_kernel, dim3(blocks), dim3(256), 0, s, mask, n, flag);
     if (int rc = nero_check_launch(fn)) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int*)flag, rank, n + 1, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "geometry evaluation: the scan of the mask failed");
+    if (int rc = exclusive_sum(b + L.temp, L.temp_bytes, (const int*)flag, rank, n + 1, s, "geometry evaluation: the scan of the mask failed")) return rc;
     hipLaunchKernelGGL(view_points_kernel, dim3(blocks), dim3(256), 0, s, depth, (const int*)flag, (const int*)rank, cam, w, n, offset, pts, cap,
                        n_pts);
     return nero_check_launch(fn);
@@ -469,8 +450,9 @@ int nero_nn_dist(const float* q, int64_t nq, const float* r, int64_t nr, void* w
 }
 
 size_t nero_voxel_downsample_workspace_bytes(int64_t n) {
-    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return 0;
-    return vx_layout(n).total;
+    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return no_workspace("nero_voxel_downsample_workspace_bytes: n must be in [0, 2^31 - 1)");
+    VxLayout L;
+    return vx_layout(n, &L) == NERO_OK ? L.total : 0;
 }
 
 int nero_voxel_downsample(const float* pts, int64_t n, double voxel, void* ws, float* out, int64_t out_cap, int64_t* n_out, void* stream) {
@@ -488,7 +470,8 @@ int nero_voxel_downsample(const float* pts, int64_t n, double voxel, void* ws, f
         return NERO_OK;
     }
     if (!pts) return nero_fail(NERO_ERR_ARG, "nero_voxel_downsample: null points");
-    const VxLayout L = vx_layout(n);
+    VxLayout L;
+    if (int rc = vx_layout(n, &L)) return rc;
     float* partial = (float*)(b + L.partial);
     uint64_t* keys_a = (uint64_t*)(b + L.keys_a);
     uint64_t* keys_b = (uint64_t*)(b + L.keys_b);
@@ -500,25 +483,21 @@ int nero_voxel_downsample(const float* pts, int64_t n, double voxel, void* ws, f
     hipLaunchKernelGGL(vx_bounds_final_kernel, dim3(1), dim3(VX_THREADS), 0, s, (const float*)partial, n_partial, voxel, hdr);
     hipLaunchKernelGGL(vx_key_kernel, dim3(blocks), dim3(VX_THREADS), 0, s, pts, n, voxel, (const VxHeader*)hdr, keys_a, vals_a);
     if (int rc = nero_check_launch("nero_voxel_downsample: keys")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)(b + L.temp), tb, (const uint64_t*)keys_a, keys_b, (const uint32_t*)vals_a, vals_b, (int)n, 0,
-                                           3 * VX_AXIS_BITS, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_voxel_downsample: the radix sort failed");
+    if (int rc = sort_pairs<uint64_t>(b + L.temp, L.temp_bytes, keys_a, keys_b, vals_a, vals_b, n, 3 * VX_AXIS_BITS, s,
+                                      "nero_voxel_downsample: the radix sort failed"))
+        return rc;
     int* flag = (int*)keys_a;                                           // (n + 1 ints in the (n + 1) x 8 bytes of the unsorted keys)
     int* seg = (int*)vals_a;
     hipLaunchKernelGGL(vx_head_kernel, dim3((unsigned)((n + 1 + VX_THREADS - 1) / VX_THREADS)), dim3(VX_THREADS), 0, s, (const uint64_t*)keys_b, n,
                        flag);
     if (int rc = nero_check_launch("nero_voxel_downsample: head flags")) return rc;
-    tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int*)flag, seg, (int)(n + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_voxel_downsample: the scan failed");
+    if (int rc = exclusive_sum(b + L.temp, L.temp_bytes, (const int*)flag, seg, n + 1, s, "nero_voxel_downsample: the scan failed")) return rc;
     hipLaunchKernelGGL(vx_total_kernel, dim3(1), dim3(64), 0, s, (const int*)seg, n, hdr, n_out);
     if (int rc = nero_check_launch("nero_voxel_downsample: total")) return rc;
     // the one synchronisation: the voxel count and the range flag, so that a cloud that does not fit is an error code and not a truncated result
     VxHeader host{};
     host.n_out = -1;
-    if (hipMemcpyAsync(&host, hdr, sizeof(VxHeader), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_voxel_downsample: reading the voxel count failed");
+    if (int rc = read_back(&host, hdr, sizeof(VxHeader), s, "nero_voxel_downsample: reading the voxel count failed")) return rc;
     if (host.overflow)
         return nero_fail(NERO_ERR_UNSUPPORTED, "nero_voxel_downsample: the cloud spans more than 2^21 voxels on an axis (or holds a non-finite point)");
     if (host.n_out < 0 || host.n_out > n) return nero_fail(NERO_ERR_LAUNCH, "nero_voxel_downsample: implausible voxel count");
@@ -542,8 +521,10 @@ int nero_view_rays(const double* K, const double* pose, int h, int w, float* ray
 }
 
 size_t nero_view_points_workspace_bytes(int h, int w) {
-    if (h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31) - 1) return 0;
-    return view_layout((int64_t)h * w).total;
+    if (h < 1 || w < 1 || (int64_t)h * w >= ((int64_t)1 << 31) - 1)
+        return no_workspace("nero_view_points_workspace_bytes: both sizes >= 1 and fewer than 2^31 - 1 pixels");
+    ViewLayout L;
+    return view_layout((int64_t)h * w, &L) == NERO_OK ? L.total : 0;
 }
 
 int nero_view_points(const float* t, const double* K, const double* pose, int h, int w, float unproject_offset, void* ws, float* depth,

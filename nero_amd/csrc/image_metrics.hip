@@ -24,8 +24,11 @@
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "ws_plan.h"
 
 namespace {
+
+using nero_ws::align256;
 
 constexpr int IM_WIN = 11;                          // skimage's win_size as the reference passes it
 constexpr int IM_HALO = IM_WIN - 1;
@@ -44,8 +47,6 @@ constexpr double IM_C1 = (0.01 * 255.0) * (0.01 * 255.0);
 constexpr double IM_C2 = (0.03 * 255.0) * (0.03 * 255.0);
 constexpr double IM_INV_NP2 = 1.0 / (121.0 * 121.0);            // means: sums / 121, products of two means
 constexpr double IM_INV_COV = 1.0 / (121.0 * 120.0);            // sample covariance: (121 sxy - sx sy) / (121 * 120)
-
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __host__ __device__ inline int tiles_of(int n) { return (n - IM_HALO + IM_T - 1) / IM_T; }      // n >= 11: at least one
 

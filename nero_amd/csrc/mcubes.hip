@@ -13,14 +13,20 @@
 //                             triangle's edges resolves to vbase[owner] + popcount(code[owner] below the edge's axis).
 // Tiles are MC_TILE = 2048 consecutive points (256 lanes x 8 rounds); workspace = 5 bytes per point + 32 bytes per tile + the scan's scratch.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
 #include "mcubes_tables.h"
+#include "ws_plan.h"
 
 namespace {
+
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 constexpr int MC_THREADS = 256;
 constexpr int MC_ROUNDS = 8;
@@ -68,17 +74,6 @@ __device__ __forceinline__ int mc_block_excl(int v, int* part, int* total) {
     return before + excl;
 }
 
-__device__ __forceinline__ int mc_block_sum(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int tot = 0;
-#pragma unroll
-    for (int q = 0; q < MC_THREADS / 64; ++q) tot += part[q];
-    return tot;
-}
-
 __global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float* __restrict__ u, McGrid g, float thr, uint8_t* __restrict__ code,
                                                               int64_t* __restrict__ tile_v, int64_t* __restrict__ tile_t) {
     __shared__ int part[MC_THREADS / 64];
@@ -104,9 +99,8 @@ __global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float* __res
             if (cube != 0 && cube != 255) st += nero_mcubes_tri_count[cube];
         }
     }
-    const int tv = mc_block_sum(sv, part);
-    __syncthreads();
-    const int tt = mc_block_sum(st, part);
+    const int tv = block_sum<MC_THREADS>(sv, part);
+    const int tt = block_sum<MC_THREADS>(st, part);
     if (threadIdx.x == 0) {
         tile_v[blockIdx.x] = tv;
         tile_t[blockIdx.x] = tt;
@@ -217,44 +211,35 @@ __global__ __launch_bounds__(MC_THREADS) void mc_tri_kernel(McGrid g, const uint
     }
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 bool degenerate(int nx, int ny, int nz) { return nx < 2 || ny < 2 || nz < 2; }
 
 int64_t n_tiles_of(int64_t n) { return (n + MC_TILE - 1) / MC_TILE; }
-
-size_t scan_temp_bytes(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (int)items);
-    return bytes;
-}
 
 struct McLayout {
     int64_t n, n_tiles;
     size_t hdr, code, vbase, tile_v, tile_t, base_v, base_t, temp, temp_bytes, total;
 };
 
-McLayout layout(int nx, int ny, int nz) {
-    McLayout w{};
-    w.n = (int64_t)nx * ny * nz;
-    w.hdr = 0;
-    size_t at = 256;                                                // header: int64 {V, T}
-    if (degenerate(nx, ny, nz)) {
-        w.total = at;
-        return w;
+int layout(int nx, int ny, int nz, McLayout* w) {
+    *w = McLayout{};
+    w->n = (int64_t)nx * ny * nz;
+    Carve c;
+    w->hdr = c.take(256);                                           // header: int64 {V, T}
+    if (!degenerate(nx, ny, nz)) {
+        w->n_tiles = n_tiles_of(w->n);
+        if (scan_temp<int64_t>(w->n_tiles + 1, &w->temp_bytes) != hipSuccess)
+            return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes: the scratch-size query of the tile scan failed");
+        const size_t tiles = (size_t)(w->n_tiles + 1) * sizeof(int64_t);
+        w->code = c.take((size_t)w->n);
+        w->vbase = c.take((size_t)w->n * sizeof(int));
+        w->tile_v = c.take(tiles);
+        w->tile_t = c.take(tiles);
+        w->base_v = c.take(tiles);
+        w->base_t = c.take(tiles);
+        w->temp = c.take(w->temp_bytes);
     }
-    w.n_tiles = n_tiles_of(w.n);
-    const size_t tiles = (size_t)(w.n_tiles + 1) * sizeof(int64_t);
-    w.code = at;   at += align256((size_t)w.n);
-    w.vbase = at;  at += align256((size_t)w.n * sizeof(int));
-    w.tile_v = at; at += align256(tiles);
-    w.tile_t = at; at += align256(tiles);
-    w.base_v = at; at += align256(tiles);
-    w.base_t = at; at += align256(tiles);
-    w.temp_bytes = scan_temp_bytes(w.n_tiles + 1);
-    w.temp = at;   at += align256(w.temp_bytes);
-    w.total = at;
-    return w;
+    w->total = c.at;
+    return NERO_OK;
 }
 
 McGrid grid_of(int nx, int ny, int nz) { return McGrid{nx, ny, nz, (int64_t)ny * nz, (int64_t)nx * ny * nz}; }
@@ -276,8 +261,9 @@ int check_dims(const char* fn, int nx, int ny, int nz) {
 }  // namespace
 
 size_t nero_mcubes_workspace_bytes(int nx, int ny, int nz) {
-    if (nx < 1 || ny < 1 || nz < 1 || (uint64_t)nx * (uint64_t)ny * (uint64_t)nz > MC_MAX_POINTS) return 0;
-    return layout(nx, ny, nz).total;
+    if (check_dims("nero_mcubes_workspace_bytes", nx, ny, nz)) return 0;
+    McLayout L;
+    return layout(nx, ny, nz, &L) == NERO_OK ? L.total : 0;
 }
 
 int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, void* ws, int64_t* totals, void* stream) {
@@ -290,7 +276,8 @@ int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, v
             return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes_count: hipMemsetAsync failed");
         return NERO_OK;
     }
-    const McLayout L = layout(nx, ny, nz);
+    McLayout L;
+    if (int rc = layout(nx, ny, nz, &L)) return rc;
     const McGrid g = grid_of(nx, ny, nz);
     int64_t* tile_v = (int64_t*)(w + L.tile_v);
     int64_t* tile_t = (int64_t*)(w + L.tile_t);
@@ -299,12 +286,10 @@ int nero_mcubes_count(const float* u, int nx, int ny, int nz, float threshold, v
         return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes_count: hipMemsetAsync failed");
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)L.n_tiles), dim3(MC_THREADS), 0, s, u, g, threshold, w + L.code, tile_v, tile_t);
     if (int rc = nero_check_launch("nero_mcubes_count: count pass")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int64_t*)tile_v, (int64_t*)(w + L.base_v), (int)(L.n_tiles + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes_count: vertex scan failed");
-    tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int64_t*)tile_t, (int64_t*)(w + L.base_t), (int)(L.n_tiles + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes_count: triangle scan failed");
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int64_t*)tile_v, (int64_t*)(w + L.base_v), L.n_tiles + 1, s, "nero_mcubes_count: vertex scan failed"))
+        return rc;
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int64_t*)tile_t, (int64_t*)(w + L.base_t), L.n_tiles + 1, s, "nero_mcubes_count: triangle scan failed"))
+        return rc;
     hipLaunchKernelGGL(mc_totals_kernel, dim3(1), dim3(64), 0, s, (const int64_t*)(w + L.base_v), (const int64_t*)(w + L.base_t), L.n_tiles,
                        (int64_t*)(w + L.hdr), totals);
     return nero_check_launch("nero_mcubes_count");
@@ -317,13 +302,13 @@ int nero_mcubes_emit(const float* u, int nx, int ny, int nz, float threshold, vo
     if (degenerate(nx, ny, nz)) return NERO_OK;                    // the empty mesh: nothing to write
     hipStream_t s = (hipStream_t)stream;
     uint8_t* w = (uint8_t*)ws;
-    const McLayout L = layout(nx, ny, nz);
+    McLayout L;
+    if (int rc = layout(nx, ny, nz, &L)) return rc;
     const McGrid g = grid_of(nx, ny, nz);
     // the one synchronisation of this file: the 16-byte totals nero_mcubes_count left in the workspace, so that a mesh that does not fit the
     // caller's buffers (or whose ids would not fit int32) is an error code and not a write out of range
     int64_t tot[2] = {-1, -1};
-    if (hipMemcpyAsync(tot, w + L.hdr, sizeof(tot), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mcubes_emit: reading the totals of nero_mcubes_count failed");
+    if (int rc = read_back(tot, w + L.hdr, sizeof(tot), s, "nero_mcubes_emit: reading the totals of nero_mcubes_count failed")) return rc;
     const int64_t V = tot[0], T = tot[1];
     if (V < 0 || T < 0 || V > 3 * L.n || T > 5 * L.n)
         return nero_fail(NERO_ERR_ARG, "nero_mcubes_emit: the workspace holds no totals of nero_mcubes_count for this grid");

@@ -4,9 +4,9 @@
 // 9.7.1; tests/mesh_atlas_ref.py restates it in numpy.  Steps, each on the mesh where the clean-up / simplification left it:
 //   adjacency  the 3T edges (min << 32 | max) of the valid faces, stable radix sort, and a look at the two entries behind every group head:
 //              a key held exactly twice joins two faces, once is a boundary edge, three times or more a non-manifold edge.
-//   label      class of every face from its float64 normal; a concurrent union-find over FACES on the pattern of mesh_clean.hip (agent-scope
-//              compare-and-swap hook, larger root under smaller, so a chart's root is its smallest face whatever order the atomics land in;
-//              flatten behind the kernel boundary); charts numbered by a prefix sum over the root flags.
+//   label      class of every face from its float64 normal; the concurrent union-find of device_prims.h over FACES (a chart's root is its
+//              smallest face whatever order the atomics land in; flatten behind the kernel boundary); charts numbered by a prefix sum over
+//              the root flags.
 //   stats      class, face count and the exact fp32 box of the two projected coordinates per chart: integer atomics on order-preserving
 //              bit images, one per wave and chart.
 //   corners    one UV vertex per (chart, mesh vertex) pair: stable sort of the 3T corner keys, head flags, a scan; two-phase, the totals
@@ -14,37 +14,27 @@
 //   uv         U, V of every UV vertex from the packed chart origins (host) and the scale: float64, no fused multiply-add.
 // No floating-point atomics and no atomic that decides a position or a label: every output is bit-identical run to run.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
+#include "ws_plan.h"
 
 namespace {
+
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 constexpr int AT_THREADS = 256;
 constexpr int64_t AT_MAX_ITEMS = ((int64_t)1 << 31) - 1;           // V, 3T < 2^31: int32 ids, int item counts of hipCUB
 constexpr unsigned long long AT_NO_KEY = ~0ull;                    // sorts behind every real key (a real key's high word is < 2^31)
 constexpr int AT_MAX_SIZE = 16384;
 
-#define AT_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ bool at_in_range(int a, int n) { return (unsigned)a < (unsigned)n; }
-
 __device__ __forceinline__ bool at_valid_face(int a, int b, int c, int V) {
-    return at_in_range(a, V) && at_in_range(b, V) && at_in_range(c, V) && a != b && b != c && c != a;
-}
-
-__device__ __forceinline__ int at_block_sum(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int tot = 0;
-#pragma unroll
-    for (int q = 0; q < AT_THREADS / 64; ++q) tot += part[q];
-    __syncthreads();
-    return tot;
+    return in_range(a, V) && in_range(b, V) && in_range(c, V) && a != b && b != c && c != a;
 }
 
 // ---- adjacency --------------------------------------------------------------------------------------------------------------------------
@@ -92,8 +82,8 @@ __global__ __launch_bounds__(AT_THREADS) void at_edge_group_kernel(const unsigne
             }
         }
     }
-    const int nb = at_block_sum(boundary, part);
-    const int nm = at_block_sum(nonmanifold, part);
+    const int nb = block_sum<AT_THREADS>(boundary, part);
+    const int nm = block_sum<AT_THREADS>(nonmanifold, part);
     if (threadIdx.x == 0) {
         if (nb) atomicAdd(counts, (unsigned long long)nb);
         if (nm) atomicAdd(counts + 1, (unsigned long long)nm);
@@ -132,39 +122,12 @@ __global__ __launch_bounds__(AT_THREADS) void at_class_kernel(const float* __res
         parent[t] = (int)t;
         chartless = cls == 6;
     }
-    const int n = at_block_sum(chartless, part);
+    const int n = block_sum<AT_THREADS>(chartless, part);
     if (threadIdx.x == 0 && n) atomicAdd(info + 1, (unsigned long long)n);
 }
 
-// the union-find of mesh_clean.hip, over faces: parent[t] <= t always holds, so the forest cannot hold a cycle and a tree's root is its
-// smallest face.  Plain loads of parent[] may be stale: a stale value is an OLDER ancestor pointer, which costs steps and decides nothing.
-__device__ __forceinline__ int at_find(int* parent, int v) {
-    int p = parent[v];
-    while (p != v) {
-        const int g = parent[p];
-        if (g != p) __hip_atomic_fetch_min(parent + v, g, AT_RLX_AGENT);
-        v = p;
-        p = g;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void at_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = at_find(parent, a);
-        b = at_find(parent, b);
-        if (a == b) return;
-        int hi = a > b ? a : b;
-        const int lo = a > b ? b : a;
-        int seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, AT_RLX_AGENT)) return;
-        a = seen;                                                    // hi had been hooked already: go on from its parent
-        b = lo;
-    }
-}
-
 // face_class is complete here (the launch before).  Every pair is joined from its smaller face; a neighbour entry that is not a face of
-// this mesh (nbr not written by nero_mesh_face_adjacency) is never followed.
+// this mesh (nbr not written by nero_mesh_face_adjacency) is never followed.  uf_unite: the union-find of device_prims.h, over faces.
 __global__ __launch_bounds__(AT_THREADS) void at_hook_kernel(const int* __restrict__ nbr, const int* __restrict__ face_class, int64_t T,
                                                              int* parent) {
     const int64_t t = (int64_t)blockIdx.x * AT_THREADS + threadIdx.x;
@@ -174,7 +137,7 @@ __global__ __launch_bounds__(AT_THREADS) void at_hook_kernel(const int* __restri
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
         const int n = nbr[3 * t + e];
-        if (n > (int)t && n < T && face_class[n] == cls) at_unite(parent, (int)t, n);
+        if (n > (int)t && n < T && face_class[n] == cls) uf_unite(parent, (int)t, n);
     }
 }
 
@@ -205,30 +168,6 @@ __global__ __launch_bounds__(AT_THREADS) void at_number_kernel(int* chart, const
 }
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------------------
-// order-preserving image of a float in the unsigned integers (as cc_f2o of mesh_clean.hip: -0 orders below +0)
-__device__ __forceinline__ unsigned at_f2o(float f) {
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float at_o2f(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
-__device__ __forceinline__ unsigned at_wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned at_wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(AT_THREADS) void at_stats_init_kernel(int* __restrict__ chart_class, int* __restrict__ n_faces, unsigned* __restrict__ box,
                                                                    int K) {
     const int64_t c = (int64_t)blockIdx.x * AT_THREADS + threadIdx.x;
@@ -250,14 +189,14 @@ __global__ __launch_bounds__(AT_THREADS) void at_stats_kernel(const float* __res
     if (t < T) {
         const int cc = chart[t], cls = face_class[t];
         const int v[3] = {tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]};
-        if (at_in_range(cc, K) && at_in_range(cls, 6) && at_valid_face(v[0], v[1], v[2], V)) {
+        if (in_range(cc, K) && in_range(cls, 6) && at_valid_face(v[0], v[1], v[2], V)) {
             c = cc;
             const int k = cls >> 1, ax[2] = {(k + 1) % 3, (k + 2) % 3};
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
                 for (int d = 0; d < 2; ++d) {
-                    const unsigned o = at_f2o(verts[3 * (int64_t)v[j] + ax[d]]);
+                    const unsigned o = f2o(verts[3 * (int64_t)v[j] + ax[d]]);
                     lo[d] = o < lo[d] ? o : lo[d];
                     hi[d] = o > hi[d] ? o : hi[d];
                 }
@@ -266,17 +205,16 @@ __global__ __launch_bounds__(AT_THREADS) void at_stats_kernel(const float* __res
     }
     const int lane = threadIdx.x & 63;
     for (unsigned long long todo = __ballot(c >= 0); todo;) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int cl = __shfl(c, leader, 64);
-        const unsigned long long m = __ballot(c == cl) & todo;
+        int cl, leader;
+        const unsigned long long m = next_group(c, todo, &cl, &leader);
         todo &= ~m;
         unsigned l[2] = {lo[0], lo[1]}, h[2] = {hi[0], hi[1]};
         if (m & (m - 1)) {                                           // (wave-uniform) more than one lane: their extrema first
             const bool mine = (m >> lane) & 1;
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
-                l[d] = at_wave_min(mine ? lo[d] : 0xFFFFFFFFu);
-                h[d] = at_wave_max(mine ? hi[d] : 0u);
+                l[d] = wave_min(mine ? lo[d] : 0xFFFFFFFFu);
+                h[d] = wave_max(mine ? hi[d] : 0u);
             }
         }
         if (lane == leader) {
@@ -292,7 +230,7 @@ __global__ __launch_bounds__(AT_THREADS) void at_stats_kernel(const float* __res
 
 __global__ __launch_bounds__(AT_THREADS) void at_box_decode_kernel(unsigned* box, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * AT_THREADS + threadIdx.x;
-    if (i < n) ((float*)box)[i] = at_o2f(box[i]);
+    if (i < n) ((float*)box)[i] = o2f(box[i]);
 }
 
 // ---- UV vertices ------------------------------------------------------------------------------------------------------------------------
@@ -305,7 +243,7 @@ __global__ __launch_bounds__(AT_THREADS) void at_corner_key_kernel(const int* __
     const int c = chart[t];
     const int a = tris[3 * t], b = tris[3 * t + 1], d = tris[3 * t + 2];
     unsigned long long k = AT_NO_KEY;
-    if (at_in_range(c, K) && at_valid_face(a, b, d, V)) k = ((unsigned long long)(unsigned)c << 32) | (unsigned)tris[i];
+    if (in_range(c, K) && at_valid_face(a, b, d, V)) k = ((unsigned long long)(unsigned)c << 32) | (unsigned)tris[i];
     key[i] = k;
     val[i] = (unsigned)i;
 }
@@ -381,9 +319,9 @@ __global__ __launch_bounds__(AT_THREADS) void at_uv_kernel(const float* __restri
     if (i >= n_vt) return;
     const int v = vt_vertex[i], c = vt_chart[i];
     float u = 0.0f, w = 0.0f;                                        // the sentinel, and anything that is not a (chart, vertex) of this mesh
-    if (at_in_range(v, V) && at_in_range(c, K)) {
+    if (in_range(v, V) && in_range(c, K)) {
         const int cls = chart_class[c];
-        if (at_in_range(cls, 6)) {
+        if (in_range(cls, 6)) {
             const int k = cls >> 1;
             const double xp = verts[3 * (int64_t)v + (k + 1) % 3], xq = verts[3 * (int64_t)v + (k + 2) % 3];
             const double dp = (cls & 1) ? (double)box[4 * (int64_t)c + 2] - xp : xp - (double)box[4 * (int64_t)c];
@@ -397,82 +335,57 @@ __global__ __launch_bounds__(AT_THREADS) void at_uv_kernel(const float* __restri
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + AT_THREADS - 1) / AT_THREADS); }
-
 bool sizes_ok(int64_t V, int64_t T) { return V >= 0 && T >= 0 && V <= AT_MAX_ITEMS && T <= AT_MAX_ITEMS / 3; }
-
-size_t scan_temp_i32(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int*)nullptr, (int*)nullptr, (int)items);
-    return bytes;
-}
-
-size_t sort_temp_u64(int64_t items) {
-    size_t bytes = 0;
-    if (items > 0)
-        (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 (const unsigned*)nullptr, (unsigned*)nullptr, (int)items, 0, 64);
-    return bytes;
-}
 
 // adjacency and corners: two key and two value arrays of 3T entries, head flags and their scan (corners), the sort's / scan's scratch
 struct SortLayout {
     size_t key_a, key_b, val_a, val_b, head, pos, temp, temp_bytes, total;
 };
 
-SortLayout sort_layout(int64_t T, bool corners) {
-    SortLayout L{};
+int sort_layout(int64_t T, bool corners, SortLayout* L) {
     const int64_t n3 = 3 * T;
-    size_t at = 256;                                                // AtCornerHeader
-    const size_t k8 = align256((size_t)n3 * sizeof(unsigned long long)), k4 = align256((size_t)n3 * sizeof(unsigned));
-    L.key_a = at; at += k8;
-    L.key_b = at; at += k8;
-    L.val_a = at; at += k4;
-    L.val_b = at; at += k4;
-    size_t tb = sort_temp_u64(n3);
+    size_t tb = 0, sb = 0;
+    if (sort_pairs_temp<unsigned long long>(n3, 64, &tb) != hipSuccess || (corners && scan_temp<int>(n3 + 1, &sb) != hipSuccess))
+        return nero_fail(NERO_ERR_LAUNCH, corners ? "nero_mesh_chart_corners: the scratch-size query of the corner sort or the head scan failed"
+                                                  : "nero_mesh_face_adjacency: the scratch-size query of the edge sort failed");
+    *L = SortLayout{};
+    Carve c{256};                                                   // AtCornerHeader
+    L->key_a = c.take((size_t)n3 * sizeof(unsigned long long));
+    L->key_b = c.take((size_t)n3 * sizeof(unsigned long long));
+    L->val_a = c.take((size_t)n3 * sizeof(unsigned));
+    L->val_b = c.take((size_t)n3 * sizeof(unsigned));
     if (corners) {
-        const size_t h4 = align256((size_t)(n3 + 1) * sizeof(int));
-        L.head = at; at += h4;
-        L.pos = at;  at += h4;
-        const size_t sb = scan_temp_i32(n3 + 1);
-        tb = sb > tb ? sb : tb;
+        L->head = c.take((size_t)(n3 + 1) * sizeof(int));
+        L->pos = c.take((size_t)(n3 + 1) * sizeof(int));
     }
-    L.temp_bytes = tb;
-    L.temp = at; at += align256(tb);
-    L.total = at;
-    return L;
+    L->temp_bytes = sb > tb ? sb : tb;
+    L->temp = c.take(L->temp_bytes);
+    L->total = c.at;
+    return NERO_OK;
 }
 
 struct LabelLayout {
     size_t flag, rank, temp, temp_bytes, total;
 };
 
-LabelLayout label_layout(int64_t T) {
-    LabelLayout L{};
-    size_t at = 0;
-    const size_t ti = align256((size_t)(T + 1) * sizeof(int));
-    L.flag = at; at += ti;
-    L.rank = at; at += ti;
-    L.temp_bytes = scan_temp_i32(T + 1);
-    L.temp = at; at += align256(L.temp_bytes);
-    L.total = at;
-    return L;
-}
-
-int bit_length(int64_t x) {
-    int n = 0;
-    while (x > 0) {
-        ++n;
-        x >>= 1;
-    }
-    return n;
+int label_layout(int64_t T, LabelLayout* L) {
+    if (scan_temp<int>(T + 1, &L->temp_bytes) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_label: the scratch-size query of the rank scan failed");
+    Carve c;
+    L->flag = c.take((size_t)(T + 1) * sizeof(int));
+    L->rank = c.take((size_t)(T + 1) * sizeof(int));
+    L->temp = c.take(L->temp_bytes);
+    L->total = c.at;
+    return NERO_OK;
 }
 
 }  // namespace
 
-size_t nero_mesh_face_adjacency_workspace_bytes(int64_t T) { return sizes_ok(0, T) ? sort_layout(T, false).total : 0; }
+size_t nero_mesh_face_adjacency_workspace_bytes(int64_t T) {
+    SortLayout L;
+    if (!sizes_ok(0, T)) return no_workspace("nero_mesh_face_adjacency_workspace_bytes: 3 T must be in [0, 2^31)");
+    return sort_layout(T, false, &L) == NERO_OK ? L.total : 0;
+}
 
 int nero_mesh_face_adjacency(const int* tris, int64_t T, int64_t V, void* ws, int* nbr, int64_t* counts, void* stream) {
     if (!sizes_ok(V, T)) return nero_fail(NERO_ERR_UNSUPPORTED, "nero_mesh_face_adjacency: V and 3 T must be in [0, 2^31)");
@@ -483,7 +396,8 @@ int nero_mesh_face_adjacency(const int* tris, int64_t T, int64_t V, void* ws, in
     if (T == 0) return NERO_OK;
     const int64_t n3 = 3 * T;
     uint8_t* w = (uint8_t*)ws;
-    const SortLayout L = sort_layout(T, false);
+    SortLayout L;
+    if (int rc = sort_layout(T, false, &L)) return rc;
     unsigned long long* key_a = (unsigned long long*)(w + L.key_a);
     unsigned long long* key_b = (unsigned long long*)(w + L.key_b);
     unsigned* val_a = (unsigned*)(w + L.val_a);
@@ -492,16 +406,19 @@ int nero_mesh_face_adjacency(const int* tris, int64_t T, int64_t V, void* ws, in
         return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_face_adjacency: hipMemsetAsync failed");
     hipLaunchKernelGGL(at_edge_key_kernel, dim3(blocks_of(n3)), dim3(AT_THREADS), 0, s, tris, n3, (int)V, key_a, val_a);
     if (int rc = nero_check_launch("nero_mesh_face_adjacency: edge keys")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)(w + L.temp), tb, (const unsigned long long*)key_a, key_b, (const unsigned*)val_a, val_b, (int)n3,
-                                           0, 32 + bit_length(V), s) != hipSuccess)       // (AT_NO_KEY stays the largest under these bits)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_face_adjacency: edge sort failed");
+    if (int rc = sort_pairs<unsigned long long>(w + L.temp, L.temp_bytes, key_a, key_b, val_a, val_b, n3, 32 + bit_length(V), s,
+                                                "nero_mesh_face_adjacency: edge sort failed"))       // (AT_NO_KEY stays the largest under these bits)
+        return rc;
     hipLaunchKernelGGL(at_edge_group_kernel, dim3(blocks_of(n3)), dim3(AT_THREADS), 0, s, (const unsigned long long*)key_b, (const unsigned*)val_b, n3,
                        nbr, (unsigned long long*)counts);
     return nero_check_launch("nero_mesh_face_adjacency: edge groups");
 }
 
-size_t nero_mesh_chart_label_workspace_bytes(int64_t T) { return sizes_ok(0, T) ? label_layout(T).total : 0; }
+size_t nero_mesh_chart_label_workspace_bytes(int64_t T) {
+    LabelLayout L;
+    if (!sizes_ok(0, T)) return no_workspace("nero_mesh_chart_label_workspace_bytes: 3 T must be in [0, 2^31)");
+    return label_layout(T, &L) == NERO_OK ? L.total : 0;
+}
 
 int nero_mesh_chart_label(const float* verts, const int* tris, int64_t T, int64_t V, const int* nbr, void* ws, int* face_class, int* chart,
                           int64_t* info, void* stream) {
@@ -513,7 +430,8 @@ int nero_mesh_chart_label(const float* verts, const int* tris, int64_t T, int64_
         return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_label: hipMemsetAsync failed");
     if (T == 0) return NERO_OK;
     uint8_t* w = (uint8_t*)ws;
-    const LabelLayout L = label_layout(T);
+    LabelLayout L;
+    if (int rc = label_layout(T, &L)) return rc;
     int* flag = (int*)(w + L.flag);
     int* rank = (int*)(w + L.rank);
     unsigned long long* inf = (unsigned long long*)info;
@@ -523,9 +441,7 @@ int nero_mesh_chart_label(const float* verts, const int* tris, int64_t T, int64_
     if (int rc = nero_check_launch("nero_mesh_chart_label: hook pass")) return rc;
     hipLaunchKernelGGL(at_flatten_kernel, dim3(blocks_of(T + 1)), dim3(AT_THREADS), 0, s, chart, (const int*)face_class, T, flag);
     if (int rc = nero_check_launch("nero_mesh_chart_label: flatten pass")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int*)flag, rank, (int)(T + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_label: rank scan failed");
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)flag, rank, T + 1, s, "nero_mesh_chart_label: rank scan failed")) return rc;
     hipLaunchKernelGGL(at_number_kernel, dim3(blocks_of(T)), dim3(AT_THREADS), 0, s, chart, (const int*)face_class, (const int*)rank, T, inf);
     return nero_check_launch("nero_mesh_chart_label: numbering");
 }
@@ -547,7 +463,11 @@ int nero_mesh_chart_stats(const float* verts, const int* tris, int64_t T, int64_
     return nero_check_launch("nero_mesh_chart_stats: box decode");
 }
 
-size_t nero_mesh_chart_corners_workspace_bytes(int64_t T) { return sizes_ok(0, T) ? sort_layout(T, true).total : 0; }
+size_t nero_mesh_chart_corners_workspace_bytes(int64_t T) {
+    SortLayout L;
+    if (!sizes_ok(0, T)) return no_workspace("nero_mesh_chart_corners_workspace_bytes: 3 T must be in [0, 2^31)");
+    return sort_layout(T, true, &L) == NERO_OK ? L.total : 0;
+}
 
 int nero_mesh_chart_corners_count(const int* tris, int64_t T, int64_t V, const int* chart, int64_t K, void* ws, int64_t* totals, void* stream) {
     if (!sizes_ok(V, T)) return nero_fail(NERO_ERR_UNSUPPORTED, "nero_mesh_chart_corners_count: V and 3 T must be in [0, 2^31)");
@@ -561,7 +481,8 @@ int nero_mesh_chart_corners_count(const int* tris, int64_t T, int64_t V, const i
             return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_corners_count: hipMemsetAsync failed");
         return NERO_OK;
     }
-    const SortLayout L = sort_layout(T, true);
+    SortLayout L;
+    if (int rc = sort_layout(T, true, &L)) return rc;
     unsigned long long* key_a = (unsigned long long*)(w + L.key_a);
     unsigned long long* key_b = (unsigned long long*)(w + L.key_b);
     unsigned* val_a = (unsigned*)(w + L.val_a);
@@ -570,15 +491,12 @@ int nero_mesh_chart_corners_count(const int* tris, int64_t T, int64_t V, const i
     int* pos = (int*)(w + L.pos);
     hipLaunchKernelGGL(at_corner_key_kernel, dim3(blocks_of(n3)), dim3(AT_THREADS), 0, s, tris, n3, (int)V, chart, (int)K, key_a, val_a);
     if (int rc = nero_check_launch("nero_mesh_chart_corners_count: corner keys")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)(w + L.temp), tb, (const unsigned long long*)key_a, key_b, (const unsigned*)val_a, val_b, (int)n3,
-                                           0, 32 + bit_length(K), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_corners_count: corner sort failed");
+    if (int rc = sort_pairs<unsigned long long>(w + L.temp, L.temp_bytes, key_a, key_b, val_a, val_b, n3, 32 + bit_length(K), s,
+                                                "nero_mesh_chart_corners_count: corner sort failed"))
+        return rc;
     hipLaunchKernelGGL(at_corner_head_kernel, dim3(blocks_of(n3 + 1)), dim3(AT_THREADS), 0, s, (const unsigned long long*)key_b, n3, head);
     if (int rc = nero_check_launch("nero_mesh_chart_corners_count: head flags")) return rc;
-    tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int*)head, pos, (int)(n3 + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_corners_count: head scan failed");
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)head, pos, n3 + 1, s, "nero_mesh_chart_corners_count: head scan failed")) return rc;
     hipLaunchKernelGGL(at_corner_totals_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)key_b, (const int*)pos, n3, (AtCornerHeader*)w,
                        totals);
     return nero_check_launch("nero_mesh_chart_corners_count: totals");
@@ -593,8 +511,7 @@ int nero_mesh_chart_corners_emit(int64_t T, void* ws, int* ft, int* vt_vertex, i
     // the one synchronisation: the totals nero_mesh_chart_corners_count left in the workspace, so that outputs that are too small are an
     // error code and not a write out of range
     AtCornerHeader h{-1, -1, -1, -1};
-    if (hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_chart_corners_emit: reading the totals of nero_mesh_chart_corners_count failed");
+    if (int rc = read_back(&h, w, sizeof(h), s, "nero_mesh_chart_corners_emit: reading the totals of nero_mesh_chart_corners_count failed")) return rc;
     if (h.n3 != n3 || h.n_pairs < 0 || h.n_pairs > n3 || h.n_charted < 0 || h.n_charted > n3 || h.n_vt != h.n_pairs + (h.n_charted < n3 ? 1 : 0))
         return nero_fail(NERO_ERR_ARG, "nero_mesh_chart_corners_emit: the workspace holds no totals of nero_mesh_chart_corners_count for this mesh");
     if (h.n_vt > vt_cap) {
@@ -604,7 +521,8 @@ int nero_mesh_chart_corners_emit(int64_t T, void* ws, int* ft, int* vt_vertex, i
     }
     if (h.n_vt > 0 && (!vt_vertex || !vt_chart)) return nero_fail(NERO_ERR_ARG, "nero_mesh_chart_corners_emit: null output pointer");
     if (T == 0) return NERO_OK;
-    const SortLayout L = sort_layout(T, true);
+    SortLayout L;
+    if (int rc = sort_layout(T, true, &L)) return rc;
     hipLaunchKernelGGL(at_corner_emit_kernel, dim3(blocks_of(n3)), dim3(AT_THREADS), 0, s, (const unsigned long long*)(w + L.key_b),
                        (const unsigned*)(w + L.val_b), (const int*)(w + L.head), (const int*)(w + L.pos), n3, h.n_pairs, h.n_charted, ft, vt_vertex,
                        vt_chart);

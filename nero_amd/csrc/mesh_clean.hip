@@ -1,14 +1,9 @@
 // mesh_clean.hip -- connected components of the extracted Stage-I mesh and the removal of the unwanted ones (include/nero_hip.h,
 // nero_mesh_*).  The marching-cubes surface of a learned SDF holds floaters, hidden inner shells and scraps of the support surface; the
 // reference leaves them to a mesh editor.  Three steps, all on the mesh where nero_mcubes_emit left it:
-//   label    concurrent union-find over the triangle edges.  parent[v] = v; every triangle hooks the roots of its vertices, the larger
-//            root under the smaller, so parent[v] <= v always holds, a tree's root is its smallest vertex, and the forest cannot hold a
-//            cycle.  The XCDs' L2 caches are not coherent inside a launch, so every change of parent[] is an agent-scope atomic: the hook is a
-//            compare-and-swap parent[hi]: hi -> lo (it succeeds only while hi is still a root; when it fails it returned hi's parent, and
-//            the search goes on from there), the path compression an atomic minimum with an ancestor.  Plain loads of parent[] may be
-//            stale: a stale value is an OLDER ancestor pointer (entries only ever decrease, and an ancestor stays an ancestor), so it
-//            costs steps and decides nothing.  A second launch, behind the kernel boundary, points every vertex at its root and counts
-//            the roots.  The labels are the smallest vertex of each component whatever order the atomics landed in.
+//   label    concurrent union-find over the triangle edges (device_prims.h: why it is correct under stale loads and incoherent L2
+//            caches): every triangle unites its vertices.  A second launch, behind the kernel boundary, points every vertex at its root and
+//            counts the roots.  The labels are the smallest vertex of each component whatever order the atomics landed in.
 //   stats    components numbered by a prefix sum over the root flags (ascending smallest vertex); vertex / face counts and boxes by integer
 //            atomics (sums and extrema of integers do not depend on arrival order), one per wave and component; areas by a stable radix
 //            sort of the faces by component and a fixed two-level float64 sum per component (no float atomics).
@@ -16,47 +11,23 @@
 //            survivors keep their relative order.
 // Work and traffic are linear in V + T (the union-find's inverse-Ackermann factor aside), whatever the diameter of the mesh graph.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
+#include "ws_plan.h"
 
 namespace {
+
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 constexpr int CC_THREADS = 256;
 constexpr int CC_PIECE = 2048;                                      // faces a wave sums into one partial area
 constexpr int64_t CC_MAX_ITEMS = ((int64_t)1 << 31) - 1;           // V, T < 2^31: int32 ids, int item counts of hipCUB
-
-#define CC_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ bool cc_in_range(int a, int V) { return (unsigned)a < (unsigned)V; }
-
-// some ancestor r of v with (a possibly stale) parent[r] == r; every vertex passed on the way is pointed at its grandparent
-__device__ __forceinline__ int cc_find(int* parent, int v) {
-    int p = parent[v];
-    while (p != v) {
-        const int g = parent[p];
-        if (g != p) __hip_atomic_fetch_min(parent + v, g, CC_RLX_AGENT);
-        v = p;
-        p = g;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;                                          // one vertex reached from both: one tree
-        int hi = a > b ? a : b;
-        const int lo = a > b ? b : a;
-        int seen = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, CC_RLX_AGENT)) return;
-        a = seen;                                                    // hi had been hooked already: go on from its parent
-        b = lo;
-    }
-}
 
 __global__ __launch_bounds__(CC_THREADS) void cc_init_kernel(int* __restrict__ parent, int V) {
     const int64_t v = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
@@ -68,23 +39,12 @@ __global__ __launch_bounds__(CC_THREADS) void cc_hook_kernel(const int* __restri
     const int64_t t = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     if (t >= T) return;
     const int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-    if (!(cc_in_range(a, V) && cc_in_range(b, V) && cc_in_range(c, V))) {
+    if (!(in_range(a, V) && in_range(b, V) && in_range(c, V))) {
         atomicAdd(info + 1, 1ull);                                   // reported by the call; the triangle is never dereferenced
         return;
     }
-    if (a != b) cc_unite(parent, a, b);
-    if (b != c) cc_unite(parent, b, c);
-}
-
-__device__ __forceinline__ int cc_block_sum(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int tot = 0;
-#pragma unroll
-    for (int q = 0; q < CC_THREADS / 64; ++q) tot += part[q];
-    return tot;
+    if (a != b) uf_unite(parent, a, b);
+    if (b != c) uf_unite(parent, b, c);
 }
 
 // after the kernel boundary: every store of the hook pass is visible.  Vertices that are rewritten while another lane walks through them
@@ -102,44 +62,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int* parent, int
         is_root = r == (int)v;
         if (!is_root) parent[v] = r;
     }
-    const int n = cc_block_sum(is_root, part);
+    const int n = block_sum<CC_THREADS>(is_root, part);
     if (threadIdx.x == 0 && n) atomicAdd(info, (unsigned long long)n);
 }
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------------------
-// order-preserving image of a float in the unsigned integers
-__device__ __forceinline__ unsigned cc_f2o(float f) {
-    const unsigned b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float cc_o2f(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
-__device__ __forceinline__ unsigned cc_wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned cc_wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-// One atomic per wave and component, not per lane: a surface with floaters is one component that holds nearly every vertex, and per-lane
-// atomics would queue on its few words.  Of the lanes in `todo` (wave-uniform), those that hold the component of the first one; every lane
-// of the wave must call this.
-__device__ __forceinline__ unsigned long long cc_next_group(int c, unsigned long long todo, int* cl, int* leader) {
-    *leader = __ffsll((long long)todo) - 1;
-    *cl = __shfl(c, *leader, 64);
-    return __ballot(c == *cl) & todo;
-}
-
 __global__ __launch_bounds__(CC_THREADS) void cc_rootflag_kernel(const int* __restrict__ label, int V, int* __restrict__ flag) {
     const int64_t v = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     if (v < V) flag[v] = label[v] == (int)v;
@@ -155,20 +82,20 @@ __global__ __launch_bounds__(CC_THREADS) void cc_vertex_kernel(const float* __re
     unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
     if (v < V) {
         const int r = label[v];
-        if (cc_in_range(r, V)) {
+        if (in_range(r, V)) {
             c = rank[r];
-            if (!cc_in_range(c, K)) c = -1;
+            if (!in_range(c, K)) c = -1;
         }
         comp[v] = c;
         if (c >= 0) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) lo[a] = hi[a] = cc_f2o(verts[3 * v + a]);
+            for (int a = 0; a < 3; ++a) lo[a] = hi[a] = f2o(verts[3 * v + a]);
         }
     }
     const int lane = threadIdx.x & 63;
     for (unsigned long long todo = __ballot(c >= 0); todo;) {
         int cl, leader;
-        const unsigned long long m = cc_next_group(c, todo, &cl, &leader);
+        const unsigned long long m = next_group(c, todo, &cl, &leader);
         todo &= ~m;
         unsigned l[3], h[3];
 #pragma unroll
@@ -180,8 +107,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_vertex_kernel(const float* __re
             const bool mine = (m >> lane) & 1;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                l[a] = cc_wave_min(mine ? lo[a] : 0xFFFFFFFFu);
-                h[a] = cc_wave_max(mine ? hi[a] : 0u);
+                l[a] = wave_min(mine ? lo[a] : 0xFFFFFFFFu);
+                h[a] = wave_max(mine ? hi[a] : 0u);
             }
         }
         if (lane == leader) {
@@ -203,13 +130,13 @@ __global__ __launch_bounds__(CC_THREADS) void cc_face_kernel(const int* __restri
     int c = -1;
     if (t < T) {
         const int a = tris[3 * t], b = tris[3 * t + 1], d = tris[3 * t + 2];
-        if (cc_in_range(a, V) && cc_in_range(b, V) && cc_in_range(d, V)) c = comp[a];
+        if (in_range(a, V) && in_range(b, V) && in_range(d, V)) c = comp[a];
         key[t] = c >= 0 ? (unsigned)c : (unsigned)K;
         val[t] = (unsigned)t;
     }
     for (unsigned long long todo = __ballot(c >= 0); todo;) {
         int cl, leader;
-        const unsigned long long m = cc_next_group(c, todo, &cl, &leader);
+        const unsigned long long m = next_group(c, todo, &cl, &leader);
         todo &= ~m;
         if ((int)(threadIdx.x & 63) == leader) atomicAdd(n_faces + cl, __popcll(m));
     }
@@ -221,12 +148,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_face_kernel(const int* __restri
 struct CcPieces {
     __host__ __device__ int operator()(int n) const { return (n + CC_PIECE - 1) / CC_PIECE; }
 };
-
-__device__ __forceinline__ double cc_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ double cc_face_area(const float* __restrict__ verts, const int* __restrict__ tris, int64_t t) {
     const float* pa = verts + 3 * (int64_t)tris[3 * t];
@@ -254,7 +175,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_area_piece_kernel(const float* 
     const int64_t end = begin + CC_PIECE < offsets[lo + 1] ? begin + CC_PIECE : offsets[lo + 1];
     double s = 0.0;
     for (int64_t i = begin + (threadIdx.x & 63); i < end; i += 64) s += cc_face_area(verts, tris, face[i]);
-    s = cc_wave_sum(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) partial[p] = s;
 }
 
@@ -265,15 +186,15 @@ __global__ __launch_bounds__(CC_THREADS) void cc_area_sum_kernel(const double* _
     if (c >= K) return;
     double s = 0.0;
     for (int64_t i = pbase[c] + (threadIdx.x & 63); i < pbase[c + 1]; i += 64) s += partial[i];
-    s = cc_wave_sum(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) area[c] = s;
 }
 
 __global__ __launch_bounds__(CC_THREADS) void cc_box_decode_kernel(unsigned* bmin, unsigned* bmax, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x;
     if (i >= n) return;
-    ((float*)bmin)[i] = cc_o2f(bmin[i]);
-    ((float*)bmax)[i] = cc_o2f(bmax[i]);
+    ((float*)bmin)[i] = o2f(bmin[i]);
+    ((float*)bmax)[i] = o2f(bmax[i]);
 }
 
 // ---- compaction -------------------------------------------------------------------------------------------------------------------------
@@ -285,9 +206,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_mark_kernel(const int* __restri
     int k = 0;
     if (t < T) {
         const int a = tris[3 * t], b = tris[3 * t + 1], d = tris[3 * t + 2];
-        if (cc_in_range(a, V) && cc_in_range(b, V) && cc_in_range(d, V)) {
+        if (in_range(a, V) && in_range(b, V) && in_range(d, V)) {
             const int c = comp[a];
-            if (cc_in_range(c, K) && keep[c]) {
+            if (in_range(c, K) && keep[c]) {
                 k = 1;
                 vflag[a] = 1;                                        // (every writer stores the same value)
                 vflag[b] = 1;
@@ -335,17 +256,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_emit_tris_kernel(const int* __r
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + CC_THREADS - 1) / CC_THREADS); }
-
 bool sizes_ok(int64_t V, int64_t T) { return V >= 0 && T >= 0 && V <= CC_MAX_ITEMS && T <= CC_MAX_ITEMS; }
-
-size_t scan_temp_i32(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int*)nullptr, (int*)nullptr, (int)items);
-    return bytes;
-}
 
 struct StatsLayout {
     size_t rank, tmp, pbase, key_a, key_b, val_a, val_b, partial, temp, temp_bytes, total;
@@ -353,54 +264,45 @@ struct StatsLayout {
 
 int64_t max_pieces(int64_t V, int64_t T) { return T / CC_PIECE + V + 1; }     // (every component with a face: one piece that is not full)
 
-StatsLayout stats_layout(int64_t V, int64_t T) {
-    StatsLayout w{};
-    size_t at = 0;
-    const size_t vi = align256((size_t)(V + 1) * sizeof(int)), ti = align256((size_t)T * sizeof(unsigned));
-    w.rank = at;  at += vi;
-    w.tmp = at;   at += vi;                                          // the root flags, then the face offsets of the components
-    w.pbase = at; at += vi;
-    w.key_a = at; at += ti;
-    w.key_b = at; at += ti;
-    w.val_a = at; at += ti;
-    w.val_b = at; at += ti;
-    w.partial = at; at += align256((size_t)max_pieces(V, T) * sizeof(double));
-    size_t a = scan_temp_i32(V + 1), b = 0;
-    if (T > 0)
-        (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, b, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                                 (unsigned*)nullptr, (int)T, 0, 32);
-    w.temp_bytes = a > b ? a : b;
-    w.temp = at;  at += align256(w.temp_bytes);
-    w.total = at;
-    return w;
+int stats_layout(int64_t V, int64_t T, StatsLayout* w) {
+    size_t a = 0, b = 0;
+    if (scan_temp<int>(V + 1, &a) != hipSuccess || sort_pairs_temp<unsigned>(T, 32, &b) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: the scratch-size query of the rank scan or the face sort failed");
+    Carve c;
+    const size_t vi = (size_t)(V + 1) * sizeof(int), ti = (size_t)T * sizeof(unsigned);
+    w->rank = c.take(vi);
+    w->tmp = c.take(vi);                                             // the root flags, then the face offsets of the components
+    w->pbase = c.take(vi);
+    w->key_a = c.take(ti);
+    w->key_b = c.take(ti);
+    w->val_a = c.take(ti);
+    w->val_b = c.take(ti);
+    w->partial = c.take((size_t)max_pieces(V, T) * sizeof(double));
+    w->temp_bytes = a > b ? a : b;
+    w->temp = c.take(w->temp_bytes);
+    w->total = c.at;
+    return NERO_OK;
 }
 
 struct CompactLayout {
     size_t hdr, vflag, vpre, fflag, fpre, temp, temp_bytes, total;
 };
 
-CompactLayout compact_layout(int64_t V, int64_t T) {
-    CompactLayout w{};
-    size_t at = 256;                                                // header: int64 {V', T'}
-    const size_t vi = align256((size_t)(V + 1) * sizeof(int)), ti = align256((size_t)(T + 1) * sizeof(int));
-    w.vflag = at; at += vi;
-    w.vpre = at;  at += vi;
-    w.fflag = at; at += ti;
-    w.fpre = at;  at += ti;
-    const size_t a = scan_temp_i32(V + 1), b = scan_temp_i32(T + 1);
-    w.temp_bytes = a > b ? a : b;
-    w.temp = at;  at += align256(w.temp_bytes);
-    w.total = at;
-    return w;
-}
-
-int bit_length(int64_t x) {
-    int n = 0;
-    while (x > 0) {
-        ++n;
-        x >>= 1;
-    }
-    return n;
+int compact_layout(int64_t V, int64_t T, CompactLayout* w) {
+    size_t a = 0, b = 0;
+    if (scan_temp<int>(V + 1, &a) != hipSuccess || scan_temp<int>(T + 1, &b) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_compact: the scratch-size query of the vertex or the triangle scan failed");
+    Carve c;
+    const size_t vi = (size_t)(V + 1) * sizeof(int), ti = (size_t)(T + 1) * sizeof(int);
+    w->hdr = c.take(256);                                            // header: int64 {V', T'}
+    w->vflag = c.take(vi);
+    w->vpre = c.take(vi);
+    w->fflag = c.take(ti);
+    w->fpre = c.take(ti);
+    w->temp_bytes = a > b ? a : b;
+    w->temp = c.take(w->temp_bytes);
+    w->total = c.at;
+    return NERO_OK;
 }
 
 }  // namespace
@@ -428,8 +330,9 @@ int nero_mesh_cc_label(const int* tris, int64_t T, int64_t V, int* label, int64_
 }
 
 size_t nero_mesh_cc_stats_workspace_bytes(int64_t V, int64_t T) {
-    if (!sizes_ok(V, T)) return 0;
-    return stats_layout(V, T).total;
+    if (!sizes_ok(V, T)) return no_workspace("nero_mesh_cc_stats_workspace_bytes: V and T must be in [0, 2^31)");
+    StatsLayout L;
+    return stats_layout(V, T, &L) == NERO_OK ? L.total : 0;
 }
 
 int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V, const int* label, int64_t K, void* ws, int* comp,
@@ -441,7 +344,8 @@ int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V
         return nero_fail(NERO_ERR_ARG, "nero_mesh_cc_stats: null pointer");
     hipStream_t s = (hipStream_t)stream;
     uint8_t* w = (uint8_t*)ws;
-    const StatsLayout L = stats_layout(V, T);
+    StatsLayout L;
+    if (int rc = stats_layout(V, T, &L)) return rc;
     int* rank = (int*)(w + L.rank);
     int* tmp = (int*)(w + L.tmp);
     if (hipMemsetAsync(n_verts, 0, (size_t)K * sizeof(int), s) != hipSuccess ||
@@ -452,9 +356,7 @@ int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V
         return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: hipMemsetAsync failed");
     hipLaunchKernelGGL(cc_rootflag_kernel, dim3(blocks_of(V + 1)), dim3(CC_THREADS), 0, s, label, (int)V, tmp);
     if (int rc = nero_check_launch("nero_mesh_cc_stats: root flags")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int*)tmp, rank, (int)(V + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: rank scan failed");
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)tmp, rank, V + 1, s, "nero_mesh_cc_stats: rank scan failed")) return rc;
     hipLaunchKernelGGL(cc_vertex_kernel, dim3(blocks_of(V)), dim3(CC_THREADS), 0, s, verts, label, (const int*)rank, (int)V, (int)K, comp,
                        n_verts, (unsigned*)bbox_min, (unsigned*)bbox_max);
     if (int rc = nero_check_launch("nero_mesh_cc_stats: vertex pass")) return rc;
@@ -473,17 +375,12 @@ int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V
     // offsets[c] = first sorted face of component c, offsets[K] = the faces that belong to a component; pbase likewise for the pieces
     if (hipMemsetAsync(tmp, 0, sizeof(int), s) != hipSuccess || hipMemsetAsync(pbase, 0, sizeof(int), s) != hipSuccess)
         return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: hipMemsetAsync failed");
-    tb = L.temp_bytes;
-    if (hipcub::DeviceScan::InclusiveSum((void*)(w + L.temp), tb, (const int*)n_faces, tmp + 1, (int)K, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: offset scan failed");
-    tb = L.temp_bytes;
+    if (int rc = inclusive_sum(w + L.temp, L.temp_bytes, (const int*)n_faces, tmp + 1, K, s, "nero_mesh_cc_stats: offset scan failed")) return rc;
     hipcub::TransformInputIterator<int, CcPieces, const int*> pieces((const int*)n_faces, CcPieces());
-    if (hipcub::DeviceScan::InclusiveSum((void*)(w + L.temp), tb, pieces, pbase + 1, (int)K, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: piece scan failed");
-    tb = L.temp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)(w + L.temp), tb, (const unsigned*)key_a, key_b, (const unsigned*)val_a, val_b, (int)T, 0,
-                                           bit_length(K), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_cc_stats: face sort failed");
+    if (int rc = inclusive_sum(w + L.temp, L.temp_bytes, pieces, pbase + 1, K, s, "nero_mesh_cc_stats: piece scan failed")) return rc;
+    if (int rc = sort_pairs<unsigned>(w + L.temp, L.temp_bytes, key_a, key_b, val_a, val_b, T, bit_length(K), s,
+                                      "nero_mesh_cc_stats: face sort failed"))
+        return rc;
     const int64_t waves = T / CC_PIECE + K;                          // at least as many as there are pieces
     hipLaunchKernelGGL(cc_area_piece_kernel, dim3(blocks_of(64 * waves)), dim3(CC_THREADS), 0, s, verts, tris, (const unsigned*)val_b,
                        (const int*)tmp, (const int*)pbase, (int)K, partial);
@@ -494,8 +391,9 @@ int nero_mesh_cc_stats(const float* verts, const int* tris, int64_t T, int64_t V
 }
 
 size_t nero_mesh_compact_workspace_bytes(int64_t V, int64_t T) {
-    if (!sizes_ok(V, T)) return 0;
-    return compact_layout(V, T).total;
+    if (!sizes_ok(V, T)) return no_workspace("nero_mesh_compact_workspace_bytes: V and T must be in [0, 2^31)");
+    CompactLayout L;
+    return compact_layout(V, T, &L) == NERO_OK ? L.total : 0;
 }
 
 int nero_mesh_compact_count(const int* tris, int64_t T, int64_t V, const int* comp, const unsigned char* keep, int64_t K, void* ws,
@@ -506,19 +404,20 @@ int nero_mesh_compact_count(const int* tris, int64_t T, int64_t V, const int* co
         return nero_fail(NERO_ERR_ARG, "nero_mesh_compact_count: null pointer");
     hipStream_t s = (hipStream_t)stream;
     uint8_t* w = (uint8_t*)ws;
-    const CompactLayout L = compact_layout(V, T);
+    CompactLayout L;
+    if (int rc = compact_layout(V, T, &L)) return rc;
     int* vflag = (int*)(w + L.vflag);
     int* fflag = (int*)(w + L.fflag);
     if (hipMemsetAsync(vflag, 0, (size_t)(V + 1) * sizeof(int), s) != hipSuccess)
         return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_compact_count: hipMemsetAsync failed");
     hipLaunchKernelGGL(cc_mark_kernel, dim3(blocks_of(T + 1)), dim3(CC_THREADS), 0, s, tris, T, (int)V, (int)K, comp, keep, fflag, vflag);
     if (int rc = nero_check_launch("nero_mesh_compact_count: mark pass")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int*)vflag, (int*)(w + L.vpre), (int)(V + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_compact_count: vertex scan failed");
-    tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), tb, (const int*)fflag, (int*)(w + L.fpre), (int)(T + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_compact_count: triangle scan failed");
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)vflag, (int*)(w + L.vpre), V + 1, s,
+                               "nero_mesh_compact_count: vertex scan failed"))
+        return rc;
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)fflag, (int*)(w + L.fpre), T + 1, s,
+                               "nero_mesh_compact_count: triangle scan failed"))
+        return rc;
     hipLaunchKernelGGL(cc_totals_kernel, dim3(1), dim3(64), 0, s, (const int*)(w + L.vpre), (const int*)(w + L.fpre), (int)V, T,
                        (int64_t*)(w + L.hdr), totals);
     return nero_check_launch("nero_mesh_compact_count");
@@ -531,12 +430,12 @@ int nero_mesh_compact_emit(const float* verts, const int* tris, int64_t T, int64
         return nero_fail(NERO_ERR_ARG, "nero_mesh_compact_emit: null pointer or negative capacity");
     hipStream_t s = (hipStream_t)stream;
     uint8_t* w = (uint8_t*)ws;
-    const CompactLayout L = compact_layout(V, T);
+    CompactLayout L;
+    if (int rc = compact_layout(V, T, &L)) return rc;
     // the one synchronisation: the totals nero_mesh_compact_count left in the workspace, so that outputs that are too small are an error
     // code and not a write out of range
     int64_t tot[2] = {-1, -1};
-    if (hipMemcpyAsync(tot, w + L.hdr, sizeof(tot), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_compact_emit: reading the totals of nero_mesh_compact_count failed");
+    if (int rc = read_back(tot, w + L.hdr, sizeof(tot), s, "nero_mesh_compact_emit: reading the totals of nero_mesh_compact_count failed")) return rc;
     const int64_t V2 = tot[0], T2 = tot[1];
     if (V2 < 0 || T2 < 0 || V2 > V || T2 > T)
         return nero_fail(NERO_ERR_ARG, "nero_mesh_compact_emit: the workspace holds no totals of nero_mesh_compact_count for this mesh");

@@ -18,16 +18,22 @@
 // The file is compiled without floating-point contraction, so that the keys, the normals and the clamp bounds are the IEEE operations the
 // restatement performs.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
+#include "ws_plan.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 constexpr int MS_THREADS = 256;
 constexpr int MS_PIECE = 2048;                                      // elements a wave sums into one partial
@@ -45,8 +51,6 @@ struct MsParams {
 
 // hdr (int64): 0 V', 1 survivors, 2 refused vertices, 3 refused triangles, 4 occupied cells, 5 T' of the last emit, 6 the count was complete
 enum { H_VOUT = 0, H_SURV = 1, H_BADV = 2, H_BADT = 3, H_CELLS = 4, H_TOUT = 5, H_FULL = 6, H_WORDS = 8 };
-
-__device__ __forceinline__ bool ms_in_range(int a, int V) { return (unsigned)a < (unsigned)V; }
 
 __device__ __forceinline__ bool ms_axis(float x, double o, double cell, u64* i) {
     const double d = floor(((double)x - o) / cell);
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_survivor_kernel(const int* __re
         int k = 0;
         if (t < T) {
             const int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-            if (ms_in_range(a, V) && ms_in_range(b, V) && ms_in_range(c, V)) {
+            if (in_range(a, V) && in_range(b, V) && in_range(c, V)) {
                 const u64 ka = key[a], kb = key[b], kc = key[c];
                 k = ka != MS_NO_KEY && kb != MS_NO_KEY && kc != MS_NO_KEY && ka != kb && kb != kc && ka != kc;
             } else {
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_contrib_key_kernel(const int* _
     const int64_t t = i / 3;
     const int a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
     int k = -1;
-    if (ms_in_range(a, V) && ms_in_range(b, V) && ms_in_range(c, V)) k = cellid[tris[i]];
+    if (in_range(a, V) && in_range(b, V) && in_range(c, V)) k = cellid[tris[i]];
     key[i] = k >= 0 ? (unsigned)k : (unsigned)V;
     val[i] = (unsigned)i;
 }
@@ -158,12 +162,6 @@ __global__ __launch_bounds__(MS_THREADS) void ms_contrib_range_kernel(const unsi
     const unsigned k = skey[i];
     if (i == 0 || skey[i - 1] != k) cstart[k] = (int)i;
     if (i == n3 - 1 || skey[i + 1] != k) cend[k] = (int)(i + 1);
-}
-
-__device__ __forceinline__ double ms_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // one wave per occupied cell; only the used cells are placed
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_place_kernel(const float* __res
             for (int a = 0; a < 3; ++a) s[a] += (double)q[a];
         }
 #pragma unroll
-        for (int a = 0; a < 3; ++a) m[a] += ms_wave_sum(s[a]);
+        for (int a = 0; a < 3; ++a) m[a] += wave_sum(s[a]);
     }
     const double cnt = (double)(ve - vb);
 #pragma unroll
@@ -220,9 +218,9 @@ __global__ __launch_bounds__(MS_THREADS) void ms_place_kernel(const float* __res
                 sr[0] += nx * d;  sr[1] += ny * d;  sr[2] += nz * d;
             }
 #pragma unroll
-            for (int a = 0; a < 6; ++a) A[a] += ms_wave_sum(sa[a]);
+            for (int a = 0; a < 6; ++a) A[a] += wave_sum(sa[a]);
 #pragma unroll
-            for (int a = 0; a < 3; ++a) r[a] += ms_wave_sum(sr[a]);
+            for (int a = 0; a < 3; ++a) r[a] += wave_sum(sr[a]);
         }
     }
     if (lane != 0) return;
@@ -359,25 +357,7 @@ __global__ void ms_final_kernel(const int* __restrict__ opre, int64_t n, u64* hd
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + MS_THREADS - 1) / MS_THREADS); }
-
 bool sizes_ok(int64_t V, int64_t T) { return V >= 0 && T >= 0 && V <= MS_MAX_V && T <= MS_MAX_T; }
-
-int bit_length(int64_t x) {
-    int n = 0;
-    while (x > 0) {
-        ++n;
-        x >>= 1;
-    }
-    return n;
-}
-
-// The scratch of the scans and sorts.  hipCUB chooses its algorithm, and with it its scratch, by the item count, and the answer is not
-// monotone in it; the workspace must be (a caller may size it once for its largest mesh), so the scratch is an explicit bound: a copy of
-// the keys and values (the merge-sort and the out-of-place passes), and the histograms and look-back words of the radix passes.
-size_t cub_bound(int64_t items, size_t bytes_per_item) { return align256((size_t)items * (bytes_per_item + 4) + ((size_t)4 << 20)); }
 
 struct Layout {
     size_t hdr, vkey_a, vkey_b, vval_a, vval_b, cellid, hflag, hpre, vstart, used, upre, fflag, fpre, ckey_a, ckey_b, cval_a, cval_b,
@@ -386,69 +366,41 @@ struct Layout {
 
 Layout layout(int64_t V, int64_t T) {
     Layout w{};
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += align256(bytes);
-        return here;
-    };
+    Carve c;
     const size_t v1 = (size_t)(V + 1) * sizeof(int), t1 = (size_t)(T + 1) * sizeof(int), n3 = (size_t)(3 * T);
-    w.hdr = take(H_WORDS * sizeof(u64));
-    w.vkey_a = take((size_t)V * 8);
-    w.vkey_b = take((size_t)V * 8);
-    w.vval_a = take((size_t)V * 4);
-    w.vval_b = take((size_t)V * 4);
-    w.cellid = take(v1);
-    w.hflag = take(v1);
-    w.hpre = take(v1);
-    w.vstart = take(v1);
-    w.used = take(v1);
-    w.upre = take(v1);
-    w.fflag = take(t1);
-    w.fpre = take(t1);
-    w.ckey_a = take(n3 * 4);
-    w.ckey_b = take(n3 * 4);
-    w.cval_a = take(n3 * 4);
-    w.cval_b = take(n3 * 4);
-    w.cstart = take(v1);
-    w.cend = take(v1);
-    w.dkey_a = take((size_t)T * 8);
-    w.dkey_b = take((size_t)T * 8);
-    w.dval_a = take((size_t)T * 4);
-    w.dval_b = take((size_t)T * 4);
-    w.akey_a = take((size_t)T * 4);
-    w.akey_b = take((size_t)T * 4);
-    w.surv_t = take((size_t)T * 4);
-    w.keep = take(t1);
-    w.opre = take(t1);
-    const size_t a = cub_bound(V + 1, 12), b = cub_bound(3 * T + 1, 8);
+    w.hdr = c.take(H_WORDS * sizeof(u64));
+    w.vkey_a = c.take((size_t)V * 8);
+    w.vkey_b = c.take((size_t)V * 8);
+    w.vval_a = c.take((size_t)V * 4);
+    w.vval_b = c.take((size_t)V * 4);
+    w.cellid = c.take(v1);
+    w.hflag = c.take(v1);
+    w.hpre = c.take(v1);
+    w.vstart = c.take(v1);
+    w.used = c.take(v1);
+    w.upre = c.take(v1);
+    w.fflag = c.take(t1);
+    w.fpre = c.take(t1);
+    w.ckey_a = c.take(n3 * 4);
+    w.ckey_b = c.take(n3 * 4);
+    w.cval_a = c.take(n3 * 4);
+    w.cval_b = c.take(n3 * 4);
+    w.cstart = c.take(v1);
+    w.cend = c.take(v1);
+    w.dkey_a = c.take((size_t)T * 8);
+    w.dkey_b = c.take((size_t)T * 8);
+    w.dval_a = c.take((size_t)T * 4);
+    w.dval_b = c.take((size_t)T * 4);
+    w.akey_a = c.take((size_t)T * 4);
+    w.akey_b = c.take((size_t)T * 4);
+    w.surv_t = c.take((size_t)T * 4);
+    w.keep = c.take(t1);
+    w.opre = c.take(t1);
+    const size_t a = sort_temp_bound(V + 1, 12), b = sort_temp_bound(3 * T + 1, 8);
     w.temp_bytes = a > b ? a : b;
-    w.temp = take(w.temp_bytes);
-    w.total = at;
+    w.temp = c.take(w.temp_bytes);
+    w.total = c.at;
     return w;
-}
-
-int scan_i32(const Layout& L, uint8_t* w, const int* in, int* out, int64_t items, hipStream_t s, const char* what) {
-    size_t need = 0;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)nullptr, need, in, out, (int)items, s) != hipSuccess || need > L.temp_bytes)
-        return nero_fail(NERO_ERR_LAUNCH, what);
-    size_t have = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(w + L.temp), have, in, out, (int)items, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, what);
-    return NERO_OK;
-}
-
-template <typename K>
-int sort_pairs(const Layout& L, uint8_t* w, const K* kin, K* kout, const unsigned* vin, unsigned* vout, int64_t items, int bits,
-               hipStream_t s, const char* what) {
-    size_t need = 0;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)nullptr, need, kin, kout, vin, vout, (int)items, 0, bits, s) != hipSuccess ||
-        need > L.temp_bytes)
-        return nero_fail(NERO_ERR_LAUNCH, what);
-    size_t have = L.temp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs((void*)(w + L.temp), have, kin, kout, vin, vout, (int)items, 0, bits, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, what);
-    return NERO_OK;
 }
 
 bool params_ok(double cell, const double* origin) {
@@ -493,14 +445,14 @@ int nero_mesh_simplify_count(const float* verts, const int* tris, int64_t T, int
     }
     hipLaunchKernelGGL(ms_survivor_kernel, dim3(blocks_of(T + 1)), dim3(MS_THREADS), 0, s, tris, T, (int)V, (const u64*)vkey, fflag, hdr);
     if (int rc = nero_check_launch("nero_mesh_simplify_count: survivors")) return rc;
-    if (int rc = scan_i32(L, w, fflag, fpre, T + 1, s, "nero_mesh_simplify_count: survivor scan failed")) return rc;
+    if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)fflag, fpre, T + 1, s, "nero_mesh_simplify_count: survivor scan failed")) return rc;
     const int full = !faces_only;
     if (full) {
         if (V > 0)
-            if (int rc = sort_pairs<u64>(L, w, vkey, skey, vval, sval, V, 64, s, "nero_mesh_simplify_count: vertex sort failed")) return rc;
+            if (int rc = sort_pairs<u64>(w + L.temp, L.temp_bytes, vkey, skey, vval, sval, V, 64, s, "nero_mesh_simplify_count: vertex sort failed")) return rc;
         hipLaunchKernelGGL(ms_head_kernel, dim3(blocks_of(V + 1)), dim3(MS_THREADS), 0, s, (const u64*)skey, (int)V, hflag);
         if (int rc = nero_check_launch("nero_mesh_simplify_count: head flags")) return rc;
-        if (int rc = scan_i32(L, w, hflag, hpre, V + 1, s, "nero_mesh_simplify_count: cell scan failed")) return rc;
+        if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)hflag, hpre, V + 1, s, "nero_mesh_simplify_count: cell scan failed")) return rc;
         hipLaunchKernelGGL(ms_cell_kernel, dim3(blocks_of(V + 1)), dim3(MS_THREADS), 0, s, (const u64*)skey, (const unsigned*)sval,
                            (const int*)hflag, (const int*)hpre, (int)V, cellid, vstart);
         if (int rc = nero_check_launch("nero_mesh_simplify_count: cells")) return rc;
@@ -510,7 +462,7 @@ int nero_mesh_simplify_count(const float* verts, const int* tris, int64_t T, int
             hipLaunchKernelGGL(ms_used_kernel, dim3(blocks_of(T)), dim3(MS_THREADS), 0, s, tris, T, (const int*)fflag, (const int*)cellid, used);
             if (int rc = nero_check_launch("nero_mesh_simplify_count: used cells")) return rc;
         }
-        if (int rc = scan_i32(L, w, used, upre, V + 1, s, "nero_mesh_simplify_count: used-cell scan failed")) return rc;
+        if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)used, upre, V + 1, s, "nero_mesh_simplify_count: used-cell scan failed")) return rc;
     }
     hipLaunchKernelGGL(ms_totals_kernel, dim3(1), dim3(64), 0, s, (const int*)fpre, T, (const int*)hpre, (const int*)upre, (int)V, full, hdr,
                        totals);
@@ -535,8 +487,7 @@ int nero_mesh_simplify_emit(const float* verts, const int* tris, int64_t T, int6
     // the one synchronisation: the totals nero_mesh_simplify_count left in the workspace, so that outputs that are too small, or input the
     // count refused, are an error code and not a write out of range
     long long h[H_WORDS];
-    if (hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_mesh_simplify_emit: reading the totals of nero_mesh_simplify_count failed");
+    if (int rc = read_back(h, hdr, sizeof(h), s, "nero_mesh_simplify_emit: reading the totals of nero_mesh_simplify_count failed")) return rc;
     const int64_t V2 = h[H_VOUT], S = h[H_SURV], C = h[H_CELLS];
     if (h[H_FULL] != 1 || V2 < 0 || S < 0 || C < 0 || V2 > C || C > V || S > T)
         return nero_fail(NERO_ERR_ARG, "nero_mesh_simplify_emit: the workspace holds no complete totals of nero_mesh_simplify_count for this mesh");
@@ -571,7 +522,7 @@ int nero_mesh_simplify_emit(const float* verts, const int* tris, int64_t T, int6
         if (quadric) {                                               // (V' > 0: there is a survivor, T > 0)
             hipLaunchKernelGGL(ms_contrib_key_kernel, dim3(blocks_of(n3)), dim3(MS_THREADS), 0, s, tris, n3, (int)V, cellid, ckey_a, cval_a);
             if (int rc = nero_check_launch("nero_mesh_simplify_emit: contribution keys")) return rc;
-            if (int rc = sort_pairs<unsigned>(L, w, ckey_a, ckey_b, cval_a, cval_b, n3, bit_length(V), s,
+            if (int rc = sort_pairs<unsigned>(w + L.temp, L.temp_bytes, ckey_a, ckey_b, cval_a, cval_b, n3, bit_length(V), s,
                                               "nero_mesh_simplify_emit: contribution sort failed"))
                 return rc;
             if (hipMemsetAsync(cstart, 0, (size_t)(V + 1) * sizeof(int), s) != hipSuccess ||
@@ -604,17 +555,17 @@ int nero_mesh_simplify_emit(const float* verts, const int* tris, int64_t T, int6
         const int bits = bit_length(V2);
         hipLaunchKernelGGL(ms_triple_kernel, dim3(blocks_of(T)), dim3(MS_THREADS), 0, s, tris, T, fflag, fpre, cellid, upre, surv_t, dkey_a, dval_a);
         if (int rc = nero_check_launch("nero_mesh_simplify_emit: triples")) return rc;
-        if (int rc = sort_pairs<u64>(L, w, dkey_a, dkey_b, dval_a, dval_b, S, 32 + bits, s, "nero_mesh_simplify_emit: first triple sort failed"))
+        if (int rc = sort_pairs<u64>(w + L.temp, L.temp_bytes, dkey_a, dkey_b, dval_a, dval_b, S, 32 + bits, s, "nero_mesh_simplify_emit: first triple sort failed"))
             return rc;
         hipLaunchKernelGGL(ms_second_key_kernel, dim3(blocks_of(S)), dim3(MS_THREADS), 0, s, tris, (const unsigned*)dval_b, S,
                            (const unsigned*)surv_t, cellid, upre, akey_a);
         if (int rc = nero_check_launch("nero_mesh_simplify_emit: second keys")) return rc;
-        if (int rc = sort_pairs<unsigned>(L, w, akey_a, akey_b, dval_b, dval_a, S, bits, s, "nero_mesh_simplify_emit: second triple sort failed"))
+        if (int rc = sort_pairs<unsigned>(w + L.temp, L.temp_bytes, akey_a, akey_b, dval_b, dval_a, S, bits, s, "nero_mesh_simplify_emit: second triple sort failed"))
             return rc;
         hipLaunchKernelGGL(ms_first_kernel, dim3(blocks_of(S + 1)), dim3(MS_THREADS), 0, s, tris, (const unsigned*)dval_a, S,
                            (const unsigned*)surv_t, cellid, upre, keep_w);
         if (int rc = nero_check_launch("nero_mesh_simplify_emit: first of each triple")) return rc;
-        if (int rc = scan_i32(L, w, keep_w, opre_w, S + 1, s, "nero_mesh_simplify_emit: output scan failed")) return rc;
+        if (int rc = exclusive_sum(w + L.temp, L.temp_bytes, (const int*)keep_w, opre_w, S + 1, s, "nero_mesh_simplify_emit: output scan failed")) return rc;
         keep = keep_w;
         opre = opre_w;
     }

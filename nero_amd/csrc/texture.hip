@@ -13,13 +13,19 @@
 // map are 2 x 262144 equal work items.  Overlaps resolve by an unsigned atomicMin on the id (lowest triangle wins; order independent).
 // Compaction (nero_uv_interp) is by prefix sum.  Nothing here uses floating-point atomics; every result is bit-identical run to run.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "cub_calls.h"
+#include "device_prims.h"
+#include "ws_plan.h"
 
 namespace {
+
+using namespace nero_cub;
+using namespace nero_prims;
+using namespace nero_ws;
 
 constexpr int TX_MAX_SIZE = 16384;
 constexpr int TX_MAX_PAD = 64;
@@ -29,8 +35,6 @@ constexpr int UV_BLOCK = 8;                         // a wave's work item: UV_BL
 constexpr int UV_WALK_BLOCKS = 2048;                // fixed grid of the block walk: 256 CUs x 8 workgroups of 4 waves
 constexpr double UV_COORD_LIMIT = 1073741824.0;     // |snapped coordinate| <= 2^30: every edge function stays below 2^63
 constexpr int FILL_TILE = 16;
-
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct TxHeader {                 // first 256 bytes of the raster / interpolation workspaces
     int bad;                      // an index out of range was seen
@@ -161,9 +165,7 @@ __global__ __launch_bounds__(256) void uv_walk_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void uv_overlap_sum_kernel(const unsigned* __restrict__ cover, int64_t n, unsigned long long* count) {
     __shared__ int part[4];
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    int v = p < n && cover[p] > 1u ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int v = wave_sum(p < n && cover[p] > 1u ? 1 : 0);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -383,18 +385,6 @@ __global__ __launch_bounds__(256) void tx_down2_kernel(const unsigned char* __re
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------------
-size_t scan_temp_i64(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (int)items);
-    return bytes;
-}
-
-size_t scan_temp_i32(int64_t items) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, bytes, (const int*)nullptr, (int*)nullptr, (int)items);
-    return bytes;
-}
-
 bool size_ok(int h, int w) { return h >= 1 && h <= TX_MAX_SIZE && w >= 1 && w <= TX_MAX_SIZE; }
 bool count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31) - 1; }
 
@@ -409,44 +399,39 @@ struct RasterLayout {
     size_t cnt, base, temp, temp_bytes, total;
 };
 
-RasterLayout raster_layout(int64_t nt) {
-    RasterLayout L{};
-    size_t at = 256;                                              // TxHeader
-    L.cnt = at;  at += align256((size_t)(nt + 1) * sizeof(int64_t));
-    L.base = at; at += align256((size_t)(nt + 1) * sizeof(int64_t));
-    L.temp_bytes = scan_temp_i64(nt + 1);
-    L.temp = at; at += align256(L.temp_bytes);
-    L.total = at;
-    return L;
+int raster_layout(int64_t nt, RasterLayout* L) {
+    if (scan_temp<int64_t>(nt + 1, &L->temp_bytes) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_raster: the scratch-size query of the block scan failed");
+    Carve c{256};                                                 // TxHeader
+    L->cnt = c.take((size_t)(nt + 1) * sizeof(int64_t));
+    L->base = c.take((size_t)(nt + 1) * sizeof(int64_t));
+    L->temp = c.take(L->temp_bytes);
+    L->total = c.at;
+    return NERO_OK;
 }
 
 struct InterpLayout {
     size_t flag, rank, temp, temp_bytes, total;
 };
 
-InterpLayout interp_layout(int64_t n) {
-    InterpLayout L{};
-    size_t at = 256;                                              // TxHeader
-    L.flag = at; at += align256((size_t)(n + 1) * sizeof(int));
-    L.rank = at; at += align256((size_t)(n + 1) * sizeof(int));
-    L.temp_bytes = scan_temp_i32(n + 1);
-    L.temp = at; at += align256(L.temp_bytes);
-    L.total = at;
-    return L;
-}
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// the header after the kernels queued so far: the one synchronisation of nero_uv_raster / nero_uv_interp
-int read_header(const char* fn, void* ws, hipStream_t s, TxHeader* host) {
-    if (hipMemcpyAsync(host, ws, sizeof(TxHeader), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, fn);
+int interp_layout(int64_t n, InterpLayout* L) {
+    if (scan_temp<int>(n + 1, &L->temp_bytes) != hipSuccess)
+        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_interp: the scratch-size query of the scan of the coverage failed");
+    Carve c{256};                                                 // TxHeader
+    L->flag = c.take((size_t)(n + 1) * sizeof(int));
+    L->rank = c.take((size_t)(n + 1) * sizeof(int));
+    L->temp = c.take(L->temp_bytes);
+    L->total = c.at;
     return NERO_OK;
 }
 
 }  // namespace
 
-size_t nero_uv_raster_workspace_bytes(int64_t nt) { return count_ok(nt) ? raster_layout(nt).total : 0; }
+size_t nero_uv_raster_workspace_bytes(int64_t nt) {
+    RasterLayout L;
+    if (!count_ok(nt)) return no_workspace("nero_uv_raster_workspace_bytes: nt must be in [0, 2^31 - 1)");
+    return raster_layout(nt, &L) == NERO_OK ? L.total : 0;
+}
 
 int nero_uv_raster(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int* tri_id, void* stream) {
     if (int rc = check_size("nero_uv_raster", h, w)) return rc;
@@ -460,27 +445,28 @@ int nero_uv_raster(const float* vt, int64_t nvt, const int* ft, int64_t nt, int 
         hipLaunchKernelGGL(tx_index_check_kernel, dim3(blocks_of(3 * nt)), dim3(256), 0, s, ft, 3 * nt, nvt, (TxHeader*)b);
         if (int rc = nero_check_launch("nero_uv_raster: index check")) return rc;
         TxHeader host{};
-        if (int rc = read_header("nero_uv_raster: reading the index check back failed", ws, s, &host)) return rc;
+        if (int rc = read_back(&host, ws, sizeof(host), s, "nero_uv_raster: reading the index check back failed")) return rc;
         if (host.bad) return nero_fail(NERO_ERR_ARG, "nero_uv_raster: ft holds an index outside [0, nvt)");
     }
     if (hipMemsetAsync(tri_id, 0xff, (size_t)n * sizeof(int), s) != hipSuccess)        // -1 = 0xffffffff: the identity of the unsigned minimum
         return nero_fail(NERO_ERR_LAUNCH, "nero_uv_raster: hipMemsetAsync failed");
     if (nt == 0) return NERO_OK;
-    const RasterLayout L = raster_layout(nt);
+    RasterLayout L;
+    if (int rc = raster_layout(nt, &L)) return rc;
     int64_t* cnt = (int64_t*)(b + L.cnt);
     int64_t* base = (int64_t*)(b + L.base);
     hipLaunchKernelGGL(uv_small_kernel<false>, dim3(blocks_of(nt + 1)), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (unsigned*)tri_id, cnt);
     if (int rc = nero_check_launch("nero_uv_raster: small-triangle pass")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int64_t*)cnt, base, (int)(nt + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_raster: block scan failed");
+    if (int rc = exclusive_sum(b + L.temp, L.temp_bytes, (const int64_t*)cnt, base, nt + 1, s, "nero_uv_raster: block scan failed")) return rc;
     hipLaunchKernelGGL(uv_walk_kernel<false>, dim3(UV_WALK_BLOCKS), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (const int64_t*)base, (unsigned*)tri_id);
     return nero_check_launch("nero_uv_raster: block walk");
 }
 
 size_t nero_uv_overlap_count_workspace_bytes(int64_t nt, int h, int w) {
-    if (!count_ok(nt) || !size_ok(h, w)) return 0;
-    return raster_layout(nt).total + align256((size_t)h * w * sizeof(unsigned));
+    RasterLayout L;
+    if (!count_ok(nt)) return no_workspace("nero_uv_overlap_count_workspace_bytes: nt must be in [0, 2^31 - 1)");
+    if (check_size("nero_uv_overlap_count_workspace_bytes", h, w) || raster_layout(nt, &L) != NERO_OK) return 0;
+    return L.total + align256((size_t)h * w * sizeof(unsigned));
 }
 
 int nero_uv_overlap_count(const float* vt, int64_t nvt, const int* ft, int64_t nt, int h, int w, void* ws, int64_t* count, void* stream) {
@@ -492,7 +478,8 @@ int nero_uv_overlap_count(const float* vt, int64_t nvt, const int* ft, int64_t n
     if (nt == 0) return NERO_OK;
     uint8_t* b = (uint8_t*)ws;
     const int64_t n = (int64_t)h * w;
-    const RasterLayout L = raster_layout(nt);
+    RasterLayout L;
+    if (int rc = raster_layout(nt, &L)) return rc;
     int64_t* cnt = (int64_t*)(b + L.cnt);
     int64_t* base = (int64_t*)(b + L.base);
     unsigned* cover = (unsigned*)(b + L.total);
@@ -500,16 +487,18 @@ int nero_uv_overlap_count(const float* vt, int64_t nvt, const int* ft, int64_t n
         return nero_fail(NERO_ERR_LAUNCH, "nero_uv_overlap_count: hipMemsetAsync failed");
     hipLaunchKernelGGL(uv_small_kernel<true>, dim3(blocks_of(nt + 1)), dim3(256), 0, s, vt, nvt, ft, nt, h, w, cover, cnt);
     if (int rc = nero_check_launch("nero_uv_overlap_count: small-triangle pass")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int64_t*)cnt, base, (int)(nt + 1), s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_overlap_count: block scan failed");
+    if (int rc = exclusive_sum(b + L.temp, L.temp_bytes, (const int64_t*)cnt, base, nt + 1, s, "nero_uv_overlap_count: block scan failed")) return rc;
     hipLaunchKernelGGL(uv_walk_kernel<true>, dim3(UV_WALK_BLOCKS), dim3(256), 0, s, vt, nvt, ft, nt, h, w, (const int64_t*)base, cover);
     if (int rc = nero_check_launch("nero_uv_overlap_count: block walk")) return rc;
     hipLaunchKernelGGL(uv_overlap_sum_kernel, dim3(blocks_of(n)), dim3(256), 0, s, (const unsigned*)cover, n, (unsigned long long*)count);
     return nero_check_launch("nero_uv_overlap_count: sum");
 }
 
-size_t nero_uv_interp_workspace_bytes(int h, int w) { return size_ok(h, w) ? interp_layout((int64_t)h * w).total : 0; }
+size_t nero_uv_interp_workspace_bytes(int h, int w) {
+    InterpLayout L;
+    if (check_size("nero_uv_interp_workspace_bytes", h, w)) return 0;
+    return interp_layout((int64_t)h * w, &L) == NERO_OK ? L.total : 0;
+}
 
 int nero_uv_interp(const int* tri_id, const float* vt, int64_t nvt, const int* ft, int64_t nt, const float* attr, int64_t nv, int C, const int* fa,
                    int h, int w, void* ws, int* texel, float* out, int64_t cap, unsigned char* mask, int64_t* n_out, void* stream) {
@@ -520,7 +509,8 @@ int nero_uv_interp(const int* tri_id, const float* vt, int64_t nvt, const int* f
     hipStream_t s = (hipStream_t)stream;
     uint8_t* b = (uint8_t*)ws;
     const int n = h * w;
-    const InterpLayout L = interp_layout(n);
+    InterpLayout L;
+    if (int rc = interp_layout(n, &L)) return rc;
     int* flag = (int*)(b + L.flag);
     int* rank = (int*)(b + L.rank);
     if (hipMemsetAsync(b, 0, 256, s) != hipSuccess) return nero_fail(NERO_ERR_LAUNCH, "nero_uv_interp: hipMemsetAsync failed");
@@ -530,13 +520,11 @@ int nero_uv_interp(const int* tri_id, const float* vt, int64_t nvt, const int* f
     }
     hipLaunchKernelGGL(uv_flag_kernel, dim3(blocks_of((int64_t)n + 1)), dim3(256), 0, s, tri_id, n, nt, flag);
     if (int rc = nero_check_launch("nero_uv_interp: flags")) return rc;
-    size_t tb = L.temp_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum((void*)(b + L.temp), tb, (const int*)flag, rank, n + 1, s) != hipSuccess)
-        return nero_fail(NERO_ERR_LAUNCH, "nero_uv_interp: the scan of the coverage failed");
+    if (int rc = exclusive_sum(b + L.temp, L.temp_bytes, (const int*)flag, rank, n + 1, s, "nero_uv_interp: the scan of the coverage failed")) return rc;
     hipLaunchKernelGGL(uv_count_kernel, dim3(1), dim3(64), 0, s, (const int*)rank, n, (TxHeader*)b);
     if (int rc = nero_check_launch("nero_uv_interp: count")) return rc;
     TxHeader host{};
-    if (int rc = read_header("nero_uv_interp: reading the count back failed", ws, s, &host)) return rc;
+    if (int rc = read_back(&host, ws, sizeof(host), s, "nero_uv_interp: reading the count back failed")) return rc;
     if (host.bad) return nero_fail(NERO_ERR_ARG, "nero_uv_interp: ft or fa holds an index out of range");
     if (host.count > cap) {
         static thread_local char msg[160];

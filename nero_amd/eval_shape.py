@@ -123,7 +123,7 @@ def voxel_down_sample(points, voxel_size, capacity=None):
     cap = n if capacity is None else int(capacity)
     need = int(_lib.nero_voxel_downsample_workspace_bytes(n))
     if need == 0:
-        raise NotImplementedError(f'voxel_down_sample: {n} points are not supported (fewer than 2^31 - 1)')
+        raise NotImplementedError(f'voxel_down_sample: {n} points are not supported: {L.lib.nero_last_error().decode()}')
     with torch.cuda.device(dev):
         L.check_workspace_fits(need + 12 * cap, dev, what='voxel down-sampling workspace')
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -184,7 +184,7 @@ def _view(rt, verts, pose, K, shape, unproject_offset, want_points):
     _, _, t = rt.trace(o, d)
     need = int(_lib.nero_view_points_workspace_bytes(h, w))
     if need == 0:
-        raise ValueError(f'render_depth: a view of {h} x {w} pixels is not supported')
+        raise ValueError(f'render_depth: a view of {h} x {w} pixels is not supported: {L.lib.nero_last_error().decode()}')
     with torch.cuda.device(dev):
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         depth = torch.empty((h, w), dtype=torch.float32, device=dev)
@@ -222,7 +222,7 @@ def depth_points(depth, mask, pose, K, unproject_offset=0.0):
     _, _, Kc, Pc = _cam(K, pose)
     need = int(_lib.nero_view_points_workspace_bytes(h, w))
     if need == 0:
-        raise ValueError(f'depth_points: a view of {h} x {w} pixels is not supported')
+        raise ValueError(f'depth_points: a view of {h} x {w} pixels is not supported: {L.lib.nero_last_error().decode()}')
     with torch.cuda.device(dev):
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         pts = torch.empty((h * w, 3), dtype=torch.float32, device=dev)

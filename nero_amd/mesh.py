@@ -75,7 +75,7 @@ def marching_cubes_device(u, threshold=0.0):
     dev = u.device
     need = workspace_bytes(u.shape)
     if need == 0:
-        raise ValueError(f'marching_cubes_device: grid {nx} x {ny} x {nz} is not supported (every size >= 1, fewer than 2^32 points)')
+        raise ValueError(f'marching_cubes_device: grid {nx} x {ny} x {nz} is not supported (every size >= 1, fewer than 2^32 points): {L.lib.nero_last_error().decode()}')
     L.check_workspace_fits(need, dev, what='marching-cubes workspace')
     with torch.cuda.device(dev):
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -166,6 +166,8 @@ def connected_components_device(verts, tris):
     V, T = verts.shape[0], tris.shape[0]
     dev = verts.device
     need = int(L.lib.nero_mesh_cc_stats_workspace_bytes(V, T))
+    if need == 0:
+        raise L.NeroHipError(f'connected_components_device: {V} vertices / {T} triangles: no workspace ({L.lib.nero_last_error().decode()})')
     L.check_workspace_fits(need + 8 * V, dev, what='connected-components workspace')
     with torch.cuda.device(dev):
         s = L.stream_ptr()
@@ -222,6 +224,8 @@ def clean_mesh_device(verts, tris, keep=None, min_faces=0, min_face_ratio=0.0):
     dev = verts.device
     flags = select_components(cc.n_faces, keep, min_faces, min_face_ratio)
     need = int(L.lib.nero_mesh_compact_workspace_bytes(V, T))
+    if need == 0:
+        raise L.NeroHipError(f'clean_mesh_device: {V} vertices / {T} triangles: no workspace ({L.lib.nero_last_error().decode()})')
     L.check_workspace_fits(need, dev, what='mesh-compaction workspace')
     with torch.cuda.device(dev):
         s = L.stream_ptr()
@@ -272,7 +276,7 @@ def _face_adjacency(tris, V):
     dev = tris.device
     need = int(L.lib.nero_mesh_face_adjacency_workspace_bytes(T))
     if T and need == 0:
-        raise L.NeroHipError(f'face_adjacency_device: {T} triangles: 2^31 or more corners')
+        raise L.NeroHipError(f'face_adjacency_device: {T} triangles: no workspace ({L.lib.nero_last_error().decode()})')
     L.check_workspace_fits(need + 12 * T, dev, what='face-adjacency workspace')
     with torch.cuda.device(dev):
         ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
@@ -307,6 +311,8 @@ def face_charts_device(verts, tris):
     dev = verts.device
     nbr, counts = _face_adjacency(tris, V)
     need = int(L.lib.nero_mesh_chart_label_workspace_bytes(T))
+    if need == 0:
+        raise L.NeroHipError(f'face_charts_device: {T} triangles: no workspace ({L.lib.nero_last_error().decode()})')
     L.check_workspace_fits(need + 8 * T, dev, what='chart-label workspace')
     with torch.cuda.device(dev):
         s = L.stream_ptr()

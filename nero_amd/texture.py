@@ -288,7 +288,7 @@ def chart_corners_device(tris, n_verts, chart, K):
     T = tris.shape[0]
     need = int(_lib.nero_mesh_chart_corners_workspace_bytes(T))
     if T and need == 0:
-        raise L.NeroHipError(f'chart_corners_device: {T} triangles: 2^31 or more corners')
+        raise L.NeroHipError(f'chart_corners_device: {T} triangles: no workspace ({L.lib.nero_last_error().decode()})')
     L.check_workspace_fits(need + 12 * T, dev, what='chart-corner workspace')
     with torch.cuda.device(dev):
         s = L.stream_ptr()
