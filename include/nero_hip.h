@@ -644,6 +644,22 @@ int nero_stage1_render_bwd(nero_stage1* h, const float* d_rgb, const float* d_ge
 int nero_stage1_get_state(nero_stage1* h, nero_stage1_state* out);
 /* no-grad SDF values of PE-6 rows [rows_pad(n),40] -> out4 [rows_pad(n),4], column 0 = sdf (sampler / occlusion march / mesh grid) */
 int nero_stage1_sdf_from_pe(nero_stage1* h, const float* pe, int n, float* out4, void* ws, size_t ws_bytes, void* stream);
+/* The occlusion-loss branch of a training step (compute_occ_loss, network/renderer.py:522-541 + get_intersection, network/field.py:454-484)
+ * on the state of the last nero_stage1_render_fwd (n_in > 0), as one call: nero_occ_candidates, nero_occ_select, nero_occ_gather and the
+ * march nero_occ_z -> PE -> SDF values of cap*sn0 rows -> nero_section_weights -> nero_sample_pdf -> PE -> SDF values of cap*sn1 rows ->
+ * nero_section_weights, the launches nero_amd/shape_step.py::secondary_occlusion issues, in its order.
+ *   d [R,3] and variance [1]: those of the forward.  keys [>= n_in] uniform draws (nero_occ_select).  thresh = occ_sdf_thresh.
+ *   1 <= cap <= 4096, 2 <= sn0 <= 160, 1 <= sn1 <= 32.  cand int32 [cap], counts int32 [2] (nero_occ_select), occ [cap] = the marched
+ *   occlusion probability of the kept candidates (unused slots: the march of the origin along +z).
+ *   ws: nero_stage1_occlusion_workspace(h, n_in, cap, sn0, sn1) bytes of the caller's, NOT part of the step workspace.
+ * Streams: the branch needs x4 / sdf4 / normal / geo / inner_idx only, which exist once nero_sdf_alpha_fwd of the forward has run, so it is
+ * enqueued on `branch_stream` behind an event the forward records there, beside the shading networks, and `join_stream` (the stream of
+ * nero_stage1_render_fwd and of whatever reads cand / counts / occ next) is made to wait for its end.  Work the caller queued on
+ * branch_stream before the call (the key draw) stays in front of the branch.  branch_stream == join_stream, a one-stream handle
+ * (NERO_STREAMS=1, no side stream) or nero_prof_enable: everything is enqueued on join_stream, behind branch_stream's earlier work. */
+size_t nero_stage1_occlusion_workspace(nero_stage1* h, int n_in, int cap, int sn0, int sn1);
+int nero_stage1_occlusion(nero_stage1* h, const float* d, const float* variance, const float* keys, float thresh, int cap, int sn0, int sn1,
+                          int* cand, int* counts, float* occ, void* ws, size_t ws_bytes, void* branch_stream, void* join_stream);
 
 /* ---- C-level driver of the Stage-II (material) shading step (nero_mc_shade_fwd / _bwd) -----------------------------------
  * predict_materials (network/field.py:915-922) and MCShadingNetwork.shade_mixed / get_lights (:856-880, 950-1012) with their backward, in

@@ -58,6 +58,13 @@ struct nero_stage1 {
     static constexpr int N_DW_EV = 12;                     // one event per fork of a step (never re-recorded while a wait on it may be pending)
     hipEvent_t ev_dw[N_DW_EV] = {}, ev_dw_done = nullptr;
     int dw_fork = 0;
+    // ---- the occlusion-loss branch (nero_stage1_occlusion) on a stream of the caller's: it reads x4 / sdf4 / normal / geo / inner_idx only,
+    // so it starts behind nero_sdf_alpha_fwd (ev_occ_in, recorded by the forward) and runs beside the material and light chains; the
+    // caller's stream waits for its end (ev_occ_out) in front of the loss.
+    hipEvent_t ev_occ_in = nullptr, ev_occ_out = nullptr;
+    // NERO_MAT_FORK=1 (three streams only): the three material predictors' forward launches go to s3, idle in the forward, behind the SDF
+    // forward -- they need feat and x8 only -- and are joined in front of nero_shade_encode, i.e. they run beside the first-order normal pass
+    bool mat_fork = false;
 };
 
 namespace {
@@ -257,11 +264,25 @@ int do_forward(nero_stage1* h, Arena& A, int R, int T, int n_in, int n_out, cons
     if (n_in > 0) {
         S.x4 = A.f32((size_t)rpi * 4);
         h->pe40 = A.f32((size_t)rpi * LD_PE);
+        h->x8 = A.f32((size_t)rpi * 8);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
         LAUNCH(nero_gather_inner(S.pts4, S.inner_idx, n_in, S.x4, h->pe40, stream));
+        if (!A.dry) hipLaunchKernelGGL(x8_from_x4_kernel, dim3((rpi + 255) / 256), dim3(256), 0, hs, S.x4, h->x8, n_in, rpi);
         // SDFField.forward_normal: value + feature, then the first-order reverse pass seeded by the sdf row of W_8 = the normal
         h->f_sdf = Fwd();
         RC(h->sdf_full.forward(A, M, h->pe40, LD_PE, h->pe40, LD_PE, n_in, true, h->f_sdf, stream));
+        S.feat = h->f_sdf.saves[8];
+        // the material predictors read feat and x8 only: beside the normal pass on the weight-gradient stream (mat_fork), else where they
+        // always were, behind nero_sdf_alpha_fwd.  No arena release between the fork and its join in front of nero_shade_encode.
+        const bool mat_fork = h->mat_fork && h->n_streams >= 3;
+        auto materials = [&](void* s) -> int {
+            for (int j = 0; j < 3; ++j) {
+                h->f_mat[j] = Fwd();
+                RC(h->mat[j].forward(A, M, S.feat, NERO_HID, h->x8, 8, n_in, true, h->f_mat[j], s));
+            }
+            return NERO_OK;
+        };
+        if (mat_fork) RC(materials((void*)fork_dw(h, A, hs)));
         float* ones = A.f32((size_t)rpi * 4);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
         if (!A.dry) hipLaunchKernelGGL(ones_col0_kernel, dim3((rpi + 255) / 256), dim3(256), 0, hs, ones, rpi);
@@ -273,22 +294,18 @@ int do_forward(nero_stage1* h, Arena& A, int R, int T, int n_in, int n_out, cons
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
         LAUNCH(nero_pe_vjp(S.x4, 4, h->b_normal.d_init, h->b_normal.ld_dinit, h->b_normal.d_aux, h->b_normal.ld_daux, N_FREQ, n_in, S.normal, 3, stream));
         S.sdf4 = h->f_sdf.heads[8];
-        S.feat = h->f_sdf.saves[8];
         float* alpha_i = A.f32(rpi);
         S.geo = A.f32((size_t)rpi * 8);
-        h->x8 = A.f32((size_t)rpi * 8);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
         LAUNCH(nero_sdf_alpha_fwd(S.sdf4, S.normal, S.x4, S.inner_idx, d, T, variance, anneal, n_in, alpha_i, S.geo, gerr, stream));
-        if (!A.dry) hipLaunchKernelGGL(x8_from_x4_kernel, dim3((rpi + 255) / 256), dim3(256), 0, hs, S.x4, h->x8, n_in, rpi);
-        for (int j = 0; j < 3; ++j) {
-            h->f_mat[j] = Fwd();
-            RC(h->mat[j].forward(A, M, S.feat, NERO_HID, h->x8, 8, n_in, true, h->f_mat[j], stream));
-        }
+        if (!A.dry && h->ev_occ_in) (void)hipEventRecord(h->ev_occ_in, hs);      // everything nero_stage1_occlusion reads exists from here on
+        if (!mat_fork) RC(materials(stream));
         h->mat8 = A.f32((size_t)rpi * 8);
         h->Xo2 = A.f32((size_t)2 * rpi * h->ld_outer);
         h->Xi = A.f32((size_t)rpi * 128);
         h->Xo = A.f32((size_t)rpi * 96);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
+        if (mat_fork) join_dw(h, A, hs);
         LAUNCH(nero_shade_encode(S.x4, S.geo, h->f_mat[0].heads[3], h->f_mat[1].heads[3], h->f_mat[2].heads[3], n_in, h->mat8, h->Xo2,
                                  h->Xo2 + (size_t)rpi * h->ld_outer, h->Xi, h->Xo, h->cfg.sphere_direction, stream));
         h->f_out = Fwd(); h->f_in = Fwd(); h->f_w = Fwd(); h->f_h = Fwd();
@@ -315,6 +332,38 @@ int do_forward(nero_stage1* h, Arena& A, int R, int T, int n_in, int n_out, cons
     if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
     if (!A.dry) join_side(h, so_, hs);                 // both branches have scattered their alpha / colour
     LAUNCH(nero_composite_fwd(h->alphaRT, h->colorRT, R, T, S.weights, rgb, stream));
+    return NERO_OK;
+}
+
+// ---- the occlusion-loss branch (nero_amd/stage1.py::ShapeStepGlue used to sequence it: nero_occ_candidates / _select / _gather, then
+// nero_amd/shape_step.py::secondary_occlusion) -- same entry points, same arguments, same order; every intermediate from the arena `A`
+int do_occlusion(nero_stage1* h, Arena& A, int n_in, const float* d, const float* variance, const float* keys, float thresh, int cap, int sn0,
+                 int sn1, int* cand, int* counts, float* occ, void* stream) {
+    const nero_stage1_state& S = h->st;
+    unsigned char* flag = static_cast<unsigned char*>(A.take((size_t)n_in));
+    const size_t sel_bytes = nero_occ_select_workspace(n_in);
+    void* sel_ws = A.take(sel_bytes);
+    float* pts = A.f32((size_t)cap * 3);
+    float* dirs = A.f32((size_t)cap * 3);
+    float* z = A.f32((size_t)cap * sn0);
+    float* pe = A.f32((size_t)rpad(cap * sn0) * LD_PE);
+    float* w = A.f32((size_t)cap * (sn0 - 1));
+    float* z_new = A.f32((size_t)cap * sn1);
+    float* pe_new = A.f32((size_t)rpad(cap * sn1) * LD_PE);
+    if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: workspace too small (nero_stage1_occlusion_workspace)");
+    LAUNCH(nero_occ_candidates(S.x4, S.sdf4, S.normal, S.inner_idx, d, S.T, thresh, n_in, flag, stream));
+    LAUNCH(nero_occ_select(flag, n_in, keys, cap, cand, counts, sel_ws, sel_bytes, stream));
+    LAUNCH(nero_occ_gather(S.x4, S.geo, cand, cap, pts, dirs, stream));
+    LAUNCH(nero_occ_z(pts, dirs, cap, sn0, z, stream));
+    LAUNCH(nero_ray_points_pe(pts, dirs, z, sn0, 0, sn0, cap, pe, stream));
+    float* s4 = nullptr;
+    RC(sdf_from_pe(h, A, pe, cap * sn0, s4, stream));
+    LAUNCH(nero_section_weights(z, s4, 4, sn0, variance, cap, w, nullptr, stream));
+    LAUNCH(nero_sample_pdf(z, sn0, w, sn0 - 1, sn0, sn1, cap, z_new, nullptr, stream));
+    LAUNCH(nero_ray_points_pe(pts, dirs, z_new, sn1, 0, sn1, cap, pe_new, stream));
+    float* s4b = nullptr;
+    RC(sdf_from_pe(h, A, pe_new, cap * sn1, s4b, stream));
+    LAUNCH(nero_section_weights(z_new, s4b, 4, sn1, variance, cap, nullptr, occ, stream));
     return NERO_OK;
 }
 
@@ -558,6 +607,12 @@ int nero_stage1_create(const nero_stage1_cfg* cfg, nero_stage1** out) {
             (void)hipGetLastError();             // (no device in reach -- the CPU-side size queries still work -- or out of handles: one stream)
             h->s2 = nullptr;
         }
+        if (h->s2 && (hipEventCreateWithFlags(&h->ev_occ_in, hipEventDisableTiming) != hipSuccess ||
+                      hipEventCreateWithFlags(&h->ev_occ_out, hipEventDisableTiming) != hipSuccess)) {
+            (void)hipGetLastError();             // (out of handles: nero_stage1_occlusion keeps to the caller's one stream)
+            if (h->ev_occ_in) (void)hipEventDestroy(h->ev_occ_in);
+            h->ev_occ_in = h->ev_occ_out = nullptr;
+        }
     }
     const bool have_device = h->s2 != nullptr || h->n_streams < 2;
     if (h->n_streams >= 3) {
@@ -573,6 +628,8 @@ int nero_stage1_create(const nero_stage1_cfg* cfg, nero_stage1** out) {
             if (have_device) h->n_streams = 2;
         }
     }
+    const char* mf = getenv("NERO_MAT_FORK");
+    h->mat_fork = mf && atoi(mf) != 0;
     *out = h;
     return NERO_OK;
 }
@@ -581,6 +638,8 @@ void nero_stage1_destroy(nero_stage1* h) {
     if (!h) return;
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    if (h->ev_occ_in) (void)hipEventDestroy(h->ev_occ_in);
+    if (h->ev_occ_out) (void)hipEventDestroy(h->ev_occ_out);
     if (h->s2) (void)hipStreamDestroy(h->s2);
     for (int i = 0; i < nero_stage1::N_DW_EV; ++i)
         if (h->ev_dw[i]) (void)hipEventDestroy(h->ev_dw[i]);
@@ -743,6 +802,49 @@ int nero_stage1_sdf_from_pe(nero_stage1* h, const float* pe, int n, float* out4,
     RC(sdf_from_pe(h, A, pe, n, res, stream));
     (void)hipMemcpyAsync(out4, res, (size_t)rpad(n) * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return nero_check_launch("nero_stage1_sdf_from_pe");
+}
+
+static bool occlusion_args_ok(const nero_stage1* h, int n_in, int cap, int sn0, int sn1) {
+    return h && n_in > 0 && cap >= 1 && cap <= 4096 && sn0 >= 2 && sn0 <= 160 && sn1 >= 1 && sn1 <= 32;
+}
+
+size_t nero_stage1_occlusion_workspace(nero_stage1* h, int n_in, int cap, int sn0, int sn1) {
+    if (!occlusion_args_ok(h, n_in, cap, sn0, sn1)) return 0;
+    nero_stage1 tmp = *h;                         // dry run on a copy: same carve logic, no memory, no launches
+    Arena A;
+    A.dry = true;
+    (void)do_occlusion(&tmp, A, n_in, nullptr, nullptr, nullptr, 0.f, cap, sn0, sn1, nullptr, nullptr, nullptr, nullptr);
+    return A.peak + 4096;
+}
+
+int nero_stage1_occlusion(nero_stage1* h, const float* d, const float* variance, const float* keys, float thresh, int cap, int sn0, int sn1,
+                          int* cand, int* counts, float* occ, void* ws, size_t ws_bytes, void* branch_stream, void* join_stream) {
+    if (!h || !h->packed || !h->A.base || !d || !variance || !keys || !cand || !counts || !occ || !ws)
+        return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: bad argument (no forward state)");
+    if (!occlusion_args_ok(h, h->st.n_in, cap, sn0, sn1))
+        return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: needs n_in > 0, 1 <= cap <= 4096, 2 <= sn0 <= 160, 1 <= sn1 <= 32");
+    if (wrong_device(h)) return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: the current device is not the one the handle was created on");
+    hipStream_t sb = (hipStream_t)branch_stream, sj = (hipStream_t)join_stream;
+    const bool side = sb != sj && h->n_streams >= 2 && h->s2 && h->ev_occ_in && h->ev_occ_out && !nero_prof_is_on();
+    if (sb != sj && !side) {
+        // one-stream order: what the caller queued on its branch stream (the key draw) goes in front, everything else on the join stream
+        if (!h->ev_occ_out || hipEventRecord(h->ev_occ_out, sb) != hipSuccess || hipStreamWaitEvent(sj, h->ev_occ_out, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(sb);
+        }
+        sb = sj;
+    }
+    if (side) (void)hipStreamWaitEvent(sb, h->ev_occ_in, 0);      // behind nero_sdf_alpha_fwd of the forward
+    Arena A;
+    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    int rc = do_occlusion(h, A, h->st.n_in, d, variance, keys, thresh, cap, sn0, sn1, cand, counts, occ, (void*)sb);
+    if (side) {                                                  // (on a failure too: nothing of the branch stays unordered behind the caller)
+        (void)hipEventRecord(h->ev_occ_out, sb);
+        (void)hipStreamWaitEvent(sj, h->ev_occ_out, 0);
+        if (rc != NERO_OK) { (void)hipStreamSynchronize(sb); (void)hipGetLastError(); }
+    }
+    RC(rc);
+    return nero_check_launch("nero_stage1_occlusion");
 }
 
 }  // extern "C"

@@ -56,6 +56,9 @@ _lib.nero_stage1_workspace_bytes_for.argtypes = [_fp, C.c_int, C.c_int, C.c_int,
 _lib.nero_stage1_pack_bytes.argtypes = [_fp]
 _lib.nero_stage1_get_state.argtypes = [_fp, C.POINTER(State)]
 _lib.nero_stage1_destroy.argtypes = [_fp]
+_lib.nero_stage1_occlusion_workspace.restype = C.c_size_t
+_lib.nero_stage1_occlusion_workspace.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int]
+_lib.nero_stage1_occlusion.argtypes = [_fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp]
 
 
 def supported(cfg=None, shader_cfg=None):
@@ -306,6 +309,8 @@ class ShapeStepGlue:
             self.G.lin[i].W, self.G.lin[i].b = dW.data_ptr(), db.data_ptr()
         self._keep = (grad_views, names)
         self._bufs = {}
+        self._side = None          # the stream of the occlusion-loss branch (key draw + nero_stage1_occlusion), created at its first use
+        self._keys = None          # the last step's keys, held until the next draw: the branch may read them on either stream
 
     @staticmethod
     def supported(net):
@@ -324,8 +329,9 @@ class ShapeStepGlue:
                 occ=torch.empty(n, **f32), d_rgb=torch.empty((R, 3), **f32), d_gerr=torch.empty(n, **f32), d_occ=torch.empty(n, **f32),
                 flag=torch.empty(n, dtype=torch.uint8, device=dev), cand=torch.empty(cap, **i32), counts=torch.zeros(2, **i32),
                 losses=torch.zeros(4, **f32), partials=torch.empty(_lib.nero_shape_loss_partials(R, n), **f32),
-                pts=torch.empty((cap, 3), **f32), dirs=torch.empty((cap, 3), **f32), dsum=torch.zeros(1, **f32),
-                sel_ws=torch.empty(_lib.nero_occ_select_workspace(n), dtype=torch.uint8, device=dev))
+                gt_occ=torch.empty(cap, **f32), dsum=torch.zeros(1, **f32),
+                # the occlusion branch's own scratch (worst case n_in = R*T): the step workspace is still being carved while it runs
+                occ_ws=torch.empty(_lib.nero_stage1_occlusion_workspace(self.drv.h, n, cap, 64, 16), dtype=torch.uint8, device=dev))
         return self._bufs[R]
 
     def forward_backward(self, o, d, gt, poses, step, variance_param, eik_weight, frozen, weights=None, rands=None):
@@ -334,7 +340,6 @@ class ShapeStepGlue:
         occ_keys [>= #candidates][, near, far]) to inject the random draws (tests).  Gradients land in the bucket views given at construction
         (the bucket must be zero on entry), d loss / d variance in variance_param.grad unless `frozen`.  -> dict(loss = device
         tensor [4]: total, rgb, eikonal, occlusion; n_in, n_out; occ_counts = device int32 [2] or None)."""
-        from .shape_step import secondary_occlusion
         net, drv = self.net, self.drv
         c = net.cfg
         R, T = o.shape[0], drv.T
@@ -348,6 +353,12 @@ class ShapeStepGlue:
             L.check(_lib.nero_near_far_sphere(_p(o), _p(d), R, _p(B['near']), _p(B['far']), st))
         var = variance_param.detach()
         nb = int(c['n_bg_samples'])
+        keys = None
+        if rands is not None and len(rands) > 2 and rands[2] is not None:
+            # injected keys: made ready here, in front of the forward on its stream, so that the branch finds them behind the forward's event
+            keys = rands[2].to(o.device).contiguous().float()
+            if keys.numel() < R * T:                      # occ_records_kernel reads keys[ordinal among the candidates], ordinal < n_in <= R*T
+                keys = torch.cat([keys, torch.full((R * T - keys.numel(),), float('inf'), dtype=torch.float32, device=o.device)])
         if c['perturb'] > 0:
             if rands is not None:
                 rand1, rand_bg = rands[0].contiguous(), rands[1].contiguous()
@@ -367,19 +378,21 @@ class ShapeStepGlue:
         occ_on = bool(c['apply_occ_loss']) and step >= c['occ_loss_step'] and n_in > 0
         cand = counts = gt_occ = None
         if occ_on:
-            s = drv.state()
-            rpi = row_pad(n_in)
-            x4, geo = drv._view(s.x4, (rpi, 4)), drv._view(s.geo, (rpi, 8))
-            L.check(_lib.nero_occ_candidates(s.x4, s.sdf4, s.normal, s.inner_idx, _p(d), T, float(c['occ_sdf_thresh']), n_in, _p(B['flag']), st))
-            keys = rands[2].to(o.device).contiguous() if (rands is not None and rands[2] is not None) else torch.rand(n_in, dtype=torch.float32, device=o.device)
             # RNG note: this path draws rand(n_in) keys every step >= occ_loss_step; the tensor glue draws rand(Pn) only when the
             # candidates exceed the cap, so NERO_STEP_GLUE=torch|hip runs are not seed-comparable from that step on.
-            if keys.numel() < n_in:                       # occ_records_kernel reads keys[ordinal among the candidates], ordinal < n_in
-                keys = torch.cat([keys, torch.full((n_in - keys.numel(),), float('inf'), dtype=torch.float32, device=o.device)])
-            cap = B['cand'].numel()
-            L.check(_lib.nero_occ_select(_p(B['flag']), n_in, _p(keys), cap, _p(B['cand']), _p(B['counts']), B['sel_ws'].data_ptr(), B['sel_ws'].numel(), st))
-            L.check(_lib.nero_occ_gather(_p(x4), _p(geo), _p(B['cand']), cap, _p(B['pts']), _p(B['dirs']), st))
-            gt_occ = secondary_occlusion(_KAdapter(drv), B['pts'], B['dirs'], var, 64, 16)
+            if self._side is None:
+                self._side = torch.cuda.Stream(o.device)
+            if keys is None:
+                # the draw goes to the branch's own stream: on the main one it would queue behind the whole forward and hold the branch
+                # back with it (the generator advances on the host: the same numbers, the same position in its sequence, on any stream)
+                with torch.cuda.stream(self._side):
+                    keys = torch.rand(n_in, dtype=torch.float32, device=o.device)
+            self._keys = keys
+            # candidates -> subset -> gather -> march, one call: beside the shading networks on the side stream, this one waits for its end
+            L.check(_lib.nero_stage1_occlusion(drv.h, _p(d), _p(var), _p(keys), float(c['occ_sdf_thresh']), B['cand'].numel(), 64, 16,
+                                               _p(B['cand']), _p(B['counts']), _p(B['gt_occ']), B['occ_ws'].data_ptr(), B['occ_ws'].numel(),
+                                               self._side.cuda_stream, st))
+            gt_occ = B['gt_occ']
             cand, counts = B['cand'], B['counts']
         if callable(weights):
             weights = weights(n_in, counts)
