@@ -2,11 +2,13 @@
 the product path -- if it is missing or fails to load, importing this module raises."""
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  -- must come first: libnero_hip.so has to bind to the HIP runtime torch already loaded
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERO_HIP_LIB') or os.path.join(_HERE, 'libnero_hip.so')     # (override: kernel-variant experiments)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip.h')
 
 MAX_LAYERS = 10
 HID = 256
@@ -83,13 +85,55 @@ class AdamJob(C.Structure):
 MAX_WN_JOBS, MAX_ADAM_JOBS = 40, 96
 
 
+_SCALARS = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
+
+
+def _ctype(decl, fn, ret=False):
+    """ctypes type of one parameter declaration (or return type) of `fn`: `const char*` is c_char_p, every other pointer -- device or
+    host, struct, handle or out-parameter -- travels as c_void_p (which takes None, data_ptr() integers, byref(), arrays and pointers)"""
+    if '*' in decl:
+        return C.c_char_p if re.fullmatch(r'const\s+char\s*\*(\s*\w+)?', decl) else C.c_void_p
+    words = [w for w in decl.split() if w != 'const']
+    ctype = ' '.join(words if ret or len(words) == 1 else words[:-1])       # a parameter's last word is its name
+    if ret and ctype == 'void':
+        return None
+    if ctype not in _SCALARS:
+        raise ImportError(f'nero_hip.h: {fn}: no ctypes type for {ctype!r} (in {decl!r})')
+    return _SCALARS[ctype]
+
+
+def parse_header(text):
+    """{function: (restype, argtypes)} for every prototype in `text`, the contents of include/nero_hip.h"""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*|^\s*#[^\n]*', ' ', text, flags=re.S | re.M)       # comments, preprocessor lines
+    sigs = {}
+    for ret, fn, params in re.findall(r'([\w\s*]+?)\b(nero_\w+)\s*\(([^()]*)\)\s*;', text):
+        params = [p.strip() for p in params.split(',') if p.strip() not in ('', 'void')]
+        sigs[fn] = (_ctype(ret.strip(), fn, ret=True), [_ctype(p, fn) for p in params])
+    names = set(re.findall(r'\b(nero_\w+)\s*\(', text))
+    if set(sigs) != names:
+        raise ImportError(f'nero_hip.h: {len(sigs)} prototypes parsed, {len(names)} functions named: {sorted(names ^ set(sigs))}')
+    return sigs
+
+
+def bind(lib):
+    """set restype and argtypes of EVERY entry point include/nero_hip.h declares on `lib` (a CDLL of libnero_hip.so): the header is the one
+    place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call site hands over"""
+    with open(HEADER_PATH) as f:
+        sigs = parse_header(f.read())
+    for fn, (restype, argtypes) in sigs.items():
+        try:
+            f = getattr(lib, fn)
+        except AttributeError:
+            raise ImportError(f'{getattr(lib, "_name", lib)} does not export {fn}, which nero_hip.h declares: rebuild the library') from None
+        f.restype, f.argtypes = restype, argtypes
+    return lib
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    lib = C.CDLL(LIB_PATH)
-    lib.nero_last_error.restype = C.c_char_p
-    return lib
+    return bind(C.CDLL(LIB_PATH))
 
 
 lib = _load()
@@ -106,14 +150,11 @@ class NeroOutOfMemory(NeroHipError, MemoryError):
 def check_workspace_fits(need_bytes, device, held_bytes=0, what='step workspace'):
     """raise NeroOutOfMemory -- with the byte counts -- BEFORE torch is asked for a workspace that cannot fit: free device memory + what torch's
     caching allocator holds without using + the caller's previous workspace (released for the new one) must cover it"""
-    import ctypes as C
-    import torch
     reusable = int(held_bytes)
     try:
         reusable += max(0, torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
     except Exception:                                  # noqa: BLE001 (no CUDA context yet)
         pass
-    lib.nero_check_device_memory.argtypes = [C.c_size_t, C.c_size_t, C.c_char_p]
     with torch.cuda.device(device):
         check(lib.nero_check_device_memory(int(need_bytes), reusable, what.encode()))
 

@@ -50,8 +50,6 @@ def f16_paired(mask=-1):
     """workgroup organisation of the f16x3 chain passes (include/nero_hip.h::nero_f16_paired): bit 0 / 1 / 2 = forward / tangent / reverse on
     the two-workgroups-per-CU kernels for launches of more than 4 tiles per CU, bit 3 = for launches of every size; mask < 0 only queries.
     Returns the previous mask.  Results are bit-identical in every setting (tests/test_paired_engine.py)."""
-    L.lib.nero_f16_paired.argtypes = [C.c_int]
-    L.lib.nero_f16_paired.restype = C.c_int
     return int(L.lib.nero_f16_paired(int(mask)))
 
 
@@ -59,8 +57,6 @@ def f16_rowowner(mask=-1):
     """forward chains that save nothing on the row-owner kernel (include/nero_hip.h::nero_f16_rowowner, mlp_f16r.hip): bit 0 = launches of at
     least 128 rows per CU, bit 1 = every launch; mask < 0 only queries.  Returns the previous mask.  Bit-identical results
     (tests/test_rowowner_engine.py)."""
-    L.lib.nero_f16_rowowner.argtypes = [C.c_int]
-    L.lib.nero_f16_rowowner.restype = C.c_int
     return int(L.lib.nero_f16_rowowner(int(mask)))
 
 
@@ -404,10 +400,8 @@ class Chain:
                 a_in = fwd['saves'][prev]
                 g['dWh'] = torch.empty((4, L.HID), dtype=torch.float32, device=self.device)
                 g['dbh'] = torch.empty(4, dtype=torch.float32, device=self.device)
-                L.check(L.lib.nero_head_dw(C.c_void_p(head_dys[i].data_ptr()), C.c_void_p(a_in.data_ptr()),
-                                           C.c_void_p(L.ptr(head_extra.get(i))), h.n_head, n_rows,
-                                           C.c_void_p(g['dWh'].data_ptr()), C.c_void_p(g['dbh'].data_ptr()),
-                                           C.c_void_p(workspace.data_ptr()), 0, st))
+                L.check(L.lib.nero_head_dw(head_dys[i].data_ptr(), a_in.data_ptr(), L.ptr(head_extra.get(i)), h.n_head, n_rows,
+                                           g['dWh'].data_ptr(), g['dbh'].data_ptr(), workspace.data_ptr(), 0, st))
                 g['dWh'] = g['dWh'][:h.n_head, :h.k]
                 g['dbh'] = g['dbh'][:h.n_head]
             if d is not None:
@@ -442,5 +436,5 @@ class Chain:
             out.append(g)
         if jobs:
             arr = (L.DwJob * len(jobs))(*jobs)
-            L.check(L.lib.nero_dw_gemm_batch(arr, len(jobs), n_rows, C.c_void_p(workspace.data_ptr()), st))
+            L.check(L.lib.nero_dw_gemm_batch(arr, len(jobs), n_rows, workspace.data_ptr(), st))
         return out

@@ -14,8 +14,6 @@ synthetic data (y up).  Row 0 is the pole el = +pi / 2 and the .hdr stores rows 
 One difference from the reference, on purpose: a direction exactly on the z axis -- the synthetic convention's pixel (row (h - 1) / 2, column
 3 (w - 1) / 4) when both are integers, e.g. (8, 24) of a 17 x 33 map -- is NaN in the reference (its IDE raises 0 to a complex power); here it
 is the finite limit of the encoding, what the neighbouring pixels converge to."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -23,10 +21,6 @@ from . import _lib as L
 from .chain import row_pad
 
 _lib = L.lib
-_lib.nero_env_encode.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_env_encode_dirs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-_lib.nero_env_finish.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
-_lib.nero_env_rgbe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
 
 DEFAULT_CHUNK = 1 << 16     # rows per encode / chain / finish round when chunk is None: 37 MB of encodings + 67 MB of chain activations
 MAX_SIZE = 16384

@@ -23,21 +23,7 @@ from .raytracing import RayTracer
 MISS_DISTANCE = 10.0                    # nero_bvh_trace reports a miss as depth 10
 
 _lib = L.lib
-_lib.nero_nn_dist_splits.argtypes = [C.c_int64, C.c_int64]
-_lib.nero_nn_dist_workspace_bytes.restype = C.c_size_t
-_lib.nero_nn_dist_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int]
-_lib.nero_nn_dist.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_voxel_downsample_workspace_bytes.restype = C.c_size_t
-_lib.nero_voxel_downsample_workspace_bytes.argtypes = [C.c_int64]
-_lib.nero_voxel_downsample.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
 _D9, _D12 = C.c_double * 9, C.c_double * 12
-_lib.nero_view_rays.argtypes = [_D9, _D12, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_view_points_workspace_bytes.restype = C.c_size_t
-_lib.nero_view_points_workspace_bytes.argtypes = [C.c_int, C.c_int]
-_lib.nero_view_points.argtypes = [C.c_void_p, _D9, _D12, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_int64, C.c_void_p, C.c_void_p]
-_lib.nero_depth_points.argtypes = [C.c_void_p, C.c_void_p, _D9, _D12, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64,
-                                   C.c_void_p, C.c_void_p]
 
 
 def _device(*tensors):

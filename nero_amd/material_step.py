@@ -2,7 +2,6 @@
 the Monte-Carlo shader (secondary rays through the BVH tracer, light MLPs on compacted hit / miss rows, microfacet estimator).
 Mirrors MCShadingNetwork.forward / shade_mixed / get_lights / material_regularization (network/field.py:856-1087) and
 NeROMaterialRenderer.shade / train_step (network/renderer.py:810-848)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,7 +10,7 @@ import torch
 from . import _lib as L
 from .chain import Chain, Dense, Head, row_pad
 from .fields import fibonacci_az_el
-from .shape_step import _p, _st, predictor_entries
+from .shape_step import _p, predictor_entries
 
 
 GEOMETRY_TYPES = {'schlick': 0, 'ggx_smith': 1}      # include/nero_hip.h nero_mc_combine_*: geometry_type
@@ -115,7 +114,7 @@ class PredictMaterials(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         x = x.contiguous()
         pe = torch.empty((rp, 56), **f32)
-        L.check(L.lib.nero_encode_pe(_p(x), x.stride(0), 3, 8, n, _p(pe), 56, _st()))
+        L.check(L.lib.nero_encode_pe(_p(x), x.stride(0), 3, 8, n, _p(pe), 56, L.stream_ptr()))
         x8 = torch.zeros((rp, 8), **f32)
         x8[:n, :3] = x
         ff = K.feats.forward(pe, pe, n)
@@ -171,7 +170,7 @@ class MCShade(torch.autograd.Function):
     @staticmethod
     def forward(ctx, K, tracer, names, gv, pts, view, normals, mat5, rand_d, rand_s, poses, *params):
         dev = pts.device
-        lib, st = L.lib, _st()
+        lib, st = L.lib, L.stream_ptr()
         f32 = dict(dtype=torch.float32, device=dev)
         cfg = K.cfg
         Pn = pts.shape[0]
@@ -245,7 +244,7 @@ class MCShade(torch.autograd.Function):
             inner_raw = fi['heads'][3]
         rgb, dl, sl, sp = (torch.empty((Pn, 3), **f32) for _ in range(4))
         L.check(lib.nero_mc_combine_fwd_h(_p(pt), _p(dirs), _p(depth), _p(slot), _p(outer_raw), _p(inner_raw), _p(human_raw), _p(hmask), n_hum,
-                                        C.c_float(cfg['light_exp_max']), C.c_float(cfg['inner_light_exp_max']), Pn, Dd, Ds,
+                                        cfg['light_exp_max'], cfg['inner_light_exp_max'], Pn, Dd, Ds,
                                         GEOMETRY_TYPES[cfg['geometry_type']], _p(rgb), _p(dl), _p(sl), _p(sp), st))
         ctx.S = dict(K=K, names=names, P=Pn, pt=pt, dirs=dirs, depth=depth, fnrm=fnrm, slot=slot, Xm=Xm, Xh=Xh, fo=fo, fi=fi,
                      fh=fh, Xhum=Xhum, hmask=hmask, poses=poses, gv=(gv or {}),
@@ -259,7 +258,7 @@ class MCShade(torch.autograd.Function):
         K, Pn = S['K'], S['P']
         cfg = K.cfg
         dev = d_rgb.device
-        lib, st = L.lib, _st()
+        lib, st = L.lib, L.stream_ptr()
         f32 = dict(dtype=torch.float32, device=dev)
         Dd, Ds = cfg['diffuse_sample_num'], cfg['specular_sample_num']
         n_miss, n_hit, n_hum = S['n_miss'], S['n_hit'], S['n_hum']
@@ -273,7 +272,7 @@ class MCShade(torch.autograd.Function):
         L.check(lib.nero_mc_combine_bwd_h(_p(S['pt']), _p(S['dirs']), _p(S['depth']), _p(S['slot']),
                                         _p(fo['heads'][3] if fo else None), _p(fi['heads'][3] if fi else None),
                                         _p(fh['heads'][3] if fh else None), _p(S['hmask']), n_hum,
-                                        C.c_float(cfg['light_exp_max']), C.c_float(cfg['inner_light_exp_max']), Pn, Dd, Ds,
+                                        cfg['light_exp_max'], cfg['inner_light_exp_max'], Pn, Dd, Ds,
                                         GEOMETRY_TYPES[cfg['geometry_type']], _p(d_rgb_c), _p(d_dl_c),
                                         _p(d_or), _p(d_ir), _p(d_hr), _p(d_mat5), _p(d_w), st))
         ws = torch.empty(L.lib.nero_dw_workspace_floats(max(n_miss, n_hit, 1)), **f32)

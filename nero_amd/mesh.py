@@ -27,36 +27,6 @@ from . import _lib as L
 
 _INT31 = 1 << 31
 
-L.lib.nero_mcubes_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mcubes_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-L.lib.nero_mcubes_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-L.lib.nero_mcubes_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                   C.c_int64, C.c_void_p]
-L.lib.nero_mesh_cc_label.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-L.lib.nero_mesh_cc_stats_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mesh_cc_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-L.lib.nero_mesh_cc_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
-L.lib.nero_mesh_compact_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mesh_compact_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-L.lib.nero_mesh_compact_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]
-L.lib.nero_mesh_compact_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                         C.c_int64, C.c_void_p, C.c_void_p]
-L.lib.nero_mesh_simplify_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mesh_simplify_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-L.lib.nero_mesh_simplify_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-L.lib.nero_mesh_simplify_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-L.lib.nero_mesh_face_adjacency_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mesh_face_adjacency_workspace_bytes.argtypes = [C.c_int64]
-L.lib.nero_mesh_face_adjacency.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-L.lib.nero_mesh_chart_label_workspace_bytes.restype = C.c_size_t
-L.lib.nero_mesh_chart_label_workspace_bytes.argtypes = [C.c_int64]
-L.lib.nero_mesh_chart_label.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6
-L.lib.nero_mesh_chart_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
-
 
 def workspace_bytes(shape):
     """device bytes nero_mcubes_count / _emit need beside the grid (< 6 bytes per grid point + 64 KiB)"""

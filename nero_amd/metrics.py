@@ -12,7 +12,6 @@ Here the images that NeROShapeRenderer.test_step / NeROMaterialRenderer.test_ste
   * ValidationEvaluator: the call contract of train/train_valid.py:18-52.
 SSIM follows this project's statement of skimage's algorithm (include/nero_hip.h); skimage is not a dependency.  PSNR is the exact value in
 float64: the reference's float32 mean is up to 2e-3 dB off it at 800 x 800."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -21,11 +20,6 @@ import torch
 from . import _lib as L
 
 _lib = L.lib
-_lib.nero_img_quantize.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-_lib.nero_img_metrics_workspace_bytes.restype = C.c_size_t
-_lib.nero_img_metrics_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
-_lib.nero_img_metrics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]
 
 WIN = 11                    # the SSIM window the reference passes to skimage
 MAX_SIZE, MAX_BATCH, MAX_CHANNELS = 16384, 65535, 4

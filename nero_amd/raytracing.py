@@ -60,14 +60,13 @@ class RayTracer:
             h = C.c_void_p()
             if self.build == 'device':
                 v, f = self._device_arrays()
-                L.lib.nero_bvh_build_workspace_bytes.restype = C.c_size_t
                 need = int(L.lib.nero_bvh_build_workspace_bytes(int(v.shape[0]), int(f.shape[0])))
                 if need == 0:
                     raise NotImplementedError(f'RayTracer(build="device"): no device build for {v.shape[0]} vertices, {f.shape[0]} triangles')
                 with torch.cuda.device(v.device):
                     ws = torch.empty(need, dtype=torch.uint8, device=v.device)
-                    L.check(L.lib.nero_bvh_create_device(C.c_void_p(v.data_ptr()), int(v.shape[0]), C.c_void_p(f.data_ptr()), int(f.shape[0]),
-                                                         C.c_void_p(ws.data_ptr()), C.c_size_t(need), L.stream_ptr(), C.byref(h)))
+                    L.check(L.lib.nero_bvh_create_device(v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]),
+                                                         ws.data_ptr(), need, L.stream_ptr(), C.byref(h)))
                     ws.record_stream(torch.cuda.current_stream())         # (the build's kernels may still be using it when it is released)
             else:
                 L.check(L.lib.nero_bvh_create(self._v.ctypes.data_as(C.c_void_p), self._v.shape[0], self._f.ctypes.data_as(C.c_void_p),
@@ -120,22 +119,18 @@ class RayTracer:
         if _chunks is not None:
             sp = None if _skip is None else (_skip.data_ptr() if torch.is_tensor(_skip) else int(_skip))
             arr = (C.c_int * len(_chunks))(*[int(c) for c in _chunks])
-            L.check(L.lib.nero_bvh_trace_ordered(self._handle(), C.c_void_p(rays_o.data_ptr()), C.c_void_p(rays_d.data_ptr()), n, C.c_void_p(sp), arr,
-                                                 len(_chunks), C.c_void_p(positions.data_ptr()), C.c_void_p(face_normals.data_ptr()),
-                                                 C.c_void_p(depth.data_ptr()), L.stream_ptr()))
+            L.check(L.lib.nero_bvh_trace_ordered(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n, sp, arr,
+                                                 len(_chunks), positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         elif _skip is not None:
             sp = _skip.data_ptr() if torch.is_tensor(_skip) else int(_skip)
             if torch.is_tensor(_skip):
                 assert _skip.dtype == torch.uint8 and _skip.is_cuda and _skip.numel() == n and _skip.is_contiguous()
-            L.check(L.lib.nero_bvh_trace_masked(self._handle(), C.c_void_p(rays_o.data_ptr()), C.c_void_p(rays_d.data_ptr()), n, C.c_void_p(sp),
-                                                C.c_void_p(positions.data_ptr()), C.c_void_p(face_normals.data_ptr()),
-                                                C.c_void_p(depth.data_ptr()), L.stream_ptr()))
+            L.check(L.lib.nero_bvh_trace_masked(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n, sp,
+                                                positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         elif _order is not None:
-            L.check(L.lib.nero_bvh_trace_grouped(self._handle(), C.c_void_p(rays_o.data_ptr()), C.c_void_p(rays_d.data_ptr()), n,
-                                                 C.c_void_p(positions.data_ptr()), C.c_void_p(face_normals.data_ptr()),
-                                                 C.c_void_p(depth.data_ptr()), _order[0], _order[1], L.stream_ptr()))
+            L.check(L.lib.nero_bvh_trace_grouped(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n,
+                                                 positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), _order[0], _order[1], L.stream_ptr()))
         else:
-            L.check(L.lib.nero_bvh_trace(self._handle(), C.c_void_p(rays_o.data_ptr()), C.c_void_p(rays_d.data_ptr()), n,
-                                         C.c_void_p(positions.data_ptr()), C.c_void_p(face_normals.data_ptr()),
-                                         C.c_void_p(depth.data_ptr()), L.stream_ptr()))
+            L.check(L.lib.nero_bvh_trace(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n,
+                                         positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         return positions.view(*prefix, 3), face_normals.view(*prefix, 3), depth.view(*prefix)

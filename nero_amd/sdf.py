@@ -49,7 +49,7 @@ def sdf_entries(eff):
 
 def encode_pe(x, n, dim, n_freq, ld):
     out = torch.empty((row_pad(n), ld), dtype=torch.float32, device=x.device)
-    L.check(L.lib.nero_encode_pe(C.c_void_p(x.data_ptr()), x.stride(0), dim, n_freq, n, C.c_void_p(out.data_ptr()), ld, L.stream_ptr()))
+    L.check(L.lib.nero_encode_pe(x.data_ptr(), x.stride(0), dim, n_freq, n, out.data_ptr(), ld, L.stream_ptr()))
     return out
 
 
@@ -76,8 +76,7 @@ class SDFField:
         R = o.shape[0]
         if self.default_pe:
             pe = torch.empty((row_pad(R * ncols), LD_PE), dtype=torch.float32, device=o.device)
-            L.check(L.lib.nero_ray_points_pe(C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(z.data_ptr()), z.stride(0), col0, ncols, R,
-                                             C.c_void_p(pe.data_ptr()), L.stream_ptr()))
+            L.check(L.lib.nero_ray_points_pe(o.data_ptr(), d.data_ptr(), z.data_ptr(), z.stride(0), col0, ncols, R, pe.data_ptr(), L.stream_ptr()))
             return pe
         pts = (o[:, None, :] + z[:, col0:col0 + ncols, None] * d[:, None, :]).reshape(R * ncols, 3).contiguous()
         return encode_pe(pts, R * ncols, 3, self.n_freq, self.ld_pe)
@@ -108,9 +107,8 @@ class SDFField:
             self._ones[:, 0] = 1.0
         nb = self.full.backward(fwd, n, dy=None, head_dys={last: self._ones}, need_dinit=True, need_daux=True, skip_last_dense=True)
         normal = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        L.check(L.lib.nero_pe_vjp(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(nb['d_init'].data_ptr()), nb['d_init'].stride(0),
-                                  C.c_void_p(nb['d_aux'].data_ptr()), nb['d_aux'].stride(0), self.n_freq, n,
-                                  C.c_void_p(normal.data_ptr()), 3, L.stream_ptr()))
+        L.check(L.lib.nero_pe_vjp(x.data_ptr(), x.stride(0), nb['d_init'].data_ptr(), nb['d_init'].stride(0),
+                                  nb['d_aux'].data_ptr(), nb['d_aux'].stride(0), self.n_freq, n, normal.data_ptr(), 3, L.stream_ptr()))
         return {'x': x, 'n': n, 'pe': pe, 'fwd': fwd, 'gbar': nb['deltas'], 'sdf4': fwd['heads'][last], 'feat': fwd['saves'][last],
                 'normal': normal}
 
@@ -125,8 +123,8 @@ class SDFField:
         injs, second, head_extra = {}, {}, {}
         if d_normal is not None:
             ehat = torch.empty((rp, LD_PE), dtype=torch.float32, device=self.device)
-            L.check(L.lib.nero_pe_jvp(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(d_normal.data_ptr()), d_normal.stride(0),
-                                      N_FREQ, n, C.c_void_p(ehat.data_ptr()), LD_PE, L.stream_ptr()))
+            L.check(L.lib.nero_pe_jvp(x.data_ptr(), x.stride(0), d_normal.data_ptr(), d_normal.stride(0),
+                                      N_FREQ, n, ehat.data_ptr(), LD_PE, L.stream_ptr()))
             tc = L.TanChain()
             tc.init, tc.ld_init, tc.k_init = ehat.data_ptr(), LD_PE, LD_PE
             tc.aux, tc.ld_aux, tc.k_aux = ehat.data_ptr(), LD_PE, LD_PE

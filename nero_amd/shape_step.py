@@ -2,7 +2,6 @@
 allocator, kernel sequencing, autograd glue).  Mirrors NeROShapeRenderer.sample_ray / render_core
 (network/renderer.py:403-443, 550-606) and AppShadingNetwork.forward (network/field.py:591-651); every arithmetic step
 is a call into libnero_hip.so (include/nero_hip.h).  See DESIGN.md §2 for the kernel sequence."""
-import ctypes as C
 import os
 
 import torch
@@ -11,15 +10,7 @@ from . import _lib as L
 from .chain import Chain, Dense, Head, row_pad
 from .sdf import SDFField
 
-P = C.c_void_p
-
-
-def _p(t):
-    return P(None if t is None else t.data_ptr())
-
-
-def _st():
-    return L.stream_ptr()
+_p = L.ptr
 
 
 def predictor_entries(eff, k_main0, k_aux0=0):
@@ -156,7 +147,7 @@ def sample_ray(K, cfg, o, d, near, far, variance, rand1=None, rand_bg=None, trac
     T = n_in + nb
     z = torch.empty((R, T), dtype=torch.float32, device=dev)
     tab = torch.empty((R, n_in), dtype=torch.float32, device=dev)
-    st = _st()
+    st = L.stream_ptr()
     lib = L.lib
     L.check(lib.nero_coarse_z(_p(near), _p(far), _p(rand1), R, ns, _p(z), T, st))
     pe = K.sdf.pe_of_rays(o, d, z, 0, ns)
@@ -173,7 +164,7 @@ def sample_ray(K, cfg, o, d, near, far, variance, rand1=None, rand_bg=None, trac
             index = torch.empty((R, n + m), dtype=torch.int32, device=dev)
             z_before = z[:, :n].clone()
             sdf_before = tab[:, :n].clone()
-        L.check(lib.nero_upsample(_p(o), _p(d), _p(z), T, _p(tab), n_in, n, _p(var_ptr), C.c_float(64.0 * 2 ** i), m, R,
+        L.check(lib.nero_upsample(_p(o), _p(d), _p(z), T, _p(tab), n_in, n, _p(var_ptr), 64.0 * 2 ** i, m, R,
                                   _p(z_new), _p(w_out), _p(inds), st))
         last = (i + 1 == up)
         if not last:
@@ -200,7 +191,7 @@ class RenderCore(torch.autograd.Function):
     def forward(ctx, meta, o, d, z_vals, variance, lut, poses, *params):
         dev = o.device
         lib = L.lib
-        st = _st()
+        st = L.stream_ptr()
         K = meta.get('K')                   # packed once per step by the caller (sampler and render share it)
         if K is None:
             K = ShapeKernels(unflatten_effective(meta['names'], [p.detach() for p in params]), meta['shader_cfg'], dev).pack()
@@ -240,7 +231,7 @@ class RenderCore(torch.autograd.Function):
             sctx = K.sdf.forward_normal(x4, n_in, pe40 if K.sdf.default_pe else None)     # (another sdf_freq: nero_encode_pe inside)
             alpha_i, geo = torch.empty(rpi, **f32), torch.empty((rpi, 8), **f32)
             L.check(lib.nero_sdf_alpha_fwd(_p(sctx['sdf4']), _p(sctx['normal']), _p(x4), _p(inner_idx), _p(d), T, _p(variance),
-                                           C.c_float(meta['anneal']), n_in, _p(alpha_i), _p(geo), _p(gerr), st))
+                                           meta['anneal'], n_in, _p(alpha_i), _p(geo), _p(gerr), st))
             x8 = torch.zeros((rpi, 8), **f32)
             x8[:, :3] = x4[:, :3]
             feat = sctx['feat']
@@ -266,7 +257,7 @@ class RenderCore(torch.autograd.Function):
             Lh = f_out['heads'][3]
             color_i = torch.empty((rpi, 3), **f32)
             L.check(lib.nero_shade_combine_fwd(_p(geo), _p(mat), _p(Lh[:rpi]), _p(Lh[rpi:]), _p(f_in['heads'][3]), _p(f_w['heads'][3]),
-                                               _p(lut), C.c_float(meta['exp_max']), n_in, _p(color_i), _p(occ_prob),
+                                               _p(lut), meta['exp_max'], n_in, _p(color_i), _p(occ_prob),
                                                _p(f_h['heads'][3] if f_h else None), _p(hmask), st))
             L.check(lib.nero_scatter_samples(_p(alpha_i), _p(color_i), _p(inner_idx), n_in, _p(alphaRT), _p(colorRT), st))
             S.update(x4=x4, x8=x8, sctx=sctx, geo=geo, mats=mats, mat=mat, Xo2=Xo2, Xi=Xi, Xo=Xo, f_out=f_out, f_in=f_in,
@@ -285,7 +276,7 @@ class RenderCore(torch.autograd.Function):
         K, R, T, n_in, n_out, meta = S['K'], S['R'], S['T'], S['n_in'], S['n_out'], S['meta']
         dev = S['o'].device
         lib = L.lib
-        st = _st()
+        st = L.stream_ptr()
         f32 = dict(dtype=torch.float32, device=dev)
         d_rgb = d_rgb.contiguous()
         d_aRT, d_cRT = torch.empty(R * T, **f32), torch.empty((R * T, 3), **f32)
@@ -342,7 +333,7 @@ class RenderCore(torch.autograd.Function):
             f_h = S['f_h']
             dLhum = torch.empty((rpi, 4), **f32) if f_h else None
             L.check(lib.nero_shade_combine_bwd(_p(geo), _p(mat), _p(Lh[:rpi]), _p(Lh[rpi:]), _p(f_in['heads'][3]), _p(f_w['heads'][3]),
-                                               _p(S['lut']), C.c_float(meta['exp_max']), n_in, _p(d_ci), _p(d_occ_c),
+                                               _p(S['lut']), meta['exp_max'], n_in, _p(d_ci), _p(d_occ_c),
                                                _p(dLh[:rpi]), _p(dLh[rpi:]), _p(dLi), _p(dLo), _p(dmat), _p(d_geo),
                                                _p(f_h['heads'][3] if f_h else None), _p(S['hmask']), _p(dLhum), st))
             n2 = rpi + n_in
@@ -377,7 +368,7 @@ class RenderCore(torch.autograd.Function):
             d_sdf4, d_grad, dinv = torch.empty((rpi, 4), **f32), torch.empty((rpi, 3), **f32), torch.empty(rpi, **f32)
             d_gerr_c = d_gerr.contiguous() if d_gerr is not None else None
             L.check(lib.nero_sdf_alpha_bwd(_p(S['sctx']['sdf4']), _p(S['sctx']['normal']), _p(S['x4']), _p(S['inner_idx']), _p(S['d']), T,
-                                           _p(S['variance']), C.c_float(meta['anneal']), n_in, _p(d_ai), _p(d_gerr_c), _p(d_geo),
+                                           _p(S['variance']), meta['anneal'], n_in, _p(d_ai), _p(d_gerr_c), _p(d_geo),
                                            _p(d_sdf4), _p(d_grad), _p(dinv), st))
             sg = K.sdf.backward(S['sctx'], d_sdf4, d_feat, d_grad, workspace=ws, outs=outs_of('sdf', range(K.sdf.last)))
             for l in range(K.sdf.n_lin):
@@ -443,7 +434,7 @@ def secondary_occlusion(K, o, dr, variance, sn0, sn1):
     """get_intersection (network/field.py:454-484) for points o [P,3] inside the unit sphere and unit directions dr [P,3]:
     sum of the sn1-1 section weights of the importance-resampled march = occlusion probability [P]"""
     dev = o.device
-    lib, st = L.lib, _st()
+    lib, st = L.lib, L.stream_ptr()
     f32 = dict(dtype=torch.float32, device=dev)
     Pn = o.shape[0]
     z = torch.empty((Pn, sn0), **f32)
@@ -468,7 +459,7 @@ def validation_info(K, cfg, shader_cfg, lut, variance, o, d, z_vals, weights, po
     """compute_validation_info (network/renderer.py:465-482): expected depth, normal map, shader intermediates at the depth point
     and the marched occlusion probability (sn0=128, sn1=9).  No grad."""
     dev = o.device
-    lib, st = L.lib, _st()
+    lib, st = L.lib, L.stream_ptr()
     f32 = dict(dtype=torch.float32, device=dev)
     R = o.shape[0]
     depth = torch.sum(weights * z_vals, -1, keepdim=True)
@@ -482,7 +473,7 @@ def validation_info(K, cfg, shader_cfg, lut, variance, o, d, z_vals, weights, po
     out = {'depth': depth, 'normal': ((torch.nn.functional.normalize(grad, dim=-1) + 1.0) * 0.5) * inner}
     idx = torch.arange(R, dtype=torch.int32, device=dev)            # sample k belongs to ray k (T = 1)
     alpha, geo, gerr = torch.empty(rp, **f32), torch.empty((rp, 8), **f32), torch.empty(rp, **f32)
-    L.check(lib.nero_sdf_alpha_fwd(_p(sctx['sdf4']), _p(grad), _p(x4), _p(idx), _p(d), 1, _p(variance), C.c_float(0.0), R,
+    L.check(lib.nero_sdf_alpha_fwd(_p(sctx['sdf4']), _p(grad), _p(x4), _p(idx), _p(d), 1, _p(variance), 0.0, R,
                                    _p(alpha), _p(geo), _p(gerr), st))
     x8 = torch.zeros((rp, 8), **f32)
     x8[:, :3] = x4[:, :3]
@@ -503,7 +494,7 @@ def validation_info(K, cfg, shader_cfg, lut, variance, o, d, z_vals, weights, po
         Lhum = K.human_light.forward(Xh, None, R, save=False)['heads'][3]
     rec = torch.empty((R, 32), **f32)
     L.check(lib.nero_shade_inter_results(_p(geo), _p(mat), _p(Lh2[:rp]), _p(Lh2[rp:]), _p(Li), _p(Lo), _p(lut),
-                                         C.c_float(shader_cfg['light_exp_max']), R, _p(Lhum), _p(hmask), _p(rec), st))
+                                         shader_cfg['light_exp_max'], R, _p(Lhum), _p(hmask), _p(rec), st))
     for k, a, b in INTER_KEYS:
         out[k] = rec[:, a:b] * inner
     if K.human:
@@ -527,7 +518,7 @@ class OccL1(torch.autograd.Function):
     def forward(ctx, occ_prob, cand, counts, gt):
         occ_prob, gt = occ_prob.contiguous(), gt.contiguous().reshape(-1)
         loss = torch.empty(1, dtype=torch.float32, device=occ_prob.device)
-        L.check(L.lib.nero_occ_l1(_p(occ_prob), _p(cand), _p(counts), _p(gt), cand.numel(), _p(loss), _st()))
+        L.check(L.lib.nero_occ_l1(_p(occ_prob), _p(cand), _p(counts), _p(gt), cand.numel(), _p(loss), L.stream_ptr()))
         ctx.save_for_backward(occ_prob, cand, counts, gt)
         return loss.reshape(())
 
@@ -536,7 +527,7 @@ class OccL1(torch.autograd.Function):
         occ_prob, cand, counts, gt = ctx.saved_tensors
         d = d_loss.contiguous().reshape(1).float()
         d_occ = torch.empty_like(occ_prob)
-        L.check(L.lib.nero_occ_l1_backward(_p(d), _p(occ_prob), _p(cand), _p(counts), _p(gt), cand.numel(), occ_prob.numel(), _p(d_occ), _st()))
+        L.check(L.lib.nero_occ_l1_backward(_p(d), _p(occ_prob), _p(cand), _p(counts), _p(gt), cand.numel(), occ_prob.numel(), _p(d_occ), L.stream_ptr()))
         return d_occ, None, None, None
 
 
@@ -545,12 +536,12 @@ def occ_loss(S, occ_prob, cfg, variance, occ_keys=None):
     (64 uniform + 16 importance z, no grad) -> L1(occ_prob, sum of section weights)."""
     K, n_in, T = S['K'], S['n_in'], S['T']
     dev = occ_prob.device
-    lib, st = L.lib, _st()
+    lib, st = L.lib, L.stream_ptr()
     f32 = dict(dtype=torch.float32, device=dev)
     flag = torch.empty(n_in, dtype=torch.uint8, device=dev)
     sctx = S['sctx']
     L.check(lib.nero_occ_candidates(_p(S['x4']), _p(sctx['sdf4']), _p(sctx['normal']), _p(S['inner_idx']), _p(S['d']), T,
-                                    C.c_float(cfg['occ_sdf_thresh']), n_in, _p(flag), st))
+                                    cfg['occ_sdf_thresh'], n_in, _p(flag), st))
     cap = int(cfg['occ_loss_max_pn'])
     if 1 <= cap <= 4096 and os.environ.get('NERO_OCC_DEVICE', '1') != '0':
         # round 6: the candidate subset chosen ON THE DEVICE (nero_occ_select: what the fused trainer's glue has done since round 4) -- no
@@ -563,9 +554,8 @@ def occ_loss(S, occ_prob, cfg, variance, occ_keys=None):
             keys = torch.cat([keys, torch.full((n_in - keys.numel(),), float('inf'), **f32)])
         cand = torch.empty(cap, dtype=torch.int32, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
-        lib.nero_occ_select_workspace.restype = C.c_size_t
         ws = torch.empty(lib.nero_occ_select_workspace(n_in), dtype=torch.uint8, device=dev)
-        L.check(lib.nero_occ_select(_p(flag), n_in, _p(keys), cap, _p(cand), _p(counts), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), st))
+        L.check(lib.nero_occ_select(_p(flag), n_in, _p(keys), cap, _p(cand), _p(counts), ws.data_ptr(), ws.numel(), st))
         pts, dirs = torch.empty((cap, 3), **f32), torch.empty((cap, 3), **f32)
         L.check(lib.nero_occ_gather(_p(S['x4']), _p(S['geo']), _p(cand), cap, _p(pts), _p(dirs), st))
         gt = secondary_occlusion(K, pts, dirs, variance, 64, 16)

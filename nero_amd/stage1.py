@@ -12,11 +12,10 @@ from . import _lib as L
 from .chain import GEMM_MODE, row_pad
 
 N_LIN = 49
-_fp = C.c_void_p
 
 
 class Linear(C.Structure):
-    _fields_ = [('W', _fp), ('b', _fp)]
+    _fields_ = [('W', C.c_void_p), ('b', C.c_void_p)]
 
 
 class Weights(C.Structure):
@@ -34,31 +33,12 @@ class Cfg(C.Structure):
 
 
 class State(C.Structure):
-    _fields_ = [('R', C.c_int), ('T', C.c_int), ('n_in', C.c_int), ('n_out', C.c_int), ('pts4', _fp), ('ray_counts', _fp), ('ray_off', _fp),
-                ('counts', _fp), ('inner_idx', _fp), ('outer_idx', _fp), ('x4', _fp), ('sdf4', _fp), ('feat', _fp), ('normal', _fp),
-                ('geo', _fp), ('weights', _fp)]
+    _fields_ = ([(n, C.c_int) for n in ('R', 'T', 'n_in', 'n_out')] +
+                [(n, C.c_void_p) for n in ('pts4', 'ray_counts', 'ray_off', 'counts', 'inner_idx', 'outer_idx', 'x4', 'sdf4', 'feat', 'normal',
+                                           'geo', 'weights')])
 
 
-_lib = L.lib
-_lib.nero_stage1_pack_bytes.restype = C.c_size_t
-_lib.nero_stage1_workspace_bytes.restype = C.c_size_t
-_lib.nero_stage1_workspace_bytes_for.restype = C.c_size_t
-_lib.nero_stage1_workspace_bytes_fwd.restype = C.c_size_t
-_lib.nero_stage1_destroy.restype = None
-_lib.nero_stage1_sample.argtypes = [_fp, C.c_int] + [_fp] * 8 + [_fp, C.c_size_t, _fp]
-_lib.nero_stage1_render_fwd.argtypes = [_fp, C.c_int] + [_fp] * 6 + [C.c_float] + [_fp] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_size_t, _fp]
-_lib.nero_stage1_render_bwd.argtypes = [_fp, _fp, _fp, _fp, C.POINTER(Grads), _fp, _fp]
-_lib.nero_stage1_sdf_from_pe.argtypes = [_fp, _fp, C.c_int, _fp, _fp, C.c_size_t, _fp]
-_lib.nero_stage1_pack.argtypes = [_fp, C.POINTER(Weights), _fp, _fp]
-_lib.nero_stage1_workspace_bytes.argtypes = [_fp, C.c_int]
-_lib.nero_stage1_workspace_bytes_fwd.argtypes = [_fp, C.c_int]
-_lib.nero_stage1_workspace_bytes_for.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int]
-_lib.nero_stage1_pack_bytes.argtypes = [_fp]
-_lib.nero_stage1_get_state.argtypes = [_fp, C.POINTER(State)]
-_lib.nero_stage1_destroy.argtypes = [_fp]
-_lib.nero_stage1_occlusion_workspace.restype = C.c_size_t
-_lib.nero_stage1_occlusion_workspace.argtypes = [_fp, C.c_int, C.c_int, C.c_int, C.c_int]
-_lib.nero_stage1_occlusion.argtypes = [_fp, _fp, _fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp]
+_lib, _p = L.lib, L.ptr
 
 
 def supported(cfg=None, shader_cfg=None):
@@ -77,10 +57,6 @@ def current_modes():
     return (GEMM_MODE['fwd'], GEMM_MODE['tan'], GEMM_MODE['bwd'], GEMM_MODE['dw'])
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 class Stage1Driver:
     """one NeROShapeRenderer configuration on the C-level driver.  pack(eff) once per optimisation step, then sample / render."""
 
@@ -92,7 +68,7 @@ class Stage1Driver:
         self.cfg = c
         self.modes = current_modes()                  # the engines this handle packs for (nero_amd.chain.GEMM_MODE at construction)
         self.T = cfg['n_samples'] + cfg['n_importance'] + cfg['n_bg_samples']
-        h = _fp()
+        h = C.c_void_p()
         L.check(_lib.nero_stage1_create(C.byref(c), C.byref(h)))
         self.h = h
         self.n_lin = 49 if c.human_light else 45
@@ -191,8 +167,7 @@ class _SdfAdapter:
         """PE-6 rows of the points o + z[:, col0 : col0 + ncols] d (the C driver exists for the YAML shapes only: stage1.supported)"""
         R = o.shape[0]
         pe = torch.empty((row_pad(R * ncols), 40), dtype=torch.float32, device=o.device)
-        P = C.c_void_p                                   # (no argtypes are declared for this entry point here: hand over real pointers)
-        L.check(_lib.nero_ray_points_pe(P(o.data_ptr()), P(d.data_ptr()), P(z.data_ptr()), z.stride(0), col0, ncols, R, P(pe.data_ptr()), L.stream_ptr()))
+        L.check(_lib.nero_ray_points_pe(_p(o), _p(d), _p(z), z.stride(0), col0, ncols, R, _p(pe), L.stream_ptr()))
         return pe
 
 
@@ -280,15 +255,6 @@ class RenderCoreC(torch.autograd.Function):
 
 
 # ---- the training glue between the driver calls (nero_amd/csrc/step_glue.hip) ---------------------------------------------------------
-_lib.nero_occ_select_workspace.restype = C.c_size_t
-_lib.nero_occ_select_workspace.argtypes = [C.c_int]
-_lib.nero_near_far_sphere.argtypes = [_fp, _fp, C.c_int, _fp, _fp, _fp]
-_lib.nero_occ_select.argtypes = [_fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]
-_lib.nero_occ_gather.argtypes = [_fp, _fp, _fp, C.c_int, _fp, _fp, _fp]
-_lib.nero_shape_loss_partials.argtypes = [C.c_int, C.c_int]
-_lib.nero_shape_loss.argtypes = [C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_float] + [_fp] * 11
-_lib.nero_var_grad.argtypes = [_fp, _fp, _fp, _fp]
-_lib.nero_occ_candidates.argtypes = [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp]
 RGB_LOSS_KIND = {'l2': 0, 'l1': 1, 'smooth_l1': 2, 'charbonier': 3}          # include/nero_hip.h NERO_RGB_*
 
 

@@ -14,7 +14,6 @@ from .fields import fibonacci_az_el
 from .stage1 import Linear, _p
 
 N_LIN = 32
-_fp = C.c_void_p
 
 
 class Weights(C.Structure):
@@ -28,21 +27,6 @@ class Cfg(C.Structure):
 
 
 _lib = L.lib
-_lib.nero_stage2_pack_bytes.restype = C.c_size_t
-_lib.nero_stage2_pack_bytes.argtypes = [_fp]
-_lib.nero_stage2_workspace_bytes.restype = C.c_size_t
-_lib.nero_stage2_workspace_bytes.argtypes = [_fp, C.c_int, C.c_int]
-_lib.nero_stage2_destroy.restype = None
-_lib.nero_stage2_destroy.argtypes = [_fp]
-_lib.nero_stage2_pack.argtypes = [_fp, C.POINTER(Weights), _fp, _fp]
-_lib.nero_stage2_predict_fwd.argtypes = [_fp, _fp, C.c_int, _fp, _fp, C.c_size_t, _fp]
-_lib.nero_stage2_rays.argtypes = [_fp, C.c_int] + [_fp] * 11
-_lib.nero_stage2_dead_rays.restype = C.c_void_p
-_lib.nero_stage2_counts.argtypes = [_fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-_lib.nero_stage2_dead_rays.argtypes = [_fp]
-_lib.nero_stage2_shade_fwd.argtypes = [_fp] + [_fp] * 8 + [C.POINTER(C.c_int), C.POINTER(C.c_int), _fp]
-_lib.nero_stage2_shade_bwd.argtypes = [_fp, _fp, _fp, C.POINTER(Weights), _fp, _fp]
-_lib.nero_stage2_predict_bwd.argtypes = [_fp, _fp, C.POINTER(Weights), _fp]
 
 GEOMETRY_TYPES = {'schlick': 0, 'ggx_smith': 1}
 
@@ -63,7 +47,7 @@ class Stage2Driver:
                 GEOMETRY_TYPES[shader_cfg['geometry_type']], float(shader_cfg['light_exp_max']), float(shader_cfg['inner_light_exp_max']),
                 GEMM_MODE['fwd'], GEMM_MODE['bwd'], GEMM_MODE['dw'])
         self.modes = (GEMM_MODE['fwd'], GEMM_MODE['bwd'], GEMM_MODE['dw'])
-        h = _fp()
+        h = C.c_void_p()
         L.check(_lib.nero_stage2_create(C.byref(c), C.byref(h)))
         self.h = h
         self.n_lin = 32 if c.human_lights else 28
@@ -228,14 +212,6 @@ class MCShadeC(torch.autograd.Function):
 class LossCfg(C.Structure):
     _fields_ = [('rgb_l1', C.c_int), ('reg_mat', C.c_int), ('reg_change', C.c_int), ('reg_lambda1', C.c_float), ('hinge_weight', C.c_float),
                 ('reg_diffuse', C.c_int), ('reg_diffuse_lambda', C.c_float)]
-
-
-_lib.nero_mat_reg_points.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp]
-_lib.nero_mat_head_fwd.argtypes = [C.c_int, _fp, _fp, _fp]
-_lib.nero_mat_head_bwd.argtypes = [C.c_int, _fp, _fp, _fp, _fp]
-_lib.nero_mat_loss_partials.argtypes = [C.c_int]
-_lib.nero_mat_loss_fwd.argtypes = [C.POINTER(LossCfg), C.c_int, C.c_int] + [_fp] * 8
-_lib.nero_mat_loss_bwd.argtypes = [C.POINTER(LossCfg), C.c_int, C.c_int] + [_fp] * 9
 
 
 def loss_cfg(renderer_cfg, shader_cfg, step, world=1):

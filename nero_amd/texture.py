@@ -13,7 +13,6 @@ step is a kernel of nero_amd/csrc/texture.hip or mesh_atlas.hip here:
   * simple_atlas: a dependency-free one-chart-per-triangle atlas for when no unwrapper is at hand; any (vt, ft) can be passed instead;
   * write_textured_obj / read_textured_obj: the reference's OBJ / MTL layout with lossless PNG maps.
 Conventions (include/nero_hip.h): maps are [h, w] row-major, texel (row y, column x) has its centre at u = (x + 0.5) / w, v = (y + 0.5) / h."""
-import ctypes as C
 import os
 import struct
 import zlib
@@ -24,28 +23,6 @@ import torch
 from . import _lib as L
 
 _lib = L.lib
-_lib.nero_uv_raster_workspace_bytes.restype = C.c_size_t
-_lib.nero_uv_raster_workspace_bytes.argtypes = [C.c_int64]
-_lib.nero_uv_raster.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_uv_overlap_count_workspace_bytes.restype = C.c_size_t
-_lib.nero_uv_overlap_count_workspace_bytes.argtypes = [C.c_int64, C.c_int, C.c_int]
-_lib.nero_uv_overlap_count.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_mesh_chart_corners_workspace_bytes.restype = C.c_size_t
-_lib.nero_mesh_chart_corners_workspace_bytes.argtypes = [C.c_int64]
-_lib.nero_mesh_chart_corners_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_mesh_chart_corners_emit.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-_lib.nero_mesh_chart_uv.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double,
-                                    C.c_int, C.c_void_p, C.c_void_p]
-_lib.nero_uv_interp_workspace_bytes.restype = C.c_size_t
-_lib.nero_uv_interp_workspace_bytes.argtypes = [C.c_int, C.c_int]
-_lib.nero_uv_interp.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_tex_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-_lib.nero_tex_regions_workspace_bytes.restype = C.c_size_t
-_lib.nero_tex_regions_workspace_bytes.argtypes = [C.c_int, C.c_int]
-_lib.nero_tex_regions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-_lib.nero_tex_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-_lib.nero_tex_downsample2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 
 
 def _dev(*tensors):

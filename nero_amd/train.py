@@ -61,9 +61,8 @@ class FusedOptimizer:
     parameter under torch (train/trainer.py:105-170 runs torch.optim.Adam)."""
 
     def __init__(self, lins, extra_plain, device, betas=(0.9, 0.999), eps=1e-8):
-        import ctypes as C
         from . import _lib as L
-        self.L, self.C, self.device = L, C, device
+        self.L, self.device = L, device
         self.betas, self.eps, self.t = betas, eps, 0
         f32 = dict(dtype=torch.float32, device=device)
         self.names, self.eff, leaves = [], [], []
@@ -126,7 +125,7 @@ class FusedOptimizer:
     def step(self, lr, world=1, absent=()):
         """all-reduce (mean) of the flat dL/dW_eff bucket, then weight-norm backward + Adam.  `absent`: parameters that received NO
         gradient this step (torch: .grad is None) -- skipped, their Adam step counters do not advance."""
-        L, C = self.L, self.C
+        L = self.L
         self.bucket.all_reduce_mean(world)
         self.t += 1
         skip = {id(p_) for p_ in absent}
@@ -136,8 +135,8 @@ class FusedOptimizer:
             else:
                 self._plain_steps[i] += 1
                 j.step = self._plain_steps[i]
-        L.check(L.lib.nero_wn_adam_batch(self._wn_jobs, len(self._wn), self._plain_jobs, len(self._plain), C.c_float(lr),
-                                         C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.t, L.stream_ptr()))
+        L.check(L.lib.nero_wn_adam_batch(self._wn_jobs, len(self._wn), self._plain_jobs, len(self._plain), lr,
+                                         self.betas[0], self.betas[1], self.eps, self.t, L.stream_ptr()))
         self._after_step()
 
     def _after_step(self):

@@ -19,9 +19,8 @@ NEW_SYMBOLS = ('nero_bvh_build_workspace_bytes', 'nero_bvh_build_lds_capacity', 
 def _lib():
     import __graft_entry__ as ge
     ge.build()
-    lib = ctypes.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so'))
-    lib.nero_bvh_build_workspace_bytes.restype = ctypes.c_size_t
-    return lib
+    from nero_amd import _lib as L
+    return L.bind(ctypes.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so')))
 
 
 def test_shape_of_the_tree_for_every_size():

@@ -14,7 +14,6 @@ pytestmark = pytest.mark.gpu
 
 def _lib():
     from nero_amd import _lib as L
-    L.lib.nero_bvh_build_workspace_bytes.restype = C.c_size_t
     return L
 
 

@@ -240,25 +240,24 @@ def test_workspace_sizes_hold_their_scratch_or_refuse():
     import ctypes as C
     import __graft_entry__ as ge
     ge.build()
-    lib = C.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so'))
-    lib.nero_last_error.restype = C.c_char_p
+    from nero_amd import _lib as L
+    lib = L.bind(C.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so')))
     a = lambda nbytes: (nbytes + 255) // 256 * 256
     V, T, n, nt, px, grid = 1000, 2000, 1000, 2000, 8 * 8, 9 ** 3
     tiles = (grid + 2047) // 2048
-    cases = [    # entry point, argument types, arguments, bytes of the arrays
-        ('nero_mesh_compact_workspace_bytes', [C.c_int64] * 2, (V, T), 256 + 2 * a(4 * (V + 1)) + 2 * a(4 * (T + 1))),
-        ('nero_mesh_cc_stats_workspace_bytes', [C.c_int64] * 2, (V, T), 3 * a(4 * (V + 1)) + 4 * a(4 * T) + a(8 * (T // 2048 + V + 1))),
-        ('nero_mesh_chart_label_workspace_bytes', [C.c_int64], (T,), 2 * a(4 * (T + 1))),
-        ('nero_mesh_chart_corners_workspace_bytes', [C.c_int64], (T,), 256 + 2 * a(8 * 3 * T) + 2 * a(4 * 3 * T) + 2 * a(4 * (3 * T + 1))),
-        ('nero_voxel_downsample_workspace_bytes', [C.c_int64], (n,), 256 + a(1024 * 6 * 4) + a(8 * (n + 1)) + a(8 * n) + a(4 * (n + 1)) + a(4 * n)),
-        ('nero_view_points_workspace_bytes', [C.c_int] * 2, (8, 8), 2 * a(4 * (px + 1))),
-        ('nero_uv_raster_workspace_bytes', [C.c_int64], (nt,), 256 + 2 * a(8 * (nt + 1))),
-        ('nero_mcubes_workspace_bytes', [C.c_int] * 3, (9, 9, 9), 256 + a(grid) + a(4 * grid) + 4 * a(8 * (tiles + 1))),
+    cases = [    # entry point, arguments, bytes of the arrays
+        ('nero_mesh_compact_workspace_bytes', (V, T), 256 + 2 * a(4 * (V + 1)) + 2 * a(4 * (T + 1))),
+        ('nero_mesh_cc_stats_workspace_bytes', (V, T), 3 * a(4 * (V + 1)) + 4 * a(4 * T) + a(8 * (T // 2048 + V + 1))),
+        ('nero_mesh_chart_label_workspace_bytes', (T,), 2 * a(4 * (T + 1))),
+        ('nero_mesh_chart_corners_workspace_bytes', (T,), 256 + 2 * a(8 * 3 * T) + 2 * a(4 * 3 * T) + 2 * a(4 * (3 * T + 1))),
+        ('nero_voxel_downsample_workspace_bytes', (n,), 256 + a(1024 * 6 * 4) + a(8 * (n + 1)) + a(8 * n) + a(4 * (n + 1)) + a(4 * n)),
+        ('nero_view_points_workspace_bytes', (8, 8), 2 * a(4 * (px + 1))),
+        ('nero_uv_raster_workspace_bytes', (nt,), 256 + 2 * a(8 * (nt + 1))),
+        ('nero_mcubes_workspace_bytes', (9, 9, 9), 256 + a(grid) + a(4 * grid) + 4 * a(8 * (tiles + 1))),
     ]
-    assert cases[0][3] == 24832
-    for name, argtypes, args, arrays in cases:
+    assert cases[0][2] == 24832
+    for name, args, arrays in cases:
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = C.c_size_t, argtypes
         got = int(fn(*args))
         err = lib.nero_last_error()
         print(name, args, 'arrays', arrays, 'got', got, err)

@@ -62,8 +62,6 @@ class Guarded:
 def cabi_atlas(v, f, size, gutter, vt_cap=None):
     """every entry point of the atlas through ctypes with guarded outputs -> dict of host arrays (rc of the emit under 'emit_rc')"""
     from nero_amd import _lib as L
-    from nero_amd import mesh as M                                   # (declares the argument types)
-    from nero_amd import texture as TX
     lib = L.lib
     vd, fd = _dev(v, f)
     V, T = vd.shape[0], fd.shape[0]
@@ -222,7 +220,7 @@ def test_the_smallest_shapes(name):
 
 def test_refused_sizes_and_null_pointers():
     from nero_amd import _lib as L
-    from nero_amd import mesh as M, texture as TX                    # noqa: F401 (declare the argument types)
+    from nero_amd import texture as TX
     lib = L.lib
     s = L.stream_ptr()
     one = torch.zeros(64, dtype=torch.int32, device='cuda')
@@ -265,7 +263,6 @@ def test_a_capacity_that_is_too_small_writes_nothing():
     o = cabi_atlas(v, f, 128, GUTTER, vt_cap=len(r['vt']) - 1)
     assert o['n_vt'] == len(r['vt']) and o['emit_rc'] == ERR_ARG
     from nero_amd import _lib as L
-    L.lib.nero_last_error.restype = C.c_char_p
     assert b'capacity' in L.lib.nero_last_error()
     for k in ('ft', 'vt_vertex', 'vt_chart'):
         assert o['guards'][k].untouched(), k

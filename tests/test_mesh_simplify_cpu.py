@@ -174,16 +174,8 @@ def test_cell_table():
 def _lib():
     import __graft_entry__ as ge
     ge.build()
-    lib = C.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so'))
-    lib.nero_last_error.restype = C.c_char_p
-    lib.nero_mesh_simplify_workspace_bytes.restype = C.c_size_t
-    lib.nero_mesh_simplify_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.nero_mesh_simplify_count.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-    lib.nero_mesh_simplify_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-    return lib
+    from nero_amd import _lib as L
+    return L.bind(C.CDLL(os.path.join(ROOT, 'nero_amd', 'libnero_hip.so')))
 
 
 def test_symbols_exist_and_are_declared():
