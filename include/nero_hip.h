@@ -35,8 +35,7 @@ enum { NERO_ACT_NONE = 0, NERO_ACT_RELU = 1, NERO_ACT_SOFTPLUS100 = 2 };
 /* F16X3: operands as two fp16 planes h = fp16(xs), l = fp16(xs - h) of their block-scaled value xs (per activation row / per weight
  * matrix, exact powers of two that put the block maximum into [2^14, 2^15), the top of fp16's range), three plane products
  * hw hx + hw lx + lw hx accumulated into ONE fp32 accumulator set -- half the MFMA count of BF16X6 at the same error class
- * (representation error <= 2^-24 of the block maximum, dropped term <= 2^-24 of the product).  (Rounds 1-4 scaled into [0.5, 1),
- * stored l * 2^11 and kept two accumulator sets; -DF16_TWO_ACC rebuilds that format.) */
+ * (representation error <= 2^-24 of the block maximum, dropped term <= 2^-24 of the product; the format of rounds 1-4: docs/experiments.md). */
 /* (value 3 was NERO_GEMM_F16X3P, the two-workgroups-per-CU forward engine of rounds 2-3, removed in round 4 for a wrong partial sum in one
  * launch of three at size.  Round 5 found the mechanism -- packed fp32 beside another wave's MFMAs, DESIGN.md 9.3 -- and the kernels are
  * back as an execution detail of F16X3, nero_f16_paired below: not a mode, the value 3 stays refused.) */

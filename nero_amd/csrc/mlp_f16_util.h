@@ -27,8 +27,8 @@ constexpr float BETA = 100.0f;
 constexpr int SA = 528;                 // bytes per row of a main plane: 256 fp16 + 16 B pad
 constexpr int PLANE_A = 64 * SA;
 constexpr int SX_N = 112, SX_W = 208;   // aux plane row strides (48 / 96 columns + 16 B)
-constexpr float LO = 2048.f, LO_INV = 1.f / 2048.f;
-// Round 5 -- ONE accumulator set (default; -DF16_TWO_ACC restores the H / L pair of rounds 1-4).  The block scale puts an operand's
+// ONE accumulator set (round 5; rounds 1-4 kept an H / L pair: docs/experiments.md, "Retired compile-time switches").  The block scale puts
+// an operand's
 // largest magnitude into [2^14, 2^15), the TOP of fp16's range, instead of [0.5, 1): the remainder l = fp16(xs - h) is then an ordinary
 // fp16 number at its TRUE scale (|l| <= 2^3 for the largest elements, normal down to 2^-14, i.e. for every element within 2^-17 of the
 // row maximum; below that its absolute error 2^-25 is 2^-40 of the maximum) -- no 2^11 pre-scale -- and the three plane products
@@ -36,29 +36,19 @@ constexpr float LO = 2048.f, LO_INV = 1.f / 2048.f;
 // round 2, mlp_f16dw.hip).  Same three MFMAs per k-step; what goes away is the second accumulator set (32 VGPRs per wave), the
 // H + 2^-11 L combine (32 VALU per lane and layer), the 2^11 multiply of every split (32 more) and half of the skip-layer rescale.
 // Products reach 2^30, a 256-term sum 2^38: far inside fp32.  Error against fp64: tests/test_mlp_engine.py (unchanged tolerances).
-#ifdef F16_TWO_ACC
-constexpr int F16_TOP = 0;
-#define ACCV(aH, aL, r, v) fmaf((aL)[r][v], LO_INV, (aH)[r][v])
-#else
 constexpr int F16_TOP = 15;
-#define ACCV(aH, aL, r, v) ((aH)[r][v])
-#endif
 constexpr int HDR_BYTES = 256;          // packed-image header: float[0] = 2^ew (the factor results are multiplied by), uint[1] = max bits
 constexpr int SCR_LD = 36, SCR_BYTES = 32 * SCR_LD * 4;
 
 // row-major workspace stores (saved activations, deltas, tangents: 1 KB per row and layer, written once, read by a LATER kernel)
 // carry the non-temporal policy so that they do not displace the weight images -- re-read by every tile -- from the XCD's L2:
-// -3.3 % on the whole training step (forward -2 %, reverse -4 %, tangent -4 %; -DNERO_PLAIN_STORES restores the default policy).
+// -3.3 % on the whole training step (forward -2 %, reverse -4 %, tangent -4 %; docs/experiments.md).
 // The mirror image on the read side (nt loads / nt LDS-DMA of those workspaces in the consumer kernels) LOSES 0.5-0.9 ms per step:
 // much of what a pass wrote is still in the MALL when the next pass asks for it.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_ws4(float* dst, float4 v) {
-#ifdef NERO_PLAIN_STORES
-    *reinterpret_cast<float4*>(dst) = v;
-#else
     f32x4_t t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t*>(dst));
-#endif
 }
 
 constexpr int SCRP_ROWS = 16;
@@ -124,11 +114,7 @@ __device__ __forceinline__ unsigned pk_f16(float a, float b) {       // v_cvt_pk
 __device__ __forceinline__ void split2h(float a, float b, unsigned& h, unsigned& l) {     // a, b already block-scaled
     h = pk_f16(a, b);
     const f16x2 hh = __builtin_bit_cast(f16x2, h);
-#ifdef F16_TWO_ACC
-    l = pk_f16((a - (float)hh[0]) * LO, (b - (float)hh[1]) * LO);
-#else
     l = pk_f16(a - (float)hh[0], b - (float)hh[1]);
-#endif
 }
 __device__ __forceinline__ void store_planes4h(char* dst, int plane_bytes, float4 v) {
     unsigned h0, l0, h1, l1;
@@ -143,21 +129,16 @@ __device__ __forceinline__ float4 load_planes4h(const char* src, int plane_bytes
     const f16x2 a0 = __builtin_bit_cast(f16x2, a.x), a1 = __builtin_bit_cast(f16x2, a.y);
     const f16x2 b0 = __builtin_bit_cast(f16x2, b.x), b1 = __builtin_bit_cast(f16x2, b.y);
     float4 v;
-#ifdef F16_TWO_ACC
-    v.x = fmaf((float)b0[0], LO_INV, (float)a0[0]);
-    v.y = fmaf((float)b0[1], LO_INV, (float)a0[1]);
-    v.z = fmaf((float)b1[0], LO_INV, (float)a1[0]);
-    v.w = fmaf((float)b1[1], LO_INV, (float)a1[1]);
-#else
     v.x = (float)a0[0] + (float)b0[0];
     v.y = (float)a0[1] + (float)b0[1];
     v.z = (float)a1[0] + (float)b1[0];
     v.w = (float)a1[1] + (float)b1[1];
-#endif
     return v;
 }
 
-// ---- activations (identical to mlp_split.hip) ---------------------------------------------------------------------------
+// ---- activations ---------------------------------------------------------------------------------------------------------
+// (NOT the code of mlp_split.hip / mlp_engine.hip: their softplus takes __expf / __logf with a log1p series for small arguments;
+//  softplus100_grad_from_out is the same formula as theirs, on exp2)
 // softplus(beta = 100) on the hardware exp2 / log2 units (v_exp_f32 / v_log_f32, ~1 ulp each, no range fix-ups needed here:
 // the exp2 argument is <= 0 and the log2 argument lies in [1, 2]):   max(x, 0) + ln(1 + exp(-|100 x|)) / 100.
 // Absolute error <= 1e-9 (the rounding of 1 + t), i.e. far below one fp32 ulp of the row maximum every value is block-scaled
@@ -223,26 +204,20 @@ constexpr int LDS_SMALL_BYTES = (64 + 64 + 512 + 32) * 4;      // rs_main[64] rs
 #define PIN_P(x) asm volatile("" : : "s"(x))
 __device__ __forceinline__ nero_fwd_layer load_layer(const nero_fwd_chain& ch, int l) {
     nero_fwd_layer L = ch.layer[l];
-#ifndef NERO_NO_PIN
     PIN_P(L.w_main); PIN_P(L.w_aux); PIN_P(L.bias); PIN_P(L.save); PIN_P(L.head_w); PIN_P(L.head_b); PIN_P(L.head_out);
     PIN_S(L.k_main); PIN_S(L.k_aux); PIN_S(L.n_tiles); PIN_S(L.n_head); PIN_S(L.act); PIN_S(L.head_k); PIN_P(L.relu_mask);
-#endif
     return L;
 }
 __device__ __forceinline__ nero_tan_layer load_layer(const nero_tan_chain& ch, int l) {
     nero_tan_layer L = ch.layer[l];
-#ifndef NERO_NO_PIN
     PIN_P(L.w_main); PIN_P(L.w_aux); PIN_P(L.a_saved); PIN_P(L.gbar); PIN_P(L.adot); PIN_P(L.inj);
     PIN_S(L.k_main); PIN_S(L.k_aux); PIN_S(L.n_tiles);
-#endif
     return L;
 }
 __device__ __forceinline__ nero_bwd_layer load_layer(const nero_bwd_chain& ch, int l) {
     nero_bwd_layer L = ch.layer[l];
-#ifndef NERO_NO_PIN
     PIN_P(L.w_main_t); PIN_P(L.w_aux_t); PIN_P(L.a_prev); PIN_P(L.inj); PIN_P(L.delta_prev); PIN_P(L.head_w); PIN_P(L.head_dy);
     PIN_S(L.n_out); PIN_S(L.k_main_tiles); PIN_S(L.k_aux_tiles); PIN_S(L.n_head); PIN_S(L.act_prev); PIN_P(L.mask_prev); PIN_P(L.inj_adot);
-#endif
     return L;
 }
 // request the scale of every packed image of the chain (uniform addresses; branch-free: a missing image reads the chain's first one) ...
@@ -278,15 +253,12 @@ __device__ __forceinline__ void wsc_commit(float* wsc, const WscRegs& r, int tid
 }
 
 // ---- GEMM core ------------------------------------------------------------------------------------------------------------
-// accH[r] += wh xh,  accL[r] += wh xl + wl xh  over `n` k-steps of 16 (r = 32-row half).  Weight planes three steps ahead in a
+// aH[r] += wl xh + wh xl + wh xh  over `n` k-steps of 16 (r = 32-row half).  Weight planes three steps ahead in a
 // ring of four register sets (L2 stream), activation planes one step ahead in a double buffer (LDS).
 struct WF { uint4 wh, wl; };
 struct XF { uint4 xh0, xl0, xh1, xl1; };
 
 __device__ __forceinline__ void load_w(WF& o, const uint4* wp, int c) {
-#ifdef F16_NO_WSTREAM                               // (timing experiments, scripts/f16_variants.sh: every k-step re-reads step 0)
-    c = 0;
-#endif
     const uint4* w = wp + (size_t)c * 128;
     o.wh = w[0];
     o.wl = w[64];
@@ -301,72 +273,32 @@ __device__ __forceinline__ void load_x(XF& o, const char* xp, int half_bytes, in
 }
 #define NERO_MFH(ACC, A, B) \
     ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, B), ACC, 0, 0, 0)
-// GEMM_SETPRIO (experiment, round 6): 1 = a wave raises its issue priority for the six MFMAs of a k-step and drops it for the operand
-// requests of the next one (the two waves of a SIMD would then alternate k-steps instead of one running ahead and the other finishing
-// alone at the lone-wave rate); 2 = the second wave of every SIMD (waves 4-7) holds priority 1 through the whole GEMM.
-#ifndef GEMM_SETPRIO
-#define GEMM_SETPRIO 0
-#endif
-__device__ __forceinline__ void ops_compute(f32x16 (&aH)[2], f32x16 (&aL)[2], const WF& w, const XF& x) {
-#if GEMM_SETPRIO == 1
-    __builtin_amdgcn_s_setprio(1);
-#endif
-#ifdef F16_NO_MFMA
-    aH[0][0] += __uint_as_float(w.wh.x ^ x.xh0.x); aL[0][0] += __uint_as_float(w.wl.x ^ x.xl0.x);
-    aH[1][0] += __uint_as_float(w.wh.y ^ x.xh1.x); aL[1][0] += __uint_as_float(w.wl.y ^ x.xl1.x);
-    return;
-#endif
-#ifdef F16_TWO_ACC
-    NERO_MFH(aL[0], w.wl, x.xh0); NERO_MFH(aL[1], w.wl, x.xh1);
-    NERO_MFH(aH[0], w.wh, x.xh0); NERO_MFH(aH[1], w.wh, x.xh1);
-    NERO_MFH(aL[0], w.wh, x.xl0); NERO_MFH(aL[1], w.wh, x.xl1);
-#else
+__device__ __forceinline__ void ops_compute(f32x16 (&aH)[2], const WF& w, const XF& x) {
     // (the two small products first: they enter an accumulator that still holds little; dependent MFMAs on one accumulator issue back
     //  to back at full rate -- accumulation forwarding, measured for the weight-gradient kernel in round 2)
     NERO_MFH(aH[0], w.wl, x.xh0); NERO_MFH(aH[1], w.wl, x.xh1);
     NERO_MFH(aH[0], w.wh, x.xl0); NERO_MFH(aH[1], w.wh, x.xl1);
     NERO_MFH(aH[0], w.wh, x.xh0); NERO_MFH(aH[1], w.wh, x.xh1);
-    (void)aL;
-#endif
-#if GEMM_SETPRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#endif
 }
 #define NERO_FENCE() __builtin_amdgcn_sched_barrier(0)      // (without the fences hipcc sinks the prefetches: the kernels run 40 % slower)
 // One k-step = 2 weight loads (VMEM) + 4 activation-fragment reads (DS) for a LATER step + 6 MFMAs of this step.  Issued as
 // [6 loads][6 MFMAs] the wave spends the load-issue time with an idle matrix pipe and the MFMA time with idle issue slots (an in-order
-// wave: a lone wave reaches 46 % of the pipe rate in the loop, two per SIMD 70 %, profiles/r03_phase_probes.txt).  -DGEMM_SGB interleaves
-// them -- MFMA, DS, MFMA, DS, ..., MFMA, VMEM, MFMA, VMEM (checked in the ISA) -- so that each load would issue in the shadow of the
-// preceding MFMA.  MEASURED SLOWER (round 3, same file): the GEMM phase of a layer-tile goes from 8.6 k to 9.4 k cycles (forward),
-// 4.7 k to 6.0 k (reverse), 17.6 k to 19.4 k (two workgroups per CU) -- a load between two MFMAs costs the pipe more than its issue
-// slot.  Kept as an experiment switch, off.
-#ifdef GEMM_SGB
-#define NERO_KSTEP_SCHED() do { \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); \
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); } while (0)
-#define NERO_MID_FENCE()
-#else
-#define NERO_KSTEP_SCHED()
-#define NERO_MID_FENCE() NERO_FENCE()
-#endif
+// wave: a lone wave reaches 46 % of the pipe rate in the loop, two per SIMD 70 %, profiles/r03_phase_probes.txt).  The loads are NOT
+// interleaved with the MFMAs (MFMA, DS, MFMA, DS, ..., MFMA, VMEM): measured slower in round 3 -- the GEMM phase of a layer-tile went from
+// 8.6 k to 9.4 k cycles (forward), 4.7 k to 6.0 k (reverse), 17.6 k to 19.4 k (two workgroups per CU): a load between two MFMAs costs the
+// pipe more than its issue slot (same file; docs/experiments.md).  Hence the fence between the requests and the MFMAs of every k-step.
 
 // The first three weight fragments of a GEMM can be requested by the CALLER ahead of time (`pre`: wa, wb, wc already hold -- or are about
 // to receive -- steps 0, 1, 2; see prefetch_w): a layer's first MFMA then waits for an LDS read instead of an L2 round trip behind
 // the barrier that ends the previous layer (~900 cycles per layer-tile).
-#ifndef F16_PW_N
-#define F16_PW_N 3                                   // fragments requested ahead by the caller (the rest at the start of the GEMM)
-#endif
+constexpr int F16_PW_N = 3;                          // fragments requested ahead by the caller (the rest at the start of the GEMM)
 __device__ __forceinline__ void prefetch_w(WF& wa, WF& wb, WF& wc, const uint4* wp, int n, int from = 0) {
     const int last = n - 1;
     if (from <= 0) load_w(wa, wp, 0);
     if (from <= 1) load_w(wb, wp, 1 < last ? 1 : last);
     if (from <= 2) load_w(wc, wp, 2 < last ? 2 : last);
 }
-__device__ __forceinline__ void gemm_f16x3_loop(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
+__device__ __forceinline__ void gemm_f16x3_loop(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes,
                                            int plane_bytes, int n, bool pre, WF& wa, WF& wb, WF& wc) {
     if (n <= 0) return;
     WF wd;
@@ -377,34 +309,34 @@ __device__ __forceinline__ void gemm_f16x3_loop(f32x16 (&aH)[2], f32x16 (&aL)[2]
     load_x(xa, xp, half_bytes, plane_bytes, 0);
     NERO_FENCE();
     for (int c = 0; c < n; c += 4) {
-        load_w(wd, wp, NERO_CL(c + 3)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 1)); NERO_MID_FENCE();
-        ops_compute(aH, aL, wa, xa); NERO_KSTEP_SCHED(); NERO_FENCE();
+        load_w(wd, wp, NERO_CL(c + 3)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 1)); NERO_FENCE();
+        ops_compute(aH, wa, xa); NERO_FENCE();
         if (c + 1 < n) {
-            load_w(wa, wp, NERO_CL(c + 4)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_MID_FENCE();
-            ops_compute(aH, aL, wb, xb); NERO_KSTEP_SCHED(); NERO_FENCE();
+            load_w(wa, wp, NERO_CL(c + 4)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_FENCE();
+            ops_compute(aH, wb, xb); NERO_FENCE();
         }
         if (c + 2 < n) {
-            load_w(wb, wp, NERO_CL(c + 5)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_MID_FENCE();
-            ops_compute(aH, aL, wc, xa); NERO_KSTEP_SCHED(); NERO_FENCE();
+            load_w(wb, wp, NERO_CL(c + 5)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_FENCE();
+            ops_compute(aH, wc, xa); NERO_FENCE();
         }
         if (c + 3 < n) {
-            load_w(wc, wp, NERO_CL(c + 6)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_MID_FENCE();
-            ops_compute(aH, aL, wd, xb); NERO_KSTEP_SCHED(); NERO_FENCE();
+            load_w(wc, wp, NERO_CL(c + 6)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_FENCE();
+            ops_compute(aH, wd, xb); NERO_FENCE();
         }
     }
 #undef NERO_CL
 }
-__device__ __forceinline__ void gemm_f16x3_loop(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
-                                           int plane_bytes, int n) {
+// the same without fragments requested ahead by the caller
+__device__ __forceinline__ void gemm_f16x3(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes, int plane_bytes, int n) {
     WF wa, wb, wc;
-    gemm_f16x3_loop(aH, aL, wp, xp, half_bytes, plane_bytes, n, false, wa, wb, wc);
+    gemm_f16x3_loop(aH, wp, xp, half_bytes, plane_bytes, n, false, wa, wb, wc);
 }
 
 
 // lean k-loop for the kernels that run FOUR waves per SIMD (<= 128 registers per wave; mlp_f16p.hip, NW = 8): weights two steps ahead in a
 // ring of three register sets, fragments one step ahead -- 56 operand registers instead of 64 + 32; the other three waves of the SIMD cover
 // what the shallower ring no longer does.  Same products in the same order as gemm_f16x3_loop.
-__device__ __forceinline__ void gemm_f16x3_lean(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
+__device__ __forceinline__ void gemm_f16x3_lean(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes,
                                                 int plane_bytes, int n) {
     if (n <= 0) return;
     WF w0, w1, w2;
@@ -417,12 +349,12 @@ __device__ __forceinline__ void gemm_f16x3_lean(f32x16 (&aH)[2], f32x16 (&aL)[2]
     NERO_FENCE();
     for (int c = 0; c < n; c += 6) {
         load_w(w2, wp, NERO_CL(c + 2)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 1)); NERO_FENCE();
-        ops_compute(aH, aL, w0, xa); NERO_FENCE();
-        if (c + 1 < n) { load_w(w0, wp, NERO_CL(c + 3)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_FENCE(); ops_compute(aH, aL, w1, xb); NERO_FENCE(); }
-        if (c + 2 < n) { load_w(w1, wp, NERO_CL(c + 4)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_FENCE(); ops_compute(aH, aL, w2, xa); NERO_FENCE(); }
-        if (c + 3 < n) { load_w(w2, wp, NERO_CL(c + 5)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_FENCE(); ops_compute(aH, aL, w0, xb); NERO_FENCE(); }
-        if (c + 4 < n) { load_w(w0, wp, NERO_CL(c + 6)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 5)); NERO_FENCE(); ops_compute(aH, aL, w1, xa); NERO_FENCE(); }
-        if (c + 5 < n) { load_w(w1, wp, NERO_CL(c + 7)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 6)); NERO_FENCE(); ops_compute(aH, aL, w2, xb); NERO_FENCE(); }
+        ops_compute(aH, w0, xa); NERO_FENCE();
+        if (c + 1 < n) { load_w(w0, wp, NERO_CL(c + 3)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_FENCE(); ops_compute(aH, w1, xb); NERO_FENCE(); }
+        if (c + 2 < n) { load_w(w1, wp, NERO_CL(c + 4)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_FENCE(); ops_compute(aH, w2, xa); NERO_FENCE(); }
+        if (c + 3 < n) { load_w(w2, wp, NERO_CL(c + 5)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_FENCE(); ops_compute(aH, w0, xb); NERO_FENCE(); }
+        if (c + 4 < n) { load_w(w0, wp, NERO_CL(c + 6)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 5)); NERO_FENCE(); ops_compute(aH, w1, xa); NERO_FENCE(); }
+        if (c + 5 < n) { load_w(w1, wp, NERO_CL(c + 7)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 6)); NERO_FENCE(); ops_compute(aH, w2, xb); NERO_FENCE(); }
     }
 #undef NERO_CL
 }
@@ -438,18 +370,18 @@ __device__ __forceinline__ void load_w2(WF2& o, const uint4* wp0, const uint4* w
     load_w(o.a, wp0, c);
     load_w(o.b, wp1, c);
 }
-__device__ __forceinline__ void ops_compute2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const WF2& w, const XF& x) {
-    ops_compute(aH0, aL0, w.a, x);
-    ops_compute(aH1, aL1, w.b, x);
+__device__ __forceinline__ void ops_compute2(f32x16 (&aH0)[2], f32x16 (&aH1)[2], const WF2& w, const XF& x) {
+    ops_compute(aH0, w.a, x);
+    ops_compute(aH1, w.b, x);
 }
-__device__ __forceinline__ void gemm_f16x3_dual(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const uint4* wp0,
+__device__ __forceinline__ void gemm_f16x3_dual(f32x16 (&aH0)[2], f32x16 (&aH1)[2], const uint4* wp0,
                                                 const uint4* wp1, const char* xp, int half_bytes, int plane_bytes, int n) {
     if (n <= 0) return;
     WF2 w0, w1, w2;
     XF xa, xb;
     const int last = n - 1;
 #define NERO_CL(c) ((c) < last ? (c) : last)
-#define NERO_K2(W, X) NERO_MID_FENCE(); ops_compute2(aH0, aL0, aH1, aL1, W, X); NERO_FENCE()
+#define NERO_K2(W, X) NERO_FENCE(); ops_compute2(aH0, aH1, W, X); NERO_FENCE()
     load_w2(w0, wp0, wp1, 0);
     load_w2(w1, wp0, wp1, NERO_CL(1));
     load_x(xa, xp, half_bytes, plane_bytes, 0);
@@ -472,19 +404,13 @@ template <int V> struct IC { static constexpr int value = V; };
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(IC<I>{}); static_for<I + 1, N>(f); }
 }
-#ifndef GEMM_XD
-#define GEMM_XD 1
-#endif
-#ifndef GEMM_WD
-#define GEMM_WD 3
-#endif
 // `hook(IC<c>)` runs in every step behind that step's operand requests: the caller issues its own global loads at the step after
 // which the GEMM requests no more weights (c = N - WD: vmcnt retires in order, a load issued earlier would hold the weight stream back,
 // one issued later has less of the GEMM left to hide behind).
 template <int N, class F>
-__device__ __forceinline__ void gemm_f16x3_fixed_hook(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
+__device__ __forceinline__ void gemm_f16x3_fixed_hook(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes,
                                                       int plane_bytes, F&& hook) {
-    constexpr int XD = GEMM_XD, XN = XD + 1, WD = GEMM_WD, WN = WD + 1;
+    constexpr int XD = 1, XN = XD + 1, WD = 3, WN = WD + 1;
     WF w[WN];
     XF x[XN];
     static_for<0, WD>([&](auto c) { if (c.value < N) load_w(w[c.value], wp, c.value); });
@@ -495,24 +421,15 @@ __device__ __forceinline__ void gemm_f16x3_fixed_hook(f32x16 (&aH)[2], f32x16 (&
         if (c + WD < N) load_w(w[(c + WD) % WN], wp, c + WD);
         if (c + XD < N) load_x(x[(c + XD) % XN], xp, half_bytes, plane_bytes, c + XD);
         hook(cc);
-        NERO_MID_FENCE();
-        ops_compute(aH, aL, w[c % WN], x[c % XN]);
-        if (c + WD < N && c + XD < N) NERO_KSTEP_SCHED();
+        NERO_FENCE();
+        ops_compute(aH, w[c % WN], x[c % XN]);
         NERO_FENCE();
     });
 }
 template <int N>
-__device__ __forceinline__ void gemm_f16x3_fixed(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
+__device__ __forceinline__ void gemm_f16x3_fixed(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes,
                                                  int plane_bytes) {
-    gemm_f16x3_fixed_hook<N>(aH, aL, wp, xp, half_bytes, plane_bytes, [](auto) {});
-}
-
-__device__ __forceinline__ void gemm_f16x3(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const char* xp, int half_bytes,
-                                           int plane_bytes, int n) {
-#ifdef GEMM_ASSUME16                                   // (timing experiments on all-256-wide chains only: wrong for any other K)
-    gemm_f16x3_fixed<16>(aH, aL, wp, xp, half_bytes, plane_bytes); return;
-#endif
-    gemm_f16x3_loop(aH, aL, wp, xp, half_bytes, plane_bytes, n);
+    gemm_f16x3_fixed_hook<N>(aH, wp, xp, half_bytes, plane_bytes, [](auto) {});
 }
 
 __device__ __forceinline__ void zero2(f32x16 (&acc)[2]) {
@@ -522,17 +439,30 @@ __device__ __forceinline__ void zero2(f32x16 (&acc)[2]) {
         for (int v = 0; v < 16; ++v) acc[r][v] = 0.f;
 }
 
+// bias + activation of one accumulator set in the unit U -> val, and the row maxima of the result (forward epilogue of both organisations)
+template <int ACT>
+__device__ __forceinline__ void fwd_values(const f32x16 (&aH)[2], const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4],
+                                           float (&m)[2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        m[r] = 0.f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float4 v;
+            v.x = act_fwd<ACT>(fmaf(aH[r][4 * g], U[r], bq[g].x));
+            v.y = act_fwd<ACT>(fmaf(aH[r][4 * g + 1], U[r], bq[g].y));
+            v.z = act_fwd<ACT>(fmaf(aH[r][4 * g + 2], U[r], bq[g].z));
+            v.w = act_fwd<ACT>(fmaf(aH[r][4 * g + 3], U[r], bq[g].w));
+            val[r][g] = v;
+            m[r] = fmaxf(m[r], amax4(v));
+        }
+    }
+}
+
 // ---- lane exchanges without the LDS (round 6) ---------------------------------------------------------------------------------
 // __shfl_xor compiles to ds_bpermute_b32 + a bounds select + s_waitcnt lgkmcnt: an LDS round trip (~100+ cycles, and lgkmcnt is shared
 // with the scalar loads) per exchange, several of them on the critical path of every layer epilogue.  gfx950 has the exchange of the two
 // 32-lane halves as ONE VALU instruction (v_permlane32_swap) and the exchanges inside a row of 16 as DPP modifiers.
-#ifdef NERO_SHFL_LDS                                   // (experiment switch: the round-5 code)
-__device__ __forceinline__ float max_xor32(float m) { return fmaxf(m, __shfl_xor(m, 32)); }
-__device__ __forceinline__ unsigned other_half(unsigned v, int h) { (void)h; return __shfl_xor(v, 32); }
-__device__ __forceinline__ float max_8lanes(float m) { m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); return fmaxf(m, __shfl_xor(m, 4)); }
-__device__ __forceinline__ float max_4lanes(float m) { m = fmaxf(m, __shfl_xor(m, 1)); return fmaxf(m, __shfl_xor(m, 2)); }
-__device__ __forceinline__ float sum_8lanes(float s) { s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); return s + __shfl_xor(s, 4); }
-#else
 // v_permlane32_swap vdst, src0: vdst[32..63] <-> src0[0..31].  With both operands = v: r[0] = v's lower half in both halves, r[1] = its
 // upper half in both halves.
 __device__ __forceinline__ float max_xor32(float m) {
@@ -552,7 +482,6 @@ __device__ __forceinline__ float max_4lanes(float m) { m = fmaxf(m, dpp_f32<0xB1
 __device__ __forceinline__ float max_8lanes(float m) { m = max_4lanes(m); return fmaxf(m, dpp_f32<0x141>(m)); }
 // (same bits as the shuffle butterfly: every step adds the partner's partial sum to the lane's own, and fp32 addition commutes)
 __device__ __forceinline__ float sum_8lanes(float s) { s += dpp_f32<0xB1>(s); s += dpp_f32<0x4E>(s); return s + dpp_f32<0x141>(s); }
-#endif
 
 // row maxima of this wave's 64x32 block (two rows per lane) -> rmax[row][wave]
 __device__ __forceinline__ void publish_rowmax(float* rmax, float m0, float m1, int wave, int i, int h) {

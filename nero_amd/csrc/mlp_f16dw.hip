@@ -72,9 +72,7 @@ __device__ __forceinline__ void split_true(float a, float b, unsigned& h, unsign
 // needs 4x the wave instructions and the texture-address path, ~38 cycles of issue per instruction beside 8 waves, was the
 // pole of the first version).  The buffer resource is rebased to the chunk's first row (SALU); rows past the slice end and
 // column quads past the matrix width fall outside num_records and read as 0; a ragged last quad is masked by multiplies.
-#ifndef DW_LOAD_AUX
-#define DW_LOAD_AUX 2                                // nt: both operand streams (0.6 GB per job) are read once; -4.5 % on the dW kernels
-#endif
+constexpr int DW_LOAD_AUX = 2;                       // nt: both operand streams (0.6 GB per job) are read once; -4.5 % on the dW kernels
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void dwh_fetch(f32x4 (&v)[4], const float* __restrict__ src, int ld, int r0, int r1, int off) {
     const int left = r1 - r0;
@@ -124,9 +122,7 @@ __device__ __forceinline__ void split_shift(int s, int& a, int& b) {
     b = b > 29 ? 29 : b;
 }
 
-#ifndef DW_SGB_V
-#define DW_SGB_V 4
-#endif
+constexpr int DW_SGB_V = 4;                          // VALU instructions between two MFMAs of the wide kernel's product block
 // (Round 4, measured and dropped: staging through LDS-DMA.  global_load_lds_dwordx4 into a raw fp32 stage of 2 x 32 KB beside the planes, a
 // chunk requested TWO iterations before its maxima are taken -- no registers while in flight, 233 instead of 248 VGPRs -- on the theory that
 // the loop waits for loads it requested only one iteration earlier.  It does not: bit-identical results, 0.177 -> 0.194 ms per 298 k-row
@@ -188,11 +184,7 @@ __device__ __forceinline__ void dw_f16_body(const nero_dw_job& job, int n_rows, 
     for (int b = 0; b < 4; ++b) fb_off[b] = h * 4096 + dwh_entry(32 * (kt0 + b) + i) * 16;
     auto fetch = [&](f32x4 (&v)[4], int q) {
         const bool second = q >= nch;
-#ifdef DW_NOSTREAM                                       // (timing experiment: every chunk re-reads the slice's first rows, L2 hits)
-        const int r0 = r_begin;
-#else
         const int r0 = r_begin + (second ? q - nch : q) * 16;
-#endif
         dwh_fetch(v, second ? src1 : src0, second ? ld1 : ld0, r0, r_end, second ? off1 : off0);
     };
     // mask the ragged quad, publish this wave's maximum of the chunk part held in v -> smax[slot][wave]
@@ -300,7 +292,7 @@ __device__ __forceinline__ void dw_f16_body(const nero_dw_job& job, int n_rows, 
 #pragma unroll
                 for (int a = 0; a < NA; ++a) mf3(acc[a][b], fa[a], fb[b]);
             DPH(3);
-#if DW_SGB_V > 0 && !defined(DW_PHASE_TIMING)
+#ifndef DW_PHASE_TIMING
 #pragma unroll
             for (int k = 0; k < 24; ++k) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // one MFMA

@@ -18,7 +18,7 @@
 // epilogue, barrier and HBM wait: the per-phase shader-clock profile (scripts/phase_timing.py, profiles/r02_phase_timing.txt)
 // shows 57 % of a forward layer inside the GEMM loop and 30-45 % of a reverse layer, the rest serial.  Here a workgroup is
 // 256 threads = 4 waves that still own 64 rows; wave w computes the feature tiles w and w + 4 (same packed operand images, same per-row
-// scaling, same results bit for bit) -- in ONE walk over the k-steps where both exist (P_DUAL_TILE below: the activation fragments of the
+// scaling, same results bit for bit) -- in ONE walk over the k-steps where both exist (gemm_tile2: the activation fragments of the
 // second tile are those of the first, so a k-step reads them once for twelve MFMAs), one after the other otherwise.  LDS per workgroup drops to 79.4 KB -- the aux operand
 // (skip / direction inputs, <= 96 columns) is converted from global memory inside its k-steps instead of living in LDS, the
 // store-transposition scratch covers 16 rows at a time -- so two workgroups share a CU and one's epilogue, barriers and HBM
@@ -36,13 +36,6 @@ namespace {
 // NW = waves per workgroup.  4 (round 2 / 5): wave w computes the feature tiles w and w + 4, 256 registers per wave,
 // two waves per SIMD.  8 (round 6): wave w computes tile w only, at most 128 registers per wave, FOUR waves per SIMD from two workgroups --
 // the occupancy at which scripts/probe/rowowner_probe.hip measures today's layer structure 13 % faster than with one workgroup per CU.
-// reverse kernel: the saved activations of a wave's first / second feature tile are requested in front of (true) or behind (false) its GEMM
-#ifndef P_PA_EARLY_A
-#define P_PA_EARLY_A true
-#endif
-#ifndef P_PA_EARLY_B
-#define P_PA_EARLY_B true
-#endif
 
 struct LdsP { char* actp; float* rs_main; float* rs_aux; float* rmax; float* wsc; char* scr; };
 __device__ __forceinline__ LdsP carve_p(char* smem) {
@@ -55,13 +48,7 @@ __device__ __forceinline__ LdsP carve_p(char* smem) {
     l.scr = reinterpret_cast<char*>(l.wsc + 32);
     return l;
 }
-#ifndef NERO_F16_PW_DEFAULT
-#define NERO_F16_PW_DEFAULT 4
-#endif
-#ifndef P_LDS_EXTRA
-#define P_LDS_EXTRA 0                                   // (timing experiment: > 2560 forces ONE workgroup per CU)
-#endif
-inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + 4 * SCRP_BYTES + P_LDS_EXTRA; }      // 79488 (NW = 8: 8 x 8-row scratch, the same)
+inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + 4 * SCRP_BYTES; }      // 79488 (NW = 8: 8 x 8-row scratch, the same)
 
 // the per-lane addresses of the chain's OUTPUTS (d_init, d_aux: written once, by the first layer) are formed from a row index the compiler
 // cannot see through: otherwise it hoists them out of the layer loop and they occupy registers -- or scratch -- through every GEMM
@@ -129,7 +116,7 @@ __device__ __forceinline__ void raw_to_x(XF& x, const RawX& r, float inv0, float
     split8(x.xh0, x.xl0, r.a0, r.a1, inv0);
     split8(x.xh1, x.xl1, r.b0, r.b1, inv1);
 }
-__device__ __forceinline__ void gemm_aux_global(f32x16 (&aH)[2], f32x16 (&aL)[2], const uint4* wp, const float* __restrict__ aux, int ld,
+__device__ __forceinline__ void gemm_aux_global(f32x16 (&aH)[2], const uint4* wp, const float* __restrict__ aux, int ld,
                                                 int k, int n, const Ctx& c, float inv0, float inv1) {
     if (n <= 0) return;
     int g0 = c.row0 + c.i, g1 = c.row0 + 32 + c.i;
@@ -146,20 +133,20 @@ __device__ __forceinline__ void gemm_aux_global(f32x16 (&aH)[2], f32x16 (&aL)[2]
         if (s + 1 < n) { load_w(wb, wp, s + 1); load_raw(rb, p0, p1, s + 1, c.h, k); }
         NERO_FENCE();
         raw_to_x(x, ra, inv0, inv1);
-        ops_compute(aH, aL, wa, x);
+        ops_compute(aH, wa, x);
         NERO_FENCE();
         if (s + 1 < n) {
             if (s + 2 < n) { load_w(wa, wp, s + 2); load_raw(ra, p0, p1, s + 2, c.h, k); }
             NERO_FENCE();
             raw_to_x(x, rb, inv0, inv1);
-            ops_compute(aH, aL, wb, x);
+            ops_compute(aH, wb, x);
             NERO_FENCE();
         }
     }
 }
 
 // the same for the two feature tiles of a wave (weights wp0 / wp1) in one walk: one conversion of the raw fragments per k-step
-__device__ __forceinline__ void gemm_aux_global2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], const uint4* wp0,
+__device__ __forceinline__ void gemm_aux_global2(f32x16 (&aH0)[2], f32x16 (&aH1)[2], const uint4* wp0,
                                                  const uint4* wp1, const float* __restrict__ aux, int ld, int k, int n, const Ctx& c, float inv0,
                                                  float inv1) {
     if (n <= 0) return;
@@ -177,43 +164,28 @@ __device__ __forceinline__ void gemm_aux_global2(f32x16 (&aH0)[2], f32x16 (&aL0)
         if (s + 1 < n) { load_w2(wb, wp0, wp1, s + 1); load_raw(rb, p0, p1, s + 1, c.h, k); }
         NERO_FENCE();
         raw_to_x(x, ra, inv0, inv1);
-        ops_compute2(aH0, aL0, aH1, aL1, wa, x);
+        ops_compute2(aH0, aH1, wa, x);
         NERO_FENCE();
         if (s + 1 < n) {
             if (s + 2 < n) { load_w2(wa, wp0, wp1, s + 2); load_raw(ra, p0, p1, s + 2, c.h, k); }
             NERO_FENCE();
             raw_to_x(x, rb, inv0, inv1);
-            ops_compute2(aH0, aL0, aH1, aL1, wb, x);
+            ops_compute2(aH0, aH1, wb, x);
             NERO_FENCE();
         }
     }
 }
 
-// P_DUAL_TILE (default on): a wave of the 4-wave kernels that owns two feature tiles (t and t + 4) computes both in ONE k-loop
-// (mlp_f16_util.h: gemm_f16x3_dual); 0 restores the two sequential single-tile loops.  The two-accumulator debug format stays sequential.
-// Forward and tangent (P_DUAL_TILE_TAN).  The REVERSE kernels keep the sequential loops: the mask-only kernel measured no gain from one
-// loop (class 5.16 against 5.13 ms), the softplus kernel does not fit (35 spilled registers): profiles/paired_dual_tile_ab.txt.
-#ifndef P_DUAL_TILE
-#ifdef F16_TWO_ACC
-#define P_DUAL_TILE 0
-#else
-#define P_DUAL_TILE 1
-#endif
-#endif
-#ifndef P_DUAL_TILE_TAN
-#define P_DUAL_TILE_TAN P_DUAL_TILE
-#endif
-
 // aux part then main part of the feature tiles t and t + NW together; the units U are those of gemm_tile (they do not depend on the tile)
 template <int NW>
-__device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f32x16 (&aH1)[2], f32x16 (&aL1)[2], float (&U)[2], const Ctx& c,
+__device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aH1)[2], float (&U)[2], const Ctx& c,
                                            int t, const float* w_main, const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx,
                                            const float* aux, int ld_aux, int k_aux_cols) {
     if (sx > 0) {
         const float wsc = wsc_aux;
         const float ra0 = c.S.rs_aux[c.i], ra1 = c.S.rs_aux[32 + c.i];
         const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)t * sx * 128 + c.lane;
-        gemm_aux_global2(aH0, aL0, aH1, aL1, wp, wp + (size_t)NW * sx * 128, aux, ld_aux, k_aux_cols, sx, c, 1.f / ra0, 1.f / ra1);
+        gemm_aux_global2(aH0, aH1, wp, wp + (size_t)NW * sx * 128, aux, ld_aux, k_aux_cols, sx, c, 1.f / ra0, 1.f / ra1);
         U[0] = wsc * ra0;
         U[1] = wsc * ra1;
     }
@@ -226,28 +198,24 @@ __device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aL0)[2], f
             for (int v = 0; v < 16; ++v) {
                 aH0[0][v] *= r0; aH0[1][v] *= r1;
                 aH1[0][v] *= r0; aH1[1][v] *= r1;
-#ifdef F16_TWO_ACC
-                aL0[0][v] *= r0; aL0[1][v] *= r1;
-                aL1[0][v] *= r0; aL1[1][v] *= r1;
-#endif
             }
         }
         U[0] = u0;
         U[1] = u1;
         const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)t * sm * 128 + c.lane;
-        gemm_f16x3_dual(aH0, aL0, aH1, aL1, wp, wp + (size_t)NW * sm * 128, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
+        gemm_f16x3_dual(aH0, aH1, wp, wp + (size_t)NW * sm * 128, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
     }
 }
 
 // aux part (its own unit) then main part of one feature tile; U = unit of the result per 32-row half
 template <int NW>
-__device__ __forceinline__ void gemm_tile(f32x16 (&aH)[2], f32x16 (&aL)[2], float (&U)[2], const Ctx& c, int t, const float* w_main,
+__device__ __forceinline__ void gemm_tile(f32x16 (&aH)[2], float (&U)[2], const Ctx& c, int t, const float* w_main,
                                           const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx, const float* aux, int ld_aux,
                                           int k_aux_cols) {
     if (sx > 0) {
         const float wsc = wsc_aux;
         const float ra0 = c.S.rs_aux[c.i], ra1 = c.S.rs_aux[32 + c.i];
-        gemm_aux_global(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)t * sx * 128 + c.lane,
+        gemm_aux_global(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)t * sx * 128 + c.lane,
                         aux, ld_aux, k_aux_cols, sx, c, 1.f / ra0, 1.f / ra1);
         U[0] = wsc * ra0;
         U[1] = wsc * ra1;
@@ -258,18 +226,13 @@ __device__ __forceinline__ void gemm_tile(f32x16 (&aH)[2], f32x16 (&aL)[2], floa
         if (sx > 0) {
             const float r0 = U[0] / u0, r1 = U[1] / u1;    // exact: powers of two
 #pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                aH[0][v] *= r0; aH[1][v] *= r1;
-#ifdef F16_TWO_ACC
-                aL[0][v] *= r0; aL[1][v] *= r1;
-#endif
-            }
+            for (int v = 0; v < 16; ++v) { aH[0][v] *= r0; aH[1][v] *= r1; }
         }
         U[0] = u0;
         U[1] = u1;
         const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)t * sm * 128 + c.lane;
-        if (NW == 8) gemm_f16x3_lean(aH, aL, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
-        else gemm_f16x3(aH, aL, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
+        if (NW == 8) gemm_f16x3_lean(aH, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
+        else gemm_f16x3(aH, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
     }
 }
 
@@ -346,25 +309,6 @@ __device__ __forceinline__ Ctx make_ctx(char* smem, int n_rows) {
 // ---------------------------------------------------------------------------------------------------------------------
 // forward chain
 // ---------------------------------------------------------------------------------------------------------------------
-template <int ACT>
-__device__ __forceinline__ void fwd_values(const f32x16 (&aH)[2], const f32x16 (&aL)[2], const float4 (&bq)[4], const float (&U)[2],
-                                           float4 (&val)[2][4], float (&m)[2]) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        m[r] = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 v;
-            v.x = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g), U[r], bq[g].x));
-            v.y = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 1), U[r], bq[g].y));
-            v.z = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 2), U[r], bq[g].z));
-            v.w = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 3), U[r], bq[g].w));
-            val[r][g] = v;
-            m[r] = fmaxf(m[r], amax4(v));
-        }
-    }
-}
-
 // bias of feature tile t in the accumulator layout of this lane
 __device__ __forceinline__ void fwd_load_bias(float4 (&bq)[4], const nero_fwd_layer& L, const Ctx& c, int t) {
 #pragma unroll
@@ -374,11 +318,11 @@ __device__ __forceinline__ void fwd_load_bias(float4 (&bq)[4], const nero_fwd_la
 
 // epilogue of one feature tile: bias + activation -> val, row-major save, ReLU sign words, row maxima
 template <int NW>
-__device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2], const f32x16 (&aL)[2],
+__device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
                                              const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4], float (&m)[2] PH_PARAM) {
-    if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, aL, bq, U, val, m);
-    else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, aL, bq, U, val, m);
-    else fwd_values<NERO_ACT_NONE>(aH, aL, bq, U, val, m);
+    if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, bq, U, val, m);
+    else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, bq, U, val, m);
+    else fwd_values<NERO_ACT_NONE>(aH, bq, U, val, m);
     PH(3);
     if (L.save) {
         float* sblock = L.save + (size_t)c.row0 * NERO_HID + 32 * t;
@@ -409,17 +353,16 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
                                          float (&m)[2] PH_PARAM) {
     m[0] = m[1] = 0.f;
     if (t < L.n_tiles) {
-        f32x16 aH[2], aL[2];
+        f32x16 aH[2];
         zero2(aH);
-        zero2(aL);
         float4 bq[4];
         if (NW == 4) fwd_load_bias(bq, L, c, t);        // (NW = 8: behind the GEMM -- 16 registers its 128 have no room for)
         float U[2] = {1.f, 1.f};
         PH(1);
-        gemm_tile<NW>(aH, aL, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
+        gemm_tile<NW>(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
         if (NW == 8) { NERO_FENCE(); fwd_load_bias(bq, L, c, t); }
         PH(2);
-        fwd_epilogue<NW>(L, c, t, aH, aL, bq, U, val, m PH_ARG);
+        fwd_epilogue<NW>(L, c, t, aH, bq, U, val, m PH_ARG);
     } else {
         publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
         PH(4);
@@ -431,22 +374,20 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
 template <int NW>
 __device__ __forceinline__ void fwd_tile_pair(const nero_fwd_chain& ch, const nero_fwd_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
                                               float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2] PH_PARAM) {
-    f32x16 aH0[2], aL0[2], aH1[2], aL1[2];
+    f32x16 aH0[2], aH1[2];
     zero2(aH0);
-    zero2(aL0);
     zero2(aH1);
-    zero2(aL1);
     float4 bq[4];
     fwd_load_bias(bq, L, c, t);
     float U[2] = {1.f, 1.f};
     PH(1);
-    gemm_tile2<NW>(aH0, aL0, aH1, aL1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+    gemm_tile2<NW>(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
                    ch.ld_aux, ch.k_aux);
     float4 bq1[4];                                     // (behind the GEMM: its round trip passes under the first tile's epilogue)
     fwd_load_bias(bq1, L, c, t + NW);
     PH(2);
-    fwd_epilogue<NW>(L, c, t, aH0, aL0, bq, U, v0, m0 PH_ARG);
-    fwd_epilogue<NW>(L, c, t + NW, aH1, aL1, bq1, U, v1, m1 PH_ARG);
+    fwd_epilogue<NW>(L, c, t, aH0, bq, U, v0, m0 PH_ARG);
+    fwd_epilogue<NW>(L, c, t + NW, aH1, bq1, U, v1, m1 PH_ARG);
 }
 
 template <int NW>
@@ -471,17 +412,12 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
         if (L.n_tiles == 0) continue;
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
-#if P_DUAL_TILE
         // (wave-uniform: no second tile for n_tiles <= 4 -- the 128-wide layers -- and for wave 3 of the 217-wide SDF layer)
         if (NW == 4 && c.wave + NW < L.n_tiles) fwd_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1 PH_ARG);
         else {
             fwd_tile<NW>(ch, L, l, c, c.wave, v0, m0 PH_ARG);
             if (NW == 4) fwd_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
         }
-#else
-        fwd_tile<NW>(ch, L, l, c, c.wave, v0, m0 PH_ARG);
-        if (NW == 4) fwd_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
-#endif
         commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
         PH(5);
     }
@@ -497,7 +433,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
 // ---------------------------------------------------------------------------------------------------------------------
 // epilogue of one feature tile of a tangent layer: adot = s * zdot (and the finished injection when the chain asks for it), row maxima
 template <int NW>
-__device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2], const f32x16 (&aL)[2],
+__device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
                                              const float (&U)[2], float4 (&val)[2][4], float (&m)[2]) {
     const size_t goff = (size_t)(c.row0 + c.i) * NERO_HID + 32 * t + 4 * c.h;     // + r*32*HID + 8g
     const size_t boff = (size_t)c.row0 * NERO_HID + 32 * t;
@@ -529,10 +465,10 @@ __device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx&
         for (int g = 0; g < 4; ++g) {
             const float4 a = pa[r][g], gb = pg[r][g];
             float4 ad, ij;
-            tan_elem(a.x, ACCV(aH, aL, r, 4 * g) * U[r], gb.x, live, ad.x, ij.x);
-            tan_elem(a.y, ACCV(aH, aL, r, 4 * g + 1) * U[r], gb.y, live, ad.y, ij.y);
-            tan_elem(a.z, ACCV(aH, aL, r, 4 * g + 2) * U[r], gb.z, live, ad.z, ij.z);
-            tan_elem(a.w, ACCV(aH, aL, r, 4 * g + 3) * U[r], gb.w, live, ad.w, ij.w);
+            tan_elem(a.x, aH[r][4 * g] * U[r], gb.x, live, ad.x, ij.x);
+            tan_elem(a.y, aH[r][4 * g + 1] * U[r], gb.y, live, ad.y, ij.y);
+            tan_elem(a.z, aH[r][4 * g + 2] * U[r], gb.z, live, ad.z, ij.z);
+            tan_elem(a.w, aH[r][4 * g + 3] * U[r], gb.w, live, ad.w, ij.w);
             val[r][g] = ad;
             m[r] = fmaxf(m[r], amax4(ad));
             adq[g] = live ? ad : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -548,12 +484,11 @@ template <int NW>
 __device__ __forceinline__ void tan_tile(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&val)[2][4],
                                          float (&m)[2]) {
     if (t < L.n_tiles) {
-        f32x16 aH[2], aL[2];
+        f32x16 aH[2];
         zero2(aH);
-        zero2(aL);
         float U[2] = {1.f, 1.f};
-        gemm_tile<NW>(aH, aL, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
-        tan_epilogue<NW>(L, c, t, aH, aL, U, val, m);
+        gemm_tile<NW>(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
+        tan_epilogue<NW>(L, c, t, aH, U, val, m);
     } else {
         m[0] = m[1] = 0.f;
         publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
@@ -564,16 +499,14 @@ __device__ __forceinline__ void tan_tile(const nero_tan_chain& ch, const nero_ta
 template <int NW>
 __device__ __forceinline__ void tan_tile_pair(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
                                               float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2]) {
-    f32x16 aH0[2], aL0[2], aH1[2], aL1[2];
+    f32x16 aH0[2], aH1[2];
     zero2(aH0);
-    zero2(aL0);
     zero2(aH1);
-    zero2(aL1);
     float U[2] = {1.f, 1.f};
-    gemm_tile2<NW>(aH0, aL0, aH1, aL1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+    gemm_tile2<NW>(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
                    ch.ld_aux, ch.k_aux);
-    tan_epilogue<NW>(L, c, t, aH0, aL0, U, v0, m0);
-    tan_epilogue<NW>(L, c, t + NW, aH1, aL1, U, v1, m1);
+    tan_epilogue<NW>(L, c, t, aH0, U, v0, m0);
+    tan_epilogue<NW>(L, c, t + NW, aH1, U, v1, m1);
 }
 
 template <int NW>
@@ -591,16 +524,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void tan_p_kernel(nero_tan_chain c
         const nero_tan_layer L = load_layer(ch, l);
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
-#if P_DUAL_TILE_TAN
         if (NW == 4 && c.wave + NW < L.n_tiles) tan_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1);
         else {
             tan_tile<NW>(ch, L, l, c, c.wave, v0, m0);
             if (NW == 4) tan_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1);
         }
-#else
-        tan_tile<NW>(ch, L, l, c, c.wave, v0, m0);
-        if (NW == 4) tan_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1);
-#endif
         commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
     }
 }
@@ -608,13 +536,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void tan_p_kernel(nero_tan_chain c
 // ---------------------------------------------------------------------------------------------------------------------
 // reverse chain:  delta_{l-1} = (delta_l W_l [+ dy_head W_head]) * act'(a_{l-1}) [+ inj_{l-1}]
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void combine_acc(float4 (&gq)[2][4], const f32x16 (&aH)[2], const f32x16 (&aL)[2], const float (&u)[2]) {
+__device__ __forceinline__ void combine_acc(float4 (&gq)[2][4], const f32x16 (&aH)[2], const float (&u)[2]) {
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            gq[r][g] = make_float4(ACCV(aH, aL, r, 4 * g) * u[r], ACCV(aH, aL, r, 4 * g + 1) * u[r],
-                                   ACCV(aH, aL, r, 4 * g + 2) * u[r], ACCV(aH, aL, r, 4 * g + 3) * u[r]);
+            gq[r][g] = make_float4(aH[r][4 * g] * u[r], aH[r][4 * g + 1] * u[r],
+                                   aH[r][4 * g + 2] * u[r], aH[r][4 * g + 3] * u[r]);
 }
 
 // one feature tile of one reverse layer; `first` = the chain's first dense layer (its input gradient goes to d_init / d_aux)
@@ -622,7 +550,7 @@ __device__ __forceinline__ void combine_acc(float4 (&gq)[2][4], const f32x16 (&a
 // (nero_bwd_layer.mask_prev) or the identity: the material / light predictors and the NeRF++ networks.  Compiled without the softplus path the
 // tile keeps 2 sign words instead of 32 activation registers, and the kernel fits its 256 registers without the 14-16 spills of the generic
 // bwd_p_kernel (which lost to the 512-thread kernel for exactly that reason).
-template <bool PA_EARLY, int NW, bool MASKS>
+template <int NW, bool MASKS>
 __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bwd_layer& L, int l, const Ctx& c, int t, bool first, float rs0, float rs1,
                                          float4 (&val)[2][4], float (&m)[2]) {
     m[0] = m[1] = 0.f;
@@ -633,8 +561,8 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
     const int steps = L.n_out >> 4;
     const bool has_inj = !MASKS && !first && L.inj != nullptr;
     const char* xp = c.S.actp + c.i * SA + 16 * c.h;
-    // saved activations of this lane's outputs (ReLU: 1 / 0 from the sign words).  PA_EARLY: requested in FRONT of the main GEMM (32
-    // registers through the k-loop, the HBM round trip under it); default: behind it (the round trip under the sibling workgroup's MFMAs)
+    // saved activations of this lane's outputs (ReLU: 1 / 0 from the sign words): requested in FRONT of the main GEMM (32 registers
+    // through the k-loop, the HBM round trip under it)
     float4 pa[2][4];
     auto load_pa = [&]() {
         if (first || !live_t) return;
@@ -657,16 +585,15 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
     };
     float4 gq[2][4];                                   // incoming gradient of this lane's outputs, true units
     if (L.n_out > 0) {
-        f32x16 aH[2], aL[2];
+        f32x16 aH[2];
         if (ch.d_aux && L.w_aux_t && t < L.k_aux_tiles) {
             zero2(aH);
-            zero2(aL);
             const float wsc = c.S.wsc[2 * l + 1];
-            if (NW == 8) gemm_f16x3_lean(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
-            else gemm_f16x3(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
+            if (NW == 8) gemm_f16x3_lean(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
+            else gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
                        xp, 32 * SA, PLANE_A, steps);
             const float u[2] = {wsc * rs0, wsc * rs1};
-            combine_acc(gq, aH, aL, u);
+            combine_acc(gq, aH, u);
             int li = c.i, lf = fbase;
             P_LOCAL_V(li);
             P_LOCAL_V(lf);
@@ -679,18 +606,15 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
                 }
         }
         if (!live_t || (first && !ch.d_init)) { publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h); return; }
-        if (PA_EARLY) {
-            load_pa();
-            NERO_FENCE();
-        }
+        load_pa();
+        NERO_FENCE();
         zero2(aH);
-        zero2(aL);
         const float wsc = c.S.wsc[2 * l];
-        if (NW == 8) gemm_f16x3_lean(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
-        else gemm_f16x3(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
+        if (NW == 8) gemm_f16x3_lean(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
+        else gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
                    xp, 32 * SA, PLANE_A, steps);
         const float u[2] = {wsc * rs0, wsc * rs1};
-        combine_acc(gq, aH, aL, u);
+        combine_acc(gq, aH, u);
         if (first) {
             if (ch.d_init) {
                 const int ldi = ch.ld_dinit;
@@ -715,16 +639,12 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
     } else {
         // head-only pseudo layer: the incoming gradient is the current content of the planes
         if (!live_t) { publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h); return; }
-        if (PA_EARLY) load_pa();
+        load_pa();
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             gq[0][g] = scale4(load_planes4h(c.S.actp + c.i * SA + (fbase + 8 * g) * 2, PLANE_A), rs0);
             gq[1][g] = scale4(load_planes4h(c.S.actp + (32 + c.i) * SA + (fbase + 8 * g) * 2, PLANE_A), rs1);
         }
-    }
-    if (!PA_EARLY) {
-        NERO_FENCE();
-        load_pa();
     }
     float4 ijp[2][4];                                  // (unused: PRE = false)
 #pragma unroll
@@ -763,8 +683,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void bwd_p_kernel(nero_bwd_chain c
         const float rs0 = c.S.rs_main[c.i], rs1 = c.S.rs_main[32 + c.i];
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
-        bwd_tile<P_PA_EARLY_A, NW, MASKS>(ch, L, l, c, c.wave, first, rs0, rs1, v0, m0);
-        if (NW == 4) bwd_tile<P_PA_EARLY_B, NW, MASKS>(ch, L, l, c, c.wave + NW, first, rs0, rs1, v1, m1);
+        bwd_tile<NW, MASKS>(ch, L, l, c, c.wave, first, rs0, rs1, v0, m0);
+        if (NW == 4) bwd_tile<NW, MASKS>(ch, L, l, c, c.wave + NW, first, rs0, rs1, v1, m1);
         if (first) break;
         commit_planes_p<NW>(c, v0, v1, c.wave < L.k_main_tiles, c.wave + NW < L.k_main_tiles);
     }
@@ -795,6 +715,7 @@ static void report_occupancy(const void* f, const char* name) {      // NERO_DEB
     fprintf(stderr, "[nero] %s: dynamic LDS %d -> %d workgroups per CU\n", name, p_lds_bytes(), nb);
 }
 // waves per workgroup of the paired kernels: NERO_F16_PW = 4 | 8, per pass as a decimal digit string "fwd tan bwd" (e.g. 848)
+constexpr int NERO_F16_PW_DEFAULT = 4;
 static int nero_pw(int kind) {
     static int sel[3] = {-1, -1, -1};
     if (sel[0] < 0) {

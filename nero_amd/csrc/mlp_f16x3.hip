@@ -1,14 +1,13 @@
 // mlp_f16x3.hip -- the fused MLP-chain passes on the fp16 matrix pipe with fp32-grade arithmetic and HALF the MFMA count of
 // the bf16x6 engine (gemm_mode NERO_GEMM_F16X3).
 //
-// An fp32 operand is carried as TWO fp16 planes of its block-scaled value xs = x * 2^-e:
-//        xs = h + 2^-11 * l,      h = fp16(xs),   l = fp16((xs - h) * 2^11)            (round to nearest)
-// fp16 keeps 11 significant bits, so |xs - h| <= 2^-12 |xs|, the scaled remainder has the magnitude of xs/2 (no subnormal
-// trouble of its own) and |xs - h - 2^-11 l| <= 2^-24 |xs|: the pair represents xs to fp32's own half-ulp.  A product is
-//        w x = [ hw hx  +  2^-11 (hw lx + lw hx) ] * 2^(ew + ex),          dropped: 2^-22 lw lx <= 2^-24 |w x|
-// i.e. THREE MFMAs in two accumulator sets (H: hw hx, L: hw lx + lw hx), combined as H + 2^-11 L in the epilogue.
-// ROUND 5 (default; mlp_f16_util.h, -DF16_TWO_ACC = the text above): the block scale puts the maximum at the TOP of fp16's range,
-// l = fp16(xs - h) at its true scale, and all three products accumulate into ONE fp32 accumulator set.
+// An fp32 operand is carried as TWO fp16 planes of its block-scaled value xs = x * 2^-e, the block scale putting the maximum at the TOP
+// of fp16's range (mlp_f16_util.h):
+//        xs = h + l,      h = fp16(xs),   l = fp16(xs - h)            (round to nearest)
+// fp16 keeps 11 significant bits, so |xs - h| <= 2^-12 |xs| and |xs - h - l| <= 2^-24 |xs|: the pair represents xs to fp32's own
+// half-ulp.  A product is
+//        w x = [ hw hx + hw lx + lw hx ] * 2^(ew + ex),          dropped: lw lx <= 2^-24 |w x|
+// i.e. THREE MFMAs that accumulate into ONE fp32 accumulator set.
 // Range: fp16 overflows at 65504 and loses precision below 2^-14, so every operand is scaled by an exact power of two:
 // activations per ROW (64 per tile; exponent of the row maximum, kept in LDS next to the planes), weights per MATRIX (exponent in
 // the packed image's header).  Elements more than 2^14 below their row's maximum lose relative -- not absolute -- precision,
@@ -137,36 +136,12 @@ inline int tan_lds_bytes() { return 2 * PLANE_A + 2 * 64 * SX_N + LDS_SMALL_BYTE
 // ---------------------------------------------------------------------------------------------------------------------
 // forward chain
 // ---------------------------------------------------------------------------------------------------------------------
-template <int ACT>
-__device__ __forceinline__ void fwd_values(const f32x16 (&aH)[2], const f32x16 (&aL)[2], const float4 (&bq)[4], const float (&U)[2],
-                                           float4 (&val)[2][4], float (&m)[2]) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        m[r] = 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float4 v;
-            v.x = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g), U[r], bq[g].x));
-            v.y = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 1), U[r], bq[g].y));
-            v.z = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 2), U[r], bq[g].z));
-            v.w = act_fwd<ACT>(fmaf(ACCV(aH, aL, r, 4 * g + 3), U[r], bq[g].w));
-            val[r][g] = v;
-            m[r] = fmaxf(m[r], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        }
-    }
-}
-
 // PERSISTENT (round 4): a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... (one workgroup per CU).  While the
 // last GEMM of a tile runs its epilogue, the NEXT tile's input rows are already on their way from HBM into registers (tile_request;
 // converted into planes when the tile is done), and after every GEMM the first three weight fragments of the next layer's first GEMM
 // are requested (prefetch_w), so that neither the workgroup dispatch + a cold 64 KB HBM read per tile (~7 k cycles) nor an L2 round trip
 // behind every layer's closing barrier (~900 cycles) sits in front of an idle matrix pipe.  Both requests are issued AFTER the last
 // weight load of the running GEMM: vmcnt retires in order, anything issued earlier would hold the weight stream back.
-#ifdef F16_NO_W_PRE
-#define F16_W_PRE false
-#else
-#define F16_W_PRE true
-#endif
 // NVI = float4 registers per thread that hold the NEXT tile's input rows while the current tile finishes (tile_request): 4 covers
 // k_init <= 128 (the SDF, NeRF++ trunk and light chains), 0 = the input is read at the top of the tile (256-wide inputs: eight more
 // float4 registers on top of the weight fragments do not fit without spilling).
@@ -188,9 +163,6 @@ __global__ __launch_bounds__(512, 1) void fwd_f16_kernel(nero_fwd_chain ch, int 
     // first weight fragments of layer `Ln`'s first GEMM (the aux part when it has one) -> pw
     WF pw0, pw1, pw2;
     auto prefetch_layer = [&](const nero_fwd_layer& Ln) {      // (Ln: a by-value copy in SGPRs, load_layer)
-#ifdef F16_NO_W_PRE
-        return;
-#endif
         if (wave >= Ln.n_tiles) return;
         const int sx = Ln.k_aux >> 4, sm = Ln.k_main >> 4;
         const int n = sx > 0 ? sx : sm;
@@ -236,24 +208,20 @@ __global__ __launch_bounds__(512, 1) void fwd_f16_kernel(nero_fwd_chain ch, int 
         if (L.n_head > 0) eval_head_f16(S.actp, S.rs_main, L.head_w, L.head_b, L.head_out, L.n_head, L.head_k, row0, tid);
         if (L.n_tiles == 0) continue;
         const bool live_wave = wave < L.n_tiles;
-        f32x16 aH[2], aL[2];
+        f32x16 aH[2];
         zero2(aH);
-        zero2(aL);
         float4 bq[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             bq[g] = (live_wave && L.bias) ? *reinterpret_cast<const float4*>(L.bias + 32 * wave + 8 * g + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
         float U[2] = {1.f, 1.f};                           // result unit of the accumulators, per 32-row half (this lane's rows i, 32+i)
         PH(1);
-#if GEMM_SETPRIO == 2
-        if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
         if (live_wave) {
             const int sm = L.k_main >> 4, sx = L.k_aux >> 4;
             if (sx > 0) {
                 const float wsc = S.wsc[2 * l + 1];
-                gemm_f16x3_loop(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux) + HDR_BYTES) + (size_t)wave * sx * 128 + lane,
-                                S.auxp + i * SX + 16 * h, 32 * SX, PLANE_X, sx, F16_W_PRE, pw0, pw1, pw2);
+                gemm_f16x3_loop(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux) + HDR_BYTES) + (size_t)wave * sx * 128 + lane,
+                                S.auxp + i * SX + 16 * h, 32 * SX, PLANE_X, sx, true, pw0, pw1, pw2);
                 U[0] = wsc * S.rs_aux[i];
                 U[1] = wsc * S.rs_aux[32 + i];
             }
@@ -264,30 +232,17 @@ __global__ __launch_bounds__(512, 1) void fwd_f16_kernel(nero_fwd_chain ch, int 
                     // bring the aux partial sums into the main part's unit (exact: powers of two)
                     const float r0 = U[0] / u0, r1 = U[1] / u1;
 #pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        aH[0][v] *= r0; aH[1][v] *= r1;
-#ifdef F16_TWO_ACC
-                        aL[0][v] *= r0; aL[1][v] *= r1;
-#endif
-                    }
+                    for (int v = 0; v < 16; ++v) { aH[0][v] *= r0; aH[1][v] *= r1; }
                 }
                 U[0] = u0;
                 U[1] = u1;
-#ifdef FWD_FIXED16
-                if (sm == 16) gemm_f16x3_fixed<16>(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main) + HDR_BYTES) + (size_t)wave * sm * 128 + lane,
-                                                   S.actp + i * SA + 16 * h, 32 * SA, PLANE_A);
-                else
-#endif
-                gemm_f16x3_loop(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main) + HDR_BYTES) + (size_t)wave * sm * 128 + lane,
-                                S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, sm, F16_W_PRE && sx == 0, pw0, pw1, pw2);
+                gemm_f16x3_loop(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main) + HDR_BYTES) + (size_t)wave * sm * 128 + lane,
+                                S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, sm, sx == 0, pw0, pw1, pw2);
             }
         }
         // requests for what comes next, behind this layer's last weight load (vmcnt retires in order): the next layer's first weight
         // fragments, or -- after the tile's last GEMM -- the next tile's input rows and the first layer's fragments again.  The
         // epilogue, two barriers and the plane conversion that follow (~6 k cycles) cover the L2 / HBM latency.
-#if GEMM_SETPRIO == 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
         NERO_FENCE();
         // (two separate call sites on purpose: merged into one, hipcc keeps the tile-ahead registers and the fragment registers of both
         //  branches alive together -- 256 VGPRs + 13-17 spilled instead of 229-233)
@@ -307,14 +262,9 @@ __global__ __launch_bounds__(512, 1) void fwd_f16_kernel(nero_fwd_chain ch, int 
         float m[2] = {0.f, 0.f};
         PH(2);
         if (live_wave) {
-#ifdef F16_NO_EPI
-            for (int r = 0; r < 2; ++r) for (int g = 0; g < 4; ++g) val[r][g] = make_float4(aH[r][4 * g], aL[r][4 * g], 0.f, 0.f);
-            m[0] = m[1] = 1.f;
-            if (false)
-#endif
-            if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, aL, bq, U, val, m);
-            else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, aL, bq, U, val, m);
-            else fwd_values<NERO_ACT_NONE>(aH, aL, bq, U, val, m);
+            if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, bq, U, val, m);
+            else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, bq, U, val, m);
+            else fwd_values<NERO_ACT_NONE>(aH, bq, U, val, m);
             PH(3);
             if (L.save) {
                 float* scr = reinterpret_cast<float*>(S.scr + wave * SCR_BYTES);
@@ -390,12 +340,12 @@ __device__ __forceinline__ void commit_planes(const Lds& S, const float4 (&val)[
 }
 
 // aux part first (its own unit), converted into the main part's unit, then the main part: returns the unit of the result
-__device__ __forceinline__ void gemm_two_sources(f32x16 (&aH)[2], f32x16 (&aL)[2], float (&U)[2], const Lds& S, const float* w_main,
+__device__ __forceinline__ void gemm_two_sources(f32x16 (&aH)[2], float (&U)[2], const Lds& S, const float* w_main,
                                                  const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx, int SXb, int PLANE_Xb,
                                                  int wave, int lane, int i, int h) {
     if (sx > 0) {
         const float wsc = wsc_aux;
-        gemm_f16x3(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)wave * sx * 128 + lane,
+        gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_aux) + HDR_BYTES) + (size_t)wave * sx * 128 + lane,
                    S.auxp + i * SXb + 16 * h, 32 * SXb, PLANE_Xb, sx);
         U[0] = wsc * S.rs_aux[i];
         U[1] = wsc * S.rs_aux[32 + i];
@@ -406,16 +356,11 @@ __device__ __forceinline__ void gemm_two_sources(f32x16 (&aH)[2], f32x16 (&aL)[2
         if (sx > 0) {
             const float r0 = U[0] / u0, r1 = U[1] / u1;    // exact: powers of two
 #pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                        aH[0][v] *= r0; aH[1][v] *= r1;
-#ifdef F16_TWO_ACC
-                        aL[0][v] *= r0; aL[1][v] *= r1;
-#endif
-                    }
+            for (int v = 0; v < 16; ++v) { aH[0][v] *= r0; aH[1][v] *= r1; }
         }
         U[0] = u0;
         U[1] = u1;
-        gemm_f16x3(aH, aL, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)wave * sm * 128 + lane,
+        gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)wave * sm * 128 + lane,
                    S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, sm);
     }
 }
@@ -464,11 +409,10 @@ __global__ __launch_bounds__(512, 1) void tan_f16_kernel(nero_tan_chain ch, int 
 #pragma unroll
                 for (int g = 0; g < 4; ++g) pg[r][g] = *reinterpret_cast<const float4*>(L.gbar + goff + (size_t)r * 32 * NERO_HID + 8 * g);
         }
-        f32x16 aH[2], aL[2];
+        f32x16 aH[2];
         zero2(aH);
-        zero2(aL);
         float U[2] = {1.f, 1.f};
-        if (live_wave) gemm_two_sources(aH, aL, U, S, L.w_main, L.w_aux, S.wsc[2 * l], S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, SX, PLANE_X, wave, lane, i, h);
+        if (live_wave) gemm_two_sources(aH, U, S, L.w_main, L.w_aux, S.wsc[2 * l], S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, SX, PLANE_X, wave, lane, i, h);
         float4 val[2][4];
         float m[2] = {0.f, 0.f};
         if (live_wave) {
@@ -488,10 +432,10 @@ __global__ __launch_bounds__(512, 1) void tan_f16_kernel(nero_tan_chain ch, int 
                 for (int g = 0; g < 4; ++g) {
                     const float4 a = pa[r][g], gb = pg[r][g];
                     float4 ad, ij;
-                    tan_elem(a.x, ACCV(aH, aL, r, 4 * g) * U[r], gb.x, live, ad.x, ij.x);
-                    tan_elem(a.y, ACCV(aH, aL, r, 4 * g + 1) * U[r], gb.y, live, ad.y, ij.y);
-                    tan_elem(a.z, ACCV(aH, aL, r, 4 * g + 2) * U[r], gb.z, live, ad.z, ij.z);
-                    tan_elem(a.w, ACCV(aH, aL, r, 4 * g + 3) * U[r], gb.w, live, ad.w, ij.w);
+                    tan_elem(a.x, aH[r][4 * g] * U[r], gb.x, live, ad.x, ij.x);
+                    tan_elem(a.y, aH[r][4 * g + 1] * U[r], gb.y, live, ad.y, ij.y);
+                    tan_elem(a.z, aH[r][4 * g + 2] * U[r], gb.z, live, ad.z, ij.z);
+                    tan_elem(a.w, aH[r][4 * g + 3] * U[r], gb.w, live, ad.w, ij.w);
                     val[r][g] = ad;
                     m[r] = fmaxf(m[r], amax4(ad));
                     adq[g] = live ? ad : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -597,15 +541,14 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
         const float rs0 = S.rs_main[i], rs1 = S.rs_main[32 + i];
         PH(1);
         if (L.n_out > 0) {
-            f32x16 aH[2], aL[2];
+            f32x16 aH[2];
             if (ch.d_aux && L.w_aux_t) {
                 zero2(aH);
-                zero2(aL);
                 if (wave < L.k_aux_tiles) {
                     const float wsc = S.wsc[2 * l + 1];
                     const uint4* wpx = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)wave * steps * 128 + lane;
-                    if constexpr (FIXED) gemm_f16x3_fixed<16>(aH, aL, wpx, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A);
-                    else gemm_f16x3(aH, aL, wpx, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, steps);
+                    if constexpr (FIXED) gemm_f16x3_fixed<16>(aH, wpx, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A);
+                    else gemm_f16x3(aH, wpx, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, steps);
                     const float u[2] = {wsc * rs0, wsc * rs1};
 #pragma unroll
                     for (int r = 0; r < 2; ++r)
@@ -614,13 +557,12 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
                             const int f = fbase + 8 * g;
                             if (f < ch.ld_daux)
                                 *reinterpret_cast<float4*>(ch.d_aux + (size_t)(row0 + 32 * r + i) * ch.ld_daux + f) =
-                                    make_float4(ACCV(aH, aL, r, 4 * g) * u[r], ACCV(aH, aL, r, 4 * g + 1) * u[r],
-                                                ACCV(aH, aL, r, 4 * g + 2) * u[r], ACCV(aH, aL, r, 4 * g + 3) * u[r]);
+                                    make_float4(aH[r][4 * g] * u[r], aH[r][4 * g + 1] * u[r],
+                                                aH[r][4 * g + 2] * u[r], aH[r][4 * g + 3] * u[r]);
                         }
                 }
             }
             zero2(aH);
-            zero2(aL);
             float u[2] = {1.f, 1.f};
             if (live_wave) {
                 const float wsc = S.wsc[2 * l];
@@ -628,8 +570,8 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
                 // (Round 4, measured and dropped: the injections requested INSIDE the GEMM, behind its last weight request, so that the
                 //  epilogue does not wait for them -- the second-order pass stayed at 1.55 ms: it is bound by its HBM traffic, 3 KB per row
                 //  and layer at 4.6 TB/s, not by that round trip.)
-                if constexpr (FIXED) gemm_f16x3_fixed<16>(aH, aL, wpm, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A);
-                else gemm_f16x3(aH, aL, wpm, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, steps);
+                if constexpr (FIXED) gemm_f16x3_fixed<16>(aH, wpm, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A);
+                else gemm_f16x3(aH, wpm, S.actp + i * SA + 16 * h, 32 * SA, PLANE_A, steps);
                 u[0] = wsc * rs0;
                 u[1] = wsc * rs1;
             }
@@ -638,8 +580,8 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    gq[r][g] = make_float4(ACCV(aH, aL, r, 4 * g) * u[r], ACCV(aH, aL, r, 4 * g + 1) * u[r],
-                                           ACCV(aH, aL, r, 4 * g + 2) * u[r], ACCV(aH, aL, r, 4 * g + 3) * u[r]);
+                    gq[r][g] = make_float4(aH[r][4 * g] * u[r], aH[r][4 * g + 1] * u[r],
+                                           aH[r][4 * g + 2] * u[r], aH[r][4 * g + 3] * u[r]);
             if (first) {
                 if (ch.d_init && live_wave) {
                     const int ldi = ch.ld_dinit;
@@ -797,9 +739,6 @@ int nero_f16_pack_batch(const nero_pack_job* jobs, int n_jobs, hipStream_t strea
     return nero_check_launch("nero_pack_batch(f16x3)");
 }
 
-#ifndef F16_TILE_AHEAD
-#define F16_TILE_AHEAD 1
-#endif
 // persistent chain kernels: one workgroup per CU, each walks its share of the 64-row tiles
 static int nero_cu_count() {
     static int n = 0;
@@ -828,9 +767,7 @@ static int nero_chain_grid(int n_tiles, int kind_bit) {
 // Measured (profiles/r05_paired_ab.txt, 4096 rays, same box): forward 9.19 -> 8.80 ms, tangent 1.61 -> 1.45 ms, reverse 8.88 -> 9.46 ms
 // (-> 8.8 with the batched epilogue loads, still no gain: its epilogue wants the saved activations the 512-thread kernel brings in by
 // LDS-DMA under the GEMM, for which two workgroups leave no LDS) => default 3.
-#ifndef NERO_F16_PAIRED_DEFAULT
-#define NERO_F16_PAIRED_DEFAULT 3
-#endif
+constexpr int NERO_F16_PAIRED_DEFAULT = 3;
 static int g_paired_mask = -1;
 static int nero_paired_mask() {
     if (g_paired_mask < 0) { const char* e = getenv("NERO_F16_PAIRED"); g_paired_mask = (e ? atoi(e) : NERO_F16_PAIRED_DEFAULT) & 15; }
@@ -854,9 +791,7 @@ static void launch_fwd(const nero_fwd_chain* ch, int n_rows, int n_tiles, dim3 g
 
 // NERO_F16_ROWOWNER: forward chains WITHOUT saves / masks on the row-owner kernel of mlp_f16r.hip (a wave owns 32 rows and all features, planes
 // in registers, weights through an LDS-DMA ring): 1 = launches of at least 128 rows per CU, 3 = every launch (tests), 0 = off.
-#ifndef NERO_F16_ROWOWNER_DEFAULT
-#define NERO_F16_ROWOWNER_DEFAULT 0
-#endif
+constexpr int NERO_F16_ROWOWNER_DEFAULT = 0;
 static int g_rowowner = -1;
 static int nero_rowowner_mask() {
     if (g_rowowner < 0) { const char* e = getenv("NERO_F16_ROWOWNER"); g_rowowner = (e ? atoi(e) : NERO_F16_ROWOWNER_DEFAULT) & 3; }
@@ -886,6 +821,7 @@ int nero_f16_forward(const nero_fwd_chain* ch, int n_rows, hipStream_t stream) {
             return nero_fail(NERO_ERR_ARG, "nero_mlp_forward(f16x3): k_main / k_aux must be multiples of 16");
     // the next tile's input travels in registers while the current tile finishes when it is narrow enough (k_init <= 128) and the
     // launch has more tiles than workgroups
+    constexpr bool F16_TILE_AHEAD = true;
     const bool ahead = F16_TILE_AHEAD && (!ch->init || ch->k_init <= 128) && (int)grid.x < n_tiles;
     (void)cus;
     if (ch->aux_wide) { if (ahead) launch_fwd<true, 4>(ch, n_rows, n_tiles, grid, stream); else launch_fwd<true, 0>(ch, n_rows, n_tiles, grid, stream); }

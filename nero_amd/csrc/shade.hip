@@ -168,21 +168,10 @@ __global__ void sdf_alpha_bwd_kernel(const float* __restrict__ sdf4, const float
     const float gd = fmaxf(gn, 1e-12f);
     const float nh[3] = {g[0] / gd, g[1] / gd, g[2] / gd};
     // eikonal: (|g|-1)^2
-#ifdef NERO_DBG_COHERENT_LOADS                        // (race hunt, round 5: device-scope loads of the two inputs only d_grad depends on)
-    auto cl = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); };
-    const float de = d_gerr ? cl(d_gerr + k) * 2.f * (gn - 1.0f) : 0.f;
-    float qv[8];
-    if (d_geo) for (int c = 0; c < 8; ++c) qv[c] = cl(d_geo + (size_t)k * 8 + c);
-#else
     const float de = d_gerr ? d_gerr[k] * 2.f * (gn - 1.0f) : 0.f;
-#endif
     for (int c = 0; c < 3; ++c) dg[c] += de * nh[c];
     if (d_geo) {
-#ifdef NERO_DBG_COHERENT_LOADS
-        const float* q = qv;
-#else
         const float* q = d_geo + (size_t)k * 8;
-#endif
         const float v[3] = {-dh[0], -dh[1], -dh[2]};
         const float nov = nh[0] * v[0] + nh[1] * v[1] + nh[2] * v[2];
         const float drn = q[4] * nh[0] + q[5] * nh[1] + q[6] * nh[2];

@@ -1,8 +1,9 @@
 #!/bin/bash
-# timing variants of the fp16 chain kernels (compile-time switches in mlp_f16_util.h / mlp_f16x3.hip), all with the
-# per-phase shader-clock instrumentation.  Build here, then on the GPU box:
+# timing variants of the fp16 chain kernels, all with the per-phase shader-clock instrumentation (-DF16_PHASE_TIMING) plus the
+# flags given per variant (the experiment switches of rounds 2-6 are retired: docs/experiments.md, "Retired compile-time
+# switches"; a variant is now a patch of the source, or a -D of your own).  Build here, then on the GPU box:
 #   for v in build/variants/libv_*.so; do NERO_HIP_LIB=$PWD/$v python scripts/phase_timing.py 524288 f16x3 quick; done
-# usage: scripts/f16_variants.sh name1:"-DFLAG ..." name2:"..." ...
+# usage: scripts/f16_variants.sh base:"" name2:"-DFLAG ..." ...
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build/variants
