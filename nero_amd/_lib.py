@@ -1,4 +1,4 @@
-"""ctypes binding of libnero_hip.so (include/nero_hip.h).  The library is REQUIRED: there is no PyTorch/CPU fallback for
+"""ctypes binding of libnero_hip.so (include/nero_hip.h, include/nero_hip_visibility.h).  The library is REQUIRED: there is no PyTorch/CPU fallback for
 the product path -- if it is missing or fails to load, importing this module raises."""
 import ctypes as C
 import os
@@ -9,6 +9,8 @@ import torch  # noqa: F401  -- must come first: libnero_hip.so has to bind to th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERO_HIP_LIB') or os.path.join(_HERE, 'libnero_hip.so')     # (override: kernel-variant experiments)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip.h')
+# every public header of the library, the first one first; an entry point is declared in exactly one of them
+HEADER_PATHS = (HEADER_PATH, os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip_visibility.h'))
 
 MAX_LAYERS = 10
 HID = 256
@@ -85,7 +87,7 @@ class AdamJob(C.Structure):
 MAX_WN_JOBS, MAX_ADAM_JOBS = 40, 96
 
 
-_SCALARS = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
+_SCALARS = {'int': C.c_int, 'unsigned': C.c_uint, 'unsigned int': C.c_uint, 'int64_t': C.c_int64, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
 
 
 def _ctype(decl, fn, ret=False):
@@ -115,16 +117,28 @@ def parse_header(text):
     return sigs
 
 
+def parse_headers(paths=None):
+    """{function: (restype, argtypes, header file name)} over all of `paths` (default HEADER_PATHS), each read by parse_header; a name that
+    two headers declare is an ImportError"""
+    sigs = {}
+    for path in HEADER_PATHS if paths is None else paths:
+        name = os.path.basename(path)
+        with open(path) as f:
+            for fn, (restype, argtypes) in parse_header(f.read()).items():
+                if fn in sigs:
+                    raise ImportError(f'{name} declares {fn}, which {sigs[fn][2]} declares already')
+                sigs[fn] = (restype, argtypes, name)
+    return sigs
+
+
 def bind(lib):
-    """set restype and argtypes of EVERY entry point include/nero_hip.h declares on `lib` (a CDLL of libnero_hip.so): the header is the one
+    """set restype and argtypes of EVERY entry point the headers (HEADER_PATHS) declare on `lib` (a CDLL of libnero_hip.so): a header is the one
     place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call site hands over"""
-    with open(HEADER_PATH) as f:
-        sigs = parse_header(f.read())
-    for fn, (restype, argtypes) in sigs.items():
+    for fn, (restype, argtypes, header) in parse_headers().items():
         try:
             f = getattr(lib, fn)
         except AttributeError:
-            raise ImportError(f'{getattr(lib, "_name", lib)} does not export {fn}, which nero_hip.h declares: rebuild the library') from None
+            raise ImportError(f'{getattr(lib, "_name", lib)} does not export {fn}, which {header} declares: rebuild the library') from None
         f.restype, f.argtypes = restype, argtypes
     return lib
 

@@ -20,6 +20,7 @@
 #include <vector>
 #include "../../include/nero_hip.h"
 #include "bvh_types.h"
+#include "bvh_walk.h"
 #include "common.h"
 
 namespace {
@@ -70,58 +71,8 @@ struct Builder {
     }
 };
 
-__device__ __forceinline__ bool box_hit(const float* mn, const float* mx, const float* o, const float* inv, float tbest, float& tn) {
-    float t0 = 0.f, t1 = tbest;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float ta = (mn[a] - o[a]) * inv[a], tb = (mx[a] - o[a]) * inv[a];
-        const float lo = fminf(ta, tb), hi = fmaxf(ta, tb);
-        t0 = fmaxf(t0, lo);
-        t1 = fminf(t1, hi);
-    }
-    tn = t0;
-    return t0 <= t1;
-}
-
-// The arithmetic of a ray is the same in every traversal kernel below, operation by operation: contraction is switched off and every
-// fused multiply-add is written out, so that the kernels agree bit for bit whatever hipcc makes of the code around the expressions.
-struct TriQ { float4 a, b, c; };           // the 48 bytes of a Tri: v0 e1 | e1 e2 | e2 pad
-__device__ __forceinline__ float cross_c(float a, float b, float c, float d) {     // a b - c d
-#pragma clang fp contract(off)
-    return fmaf(a, b, -(c * d));
-}
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-__device__ __forceinline__ void tri_test(const TriQ& q, int index, const float* o, const float* d, float& tbest, int& best) {
-#pragma clang fp contract(off)
-    const float v0[3] = {q.a.x, q.a.y, q.a.z}, e1[3] = {q.a.w, q.b.x, q.b.y}, e2[3] = {q.b.z, q.b.w, q.c.x};
-    const float px = cross_c(d[1], e2[2], d[2], e2[1]), py = cross_c(d[2], e2[0], d[0], e2[2]), pz = cross_c(d[0], e2[1], d[1], e2[0]);
-    const float det = dot3(e1[0], e1[1], e1[2], px, py, pz);
-    if (fabsf(det) < 1e-20f) return;
-    const float inv = 1.0f / det;
-    const float tx = o[0] - v0[0], ty = o[1] - v0[1], tz = o[2] - v0[2];
-    const float u = dot3(tx, ty, tz, px, py, pz) * inv;
-    if (u < 0.f || u > 1.f) return;
-    const float qx = cross_c(ty, e1[2], tz, e1[1]), qy = cross_c(tz, e1[0], tx, e1[2]), qz = cross_c(tx, e1[1], ty, e1[0]);
-    const float v = dot3(d[0], d[1], d[2], qx, qy, qz) * inv;
-    if (v < 0.f || u + v > 1.f) return;
-    const float tt = dot3(e2[0], e2[1], e2[2], qx, qy, qz) * inv;
-    if (tt > 0.f && tt < tbest) { tbest = tt; best = index; }
-}
-__device__ __forceinline__ TriQ load_tri(const Tri* __restrict__ tris, int i) {
-    const float4* p = reinterpret_cast<const float4*>(tris + i);
-    TriQ q;
-    q.a = p[0]; q.b = p[1]; q.c = p[2];
-    return q;
-}
-// the triangles of a leaf one after the other (low register use: trace_kernel)
-__device__ __forceinline__ void leaf_test(const Tri* __restrict__ tris, int ref, const float* o, const float* d, float& tbest, int& best) {
-    const int code = -ref - 1;
-    const int start = code >> 3, count = code & 7;
-    for (int i = 0; i < count; ++i) tri_test(load_tri(tris, start + i), start + i, o, d, tbest, best);
-}
+// box_hit, tri_test, the leaf loaders and the text of the two walks are in bvh_walk.h (shared with the any-hit kernels of visibility.hip);
+// the kernels below expand the walks with ANY = false
 __device__ __forceinline__ void write_hit(const Tri* __restrict__ tris, int r, const float* o, const float* d, float tbest, int best,
                                           float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ depth) {
 #pragma clang fp contract(off)
@@ -150,33 +101,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const Node* __restrict__ nod
     float inv[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (fabsf(d[a]) > 1e-20f ? d[a] : (d[a] < 0.f ? -1e-20f : 1e-20f));
-    float tbest = MISS_DEPTH;
-    int best = -1;
-    int stack[64];
-    int sp = 0;
-    int cur = (skip != nullptr && skip[r] != 0) ? NONE : root;          // a skipped ray reports a miss without a single node visit
-    if (cur != NONE && cur < 0) { leaf_test(tris, cur, o, d, tbest, best); cur = NONE; }
-    while (cur != NONE) {
-        const Node nd = nodes[cur];
-        float tl, tr;
-        const bool hl = box_hit(nd.lmin, nd.lmax, o, inv, tbest, tl);
-        const bool hr = box_hit(nd.rmin, nd.rmax, o, inv, tbest, tr);
-        int next = NONE;
-        int first = nd.left, second = nd.right;
-        bool hf = hl, hs = hr;
-        if (hl && hr && tr < tl) { first = nd.right; second = nd.left; }
-        if (!hl) { first = nd.right; hf = hr; hs = false; }
-        if (hf) {
-            if (first < 0) leaf_test(tris, first, o, d, tbest, best); else next = first;
-        }
-        if (hs) {
-            if (second < 0) leaf_test(tris, second, o, d, tbest, best);
-            else if (next == NONE) next = second;
-            else if (sp < 64) stack[sp++] = second;
-        }
-        if (next == NONE && sp > 0) next = stack[--sp];
-        cur = next;
-    }
+    NERO_WALK_PRIVATE(false, MISS_DEPTH, (skip != nullptr && skip[r] != 0) ? NONE : root)   // a skipped ray reports a miss without a single node visit
     write_hit(tris, r, o, d, tbest, best, pos, nrm, depth);
 }
 
@@ -187,27 +112,6 @@ __global__ __launch_bounds__(256) void trace_kernel(const Node* __restrict__ nod
 // 40 %, texture addresser busy 47 %, 3.5 waves per SIMD on average; 4.8 k cycles per step).  Here a step asks for everything at once:
 // the NEXT node (its index is known as soon as the boxes are tested -- the leaf tests only shrink tbest) and all triangles of the
 // leaves, then tests; the stack is in LDS.  Same visit order and the same arithmetic per ray as trace_kernel.
-struct NodeQ { float4 a, b, c, d; };       // the 64 bytes of a Node: lmin lmax | rmin rmax | left right pad pad
-__device__ __forceinline__ NodeQ load_node(const Node* __restrict__ nodes, int i) {
-    const float4* p = reinterpret_cast<const float4*>(nodes + i);
-    NodeQ q;
-    q.a = p[0]; q.b = p[1]; q.c = p[2]; q.d = p[3];
-    return q;
-}
-__device__ __forceinline__ void leaf_test_batched(const Tri* __restrict__ tris, int ref, const float* o, const float* d, float& tbest, int& best) {
-    const int code = -ref - 1;
-    const int start = code >> 3, count = code & 7;            // <= 4 (Builder::build)
-    const float4* p = reinterpret_cast<const float4*>(tris + start);
-    TriQ q[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // unconditional (a short leaf re-reads its first triangle): predicated loads come out of hipcc with a
-        const int j = i < count ? i : 0;   // wait inside every predicated block, i.e. one triangle after the other again
-        q[i].a = p[3 * j]; q[i].b = p[3 * j + 1]; q[i].c = p[3 * j + 2];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (i < count) tri_test(q[i], start + i, o, d, tbest, best);
-}
 
 // one wavefront per workgroup: the workgroups of a launch retire at very different times (secondary rays), and small ones refill the
 // CUs sooner (1 M / 3.1 M secondary rays: 0.52 / 1.22 ms with 64 threads, 0.53 / 1.26 with 128, 0.56 / 1.38 with 256; coherent camera
@@ -219,7 +123,6 @@ __device__ __forceinline__ void leaf_test_batched(const Tri* __restrict__ tris, 
 // same closest triangle on every ray) -- half the dependent steps per ray (36 -> 20), but 101 VGPRs and twice the box work per step:
 // 0.57 ms per 1 M synthetic rays against 0.51, 0.83 against 0.73 on the rays of a training step.
 struct ChunkOrder { int n; unsigned char c[32]; };            // n = 0: no explicit order
-constexpr int PL_THREADS = 64;
 
 // LAUNCH ORDER (round 5, nero_bvh_trace_grouped): the secondary rays of Stage II come as [point][direction] with the cosine-weighted
 // diffuse directions first and the GGX specular ones behind them.  Every ray that points below the geometric surface -- it crosses the
@@ -250,48 +153,7 @@ __global__ __launch_bounds__(PL_THREADS) void trace_overlap_kernel(const Node* _
     float inv[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (fabsf(d[a]) > 1e-20f ? d[a] : (d[a] < 0.f ? -1e-20f : 1e-20f));
-    float tbest = MISS_DEPTH;
-    int best = -1, sp = 0, cur = (skip != nullptr && skip[r] != 0) ? NONE : root;      // (a skipped ray: a miss without a node visit)
-    NodeQ nd = {};
-    if (cur == NONE) {}
-    else if (cur < 0) { leaf_test(tris, cur, o, d, tbest, best); cur = NONE; }
-    else nd = load_node(nodes, cur);
-    // ONE leaf section per step: the second leaf of a node is tested at the start of the lane's next step, before its next node -- the
-    // same order of visits, but a wavefront executes the triangle code once per step instead of twice (0.57 -> 0.52 ms per 1 M rays)
-    int pend = NONE;
-    while (cur != NONE || pend != NONE) {
-        int leaf = pend;
-        pend = NONE;
-        if (leaf == NONE) {
-            const float lmin[3] = {nd.a.x, nd.a.y, nd.a.z}, lmax[3] = {nd.a.w, nd.b.x, nd.b.y};
-            const float rmin[3] = {nd.b.z, nd.b.w, nd.c.x}, rmax[3] = {nd.c.y, nd.c.z, nd.c.w};
-            const int left = __float_as_int(nd.d.x), right = __float_as_int(nd.d.y);
-            float tl, tr;
-            const bool hl = box_hit(lmin, lmax, o, inv, tbest, tl);
-            const bool hr = box_hit(rmin, rmax, o, inv, tbest, tr);
-            int next = NONE, leaf_a = NONE, leaf_b = NONE;
-            int first = left, second = right;
-            bool hf = hl, hs = hr;
-            if (hl && hr && tr < tl) { first = right; second = left; }
-            if (!hl) { first = right; hf = hr; hs = false; }
-            if (hf) {
-                if (first < 0) leaf_a = first; else next = first;
-            }
-            if (hs) {
-                if (second < 0) leaf_b = second;
-                else if (next == NONE) next = second;
-                else if (sp < PL_STACK) st[(sp++) * PL_THREADS] = second;
-            }
-            if (next == NONE && sp > 0) next = st[(--sp) * PL_THREADS];
-            nd = load_node(nodes, next != NONE ? next : 0);                    // in flight while the triangles are fetched and tested.  Unconditional (a
-                                                                               // finished lane re-reads node 0): behind `if (next != NONE)` hipcc reused a padding register of
-                                                                               // the load as scratch and waited for the node before it requested the triangles (0.77 -> 0.73 ms
-                                                                               // on the rays of a training step)
-            cur = next;
-            if (leaf_a != NONE) { leaf = leaf_a; pend = leaf_b; } else leaf = leaf_b;
-        }
-        if (leaf != NONE) leaf_test_batched(tris, leaf, o, d, tbest, best);
-    }
+    NERO_WALK_OVERLAP(false, MISS_DEPTH, (skip != nullptr && skip[r] != 0) ? NONE : root)   // (a skipped ray: a miss without a node visit)
     write_hit(tris, r, o, d, tbest, best, pos, nrm, depth);
 }
 

@@ -134,3 +134,39 @@ class RayTracer:
             L.check(L.lib.nero_bvh_trace(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n,
                                          positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         return positions.view(*prefix, 3), face_normals.view(*prefix, 3), depth.view(*prefix)
+
+    def occluded(self, rays_o, rays_d, tmax=None, skip=None):
+        """shadow rays (nero_bvh_occluded): uint8 tensor of the rays' leading shape, 1 where some triangle lies at 0 < t < tmax along the ray
+        -- what `trace(...)[2] < tmax` says, without the walk to the closest hit.  tmax: None (10, the miss distance), a float in (0, 10],
+        or a float32 CUDA tensor of the rays' leading shape (per ray, clamped to [0, 10]).  skip: uint8 CUDA tensor of that shape or None; a
+        flagged ray reports 0 without a node visit."""
+        rays_o = rays_o.float().contiguous()
+        rays_d = rays_d.float().contiguous()
+        if not rays_o.is_cuda:
+            rays_o = rays_o.cuda()
+        if not rays_d.is_cuda:
+            rays_d = rays_d.cuda()
+        prefix = rays_o.shape[:-1]
+        rays_o = rays_o.view(-1, 3)
+        rays_d = rays_d.view(-1, 3)
+        n = rays_o.shape[0]
+        assert rays_d.shape[0] == n and rays_d.device == rays_o.device
+        tp, tmax_all = None, 10.0
+        if torch.is_tensor(tmax):
+            assert tmax.dtype == torch.float32 and tmax.is_cuda and tmax.device == rays_o.device and tmax.is_contiguous() \
+                and tmax.shape == prefix and tmax.numel() == n
+            tp = tmax.data_ptr()
+        elif tmax is not None:
+            tmax_all = float(tmax)
+        sp = None
+        if skip is not None:
+            assert torch.is_tensor(skip) and skip.dtype == torch.uint8 and skip.is_cuda and skip.device == rays_o.device \
+                and skip.is_contiguous() and skip.shape == prefix and skip.numel() == n
+            sp = skip.data_ptr()
+        out = torch.empty(n, dtype=torch.uint8, device=rays_o.device)
+        if n == 0:
+            return out.view(*prefix)
+        with torch.cuda.device(rays_o.device):
+            L.check(L.lib.nero_bvh_occluded(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n, tp, tmax_all, sp, out.data_ptr(),
+                                            L.stream_ptr()))
+        return out.view(*prefix)

@@ -815,7 +815,8 @@ class NeROMaterialRenderer(nn.Module):
     def extract_texture_maps(self, **kw):
         """albedo / metallic / roughness baked into UV texture maps on the device (extract_materials_texture_map.py): nero_amd.texture.
         bake_materials(self, **kw) -- vt / ft of any unwrapper, or atlas='triangles' (the built-in simple_atlas, the default) / atlas='charts'
-        (the projection atlas, nero_amd.texture.chart_atlas)"""
+        (the projection atlas, nero_amd.texture.chart_atlas); ao={'samples': 64, 'radius': None, 'bias': 1e-4, 'seed': 0} (any subset) adds
+        an ambient-occlusion map 'ao' from shadow rays on self.ray_tracer (nero_amd.texture.bake_ambient_occlusion)"""
         from .texture import bake_materials
         return bake_materials(self, **kw)
 

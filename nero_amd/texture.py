@@ -11,6 +11,8 @@ step is a kernel of nero_amd/csrc/texture.hip or mesh_atlas.hip here:
   * chart_atlas: the projection atlas in place of xatlas: charts of faces that look along one signed axis, projected at one
     texel density and shelf-packed; uv_overlap measures what such an atlas (or anyone's) covers twice;
   * simple_atlas: a dependency-free one-chart-per-triangle atlas for when no unwrapper is at hand; any (vt, ft) can be passed instead;
+  * ambient_occlusion / ao_bytes / bake_ambient_occlusion: an occlusion map from shadow rays on the mesh tracer's BVH (nero_bvh_ao of
+    include/nero_hip_visibility.h; the reference has no counterpart), also as bake_materials(..., ao={...});
   * write_textured_obj / read_textured_obj: the reference's OBJ / MTL layout with lossless PNG maps.
 Conventions (include/nero_hip.h): maps are [h, w] row-major, texel (row y, column x) has its centre at u = (x + 0.5) / w, v = (y + 0.5) / h."""
 import os
@@ -361,8 +363,117 @@ def simple_atlas(verts, tris, size):
     return vt, ft
 
 
+# ---- ambient occlusion ----------------------------------------------------------------------------------------------------------------------
+AO_MAX_RAYS = (1 << 31) - 64            # n * S of one nero_bvh_ao call
+AO_MISS = 10.0                          # the tracer's miss distance: the radius of an unbounded query
+
+
+def ambient_occlusion(tracer, pts, nrm, key, samples=64, radius=None, bias=1e-4, seed=0, chunk=None):
+    """how many of `samples` cosine-distributed shadow rays leaving pts [n,3] (lifted by `bias` along the UNIT normals nrm [n,3]) meet the
+    mesh of `tracer` (nero_amd.raytracing.RayTracer) within `radius` (None: 10, the tracer's miss distance): int32 counts [n] on the device,
+    through nero_bvh_ao -- the rays are made and cast in one kernel and never stored.  key int32 [n] names each point's sample set (the
+    texel's row-major index: the result does not depend on the order or the chunking of the points); samples: a power of two in
+    [8, 1024].  `chunk` points per call, at most (2^31 - 64) // samples (the default)."""
+    dev = _dev(pts, nrm, key)
+    pts, nrm, key = _to(pts, torch.float32, dev, 3), _to(nrm, torch.float32, dev, 3), _to(key, torch.int32, dev)
+    n, S = pts.shape[0], int(samples)
+    if nrm.shape[0] != n or key.shape != (n,):
+        raise ValueError(f'ambient_occlusion: pts [n,3], nrm [n,3] and key [n] expected, got {tuple(pts.shape)}, {tuple(nrm.shape)}, {tuple(key.shape)}')
+    if S < 8 or S > 1024 or S & (S - 1):
+        raise ValueError(f'ambient_occlusion: samples must be a power of two in [8, 1024], got {samples}')
+    tmax = AO_MISS if radius is None else float(radius)
+    limit = AO_MAX_RAYS // S
+    chunk = limit if chunk is None else min(max(1, int(chunk)), limit)
+    with torch.cuda.device(dev):
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        h, s = tracer._handle(), L.stream_ptr()
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            L.check(_lib.nero_bvh_ao(h, L.ptr(pts[i:i + m]), L.ptr(nrm[i:i + m]), L.ptr(key[i:i + m]), m, S, int(seed) & 0xffffffff, float(bias),
+                                     tmax, L.ptr(count[i:i + m]), s))
+    return count
+
+
+def ao_bytes(count, samples):
+    """occluded-ray counts of `samples` rays -> the 8-bit ambient-occlusion level, LINEAR (no sRGB curve: nero_tex_quantize is not used):
+    floor(255 (S - c) / S + 1 / 2) as (510 (S - c) + S) // (2 S) in integers.  255: nothing in the way; 0: every ray blocked."""
+    S = int(samples)
+    c = count.to(torch.int64)
+    return torch.div(510 * (S - c) + S, 2 * S, rounding_mode='floor').to(torch.uint8)
+
+
+def face_normals(verts, tris, flip=False):
+    """unit geometric normals of the triangles, float32 [T,3] on the device: normalize(cross(v1 - v0, v2 - v0)), negated when `flip` (a mesh
+    wound inward, as the renderer's: NeROMaterialRenderer.trace negates the tracer's face normal)"""
+    dev = _dev(verts, tris)
+    v, f = _to(verts, torch.float32, dev, 3), _to(tris, torch.int32, dev, 3).long()
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    n = torch.nn.functional.normalize(torch.linalg.cross(b - a, c - a), dim=-1)
+    return -n if flip else n
+
+
+def _ao_texture(tracer, tri_id, texel, pts, v_d, f_d, flip_normals, samples, radius, bias, seed):
+    """the AO pass over the covered texels of a rasterised atlas -> (counts int32 [n], normals [n,3], texture uint8 [H, W, 1], zero elsewhere)"""
+    H, W = tri_id.shape
+    nrm = face_normals(v_d, f_d, flip_normals)[tri_id.reshape(-1)[texel.long()].long()].contiguous()
+    count = ambient_occlusion(tracer, pts, nrm, texel, samples, radius, bias, seed)
+    tex = torch.zeros((H, W, 1), dtype=torch.uint8, device=tri_id.device)
+    tex.view(-1)[texel.long()] = ao_bytes(count, samples)
+    return count, nrm, tex
+
+
+def bake_ambient_occlusion(verts, tris, vt=None, ft=None, size=1024, ssaa=2, pad=32, border=3, samples=64, radius=None, bias=1e-4, seed=0,
+                           flip_normals=False, tracer=None, atlas='triangles', return_intermediates=False):
+    """an ambient-occlusion map of a mesh, no network needed -> {'ao' [size, size] uint8 on the device (255: open, 0: shut in), 'mask' [size,
+    size] bool, 'vt', 'ft'}.
+
+    Rasterise and interpolate as bake_materials does; at every covered texel cast `samples` cosine-distributed shadow rays from the surface
+    point, lifted by `bias` along the geometric normal of the texel's triangle (negated with flip_normals: a mesh wound inward), no further
+    than `radius` (None: unbounded); ao_bytes of the counts; gutter fill and 2 x 2 mean as for the material maps.  tracer: a RayTracer of
+    the same mesh (one is built when None).  atlas / vt / ft as in bake_materials.  return_intermediates: also 'tri_id', 'texel', 'points',
+    'normals', 'ao_count', 'region' and 'texture' (the filled map [H, W, 1]) at the supersampled size."""
+    if ssaa not in (1, 2):
+        raise ValueError(f'bake_ambient_occlusion: ssaa must be 1 or 2, got {ssaa}')
+    if (vt is None) != (ft is None):
+        raise ValueError('bake_ambient_occlusion: pass both vt and ft, or neither')
+    if atlas not in ('triangles', 'charts'):
+        raise ValueError(f"bake_ambient_occlusion: atlas must be 'triangles' or 'charts', got {atlas!r}")
+    dev = _dev(verts, tris, vt, ft)
+    atlas_info = None
+    with torch.cuda.device(dev), torch.no_grad():
+        v_d, f_d = _to(verts, torch.float32, dev, 3), _to(tris, torch.int32, dev, 3)
+        if vt is None and atlas == 'charts':
+            vt, ft, atlas_info = chart_atlas(v_d, f_d, size)
+        elif vt is None:
+            vt, ft = simple_atlas(_np(verts), _np(tris), size)
+        vt_d, ft_d = _to(vt, torch.float32, dev, 2), _to(ft, torch.int32, dev, 3)
+        if ft_d.shape[0] != f_d.shape[0]:
+            raise ValueError(f'bake_ambient_occlusion: ft has {ft_d.shape[0]} faces, the mesh {f_d.shape[0]}')
+        if tracer is None:
+            from .raytracing import RayTracer
+            tracer = RayTracer(_np(verts), _np(tris))
+        H = W = int(size) * ssaa
+        tri_id = rasterize_uv(vt_d, ft_d, H, W)
+        texel, pts, mask = interpolate(tri_id, vt_d, ft_d, v_d, f_d, return_mask=True)
+        count, nrm, tex = _ao_texture(tracer, tri_id, texel, pts, v_d, f_d, flip_normals, samples, radius, bias, seed)
+        region = gutter_regions(mask, pad, border)
+        tex_ss = fill_gutter(tex, region, pad)
+        if ssaa == 2:
+            tex = downsample2(tex_ss)
+            mask_out = mask.view(size, 2, size, 2).amax(dim=(1, 3)) > 0
+        else:
+            tex, mask_out = tex_ss, mask > 0
+        out = {'ao': tex[..., 0].contiguous(), 'mask': mask_out, 'vt': vt, 'ft': ft}
+        if atlas_info is not None:
+            out['atlas_info'] = atlas_info
+        if return_intermediates:
+            out.update(tri_id=tri_id, texel=texel, points=pts, normals=nrm, ao_count=count, region=region, texture=tex_ss)
+    return out
+
+
 # ---- the pipeline ---------------------------------------------------------------------------------------------------------------------------
-def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=1 << 19, border=3, return_intermediates=False, atlas='triangles'):
+def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=1 << 19, border=3, return_intermediates=False, atlas='triangles',
+                   ao=None):
     """NeROMaterialRenderer -> {'albedo' [size, size, 3], 'metallic' [size, size], 'roughness' [size, size]: uint8 device tensors, 'mask'
     [size, size] bool (a chart covers the texel), 'vt', 'ft'}: extract_materials_texture_map.py:89-160 on the device.
 
@@ -374,9 +485,13 @@ def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=
     'atlas_info'); or pass an unwrapper's vt / ft (xatlas).  The only host traffic is the count readbacks of rasterize_uv / interpolate.  The MLPs run
     on this project's fp32-grade engine (the reference: fp16 autocast), so single 8-bit levels can differ from the reference's maps.
     return_intermediates: also 'tri_id', 'texel', 'points', 'values' [n, 5], 'region', 'source' and 'texture' (the filled maps [H, W, 5])
-    at the supersampled size."""
+    at the supersampled size.  ao: None, or a dict with any of 'samples' (64), 'radius' (None), 'bias' (1e-4), 'seed' (0): the same
+    rasterisation also feeds an ambient-occlusion pass on renderer.ray_tracer (bake_ambient_occlusion with flip_normals=True: the renderer's
+    mesh is wound inward), and the result holds 'ao' [size, size] (with return_intermediates 'ao_count' too).  ao=None: nothing changes."""
     if ssaa not in (1, 2):
         raise ValueError(f'bake_materials: ssaa must be 1 or 2, got {ssaa}')
+    if ao is not None and (not isinstance(ao, dict) or set(ao) - {'samples', 'radius', 'bias', 'seed'}):
+        raise ValueError(f"bake_materials: ao must be None or a dict of 'samples' / 'radius' / 'bias' / 'seed', got {ao!r}")
     verts, tris = renderer.mesh_vertices, renderer.mesh_triangles
     dev = next(renderer.parameters()).device
     if dev.type != 'cuda':
@@ -423,6 +538,13 @@ def bake_materials(renderer, vt=None, ft=None, size=1024, ssaa=2, pad=32, chunk=
             out['atlas_info'] = atlas_info
         if return_intermediates:
             out.update(tri_id=tri_id, texel=texel, points=pts, values=values, region=region, source=src, texture=tex_ss)
+        if ao is not None:
+            count, _, ao_tex = _ao_texture(renderer.ray_tracer, tri_id, texel, pts, v_d, f_d, True, ao.get('samples', 64), ao.get('radius'),
+                                           ao.get('bias', 1e-4), ao.get('seed', 0))
+            ao_tex = fill_gutter(ao_tex, region, pad)
+            out['ao'] = (downsample2(ao_tex) if ssaa == 2 else ao_tex)[..., 0].contiguous()
+            if return_intermediates:
+                out['ao_count'] = count
     return out
 
 
@@ -524,7 +646,9 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
     """the reference's OBJ / MTL layout (extract_materials_texture_map.py:166-197) in `dir`: <name>.obj with `v x y z`, `vt u 1-v`, 1-based
     `f a/b` faces; <name>.mtl whose map_Kd names the albedo image; feat0_<cas>.png (albedo), feat1_<cas>.png (metallic), feat2_<cas>.png
     (roughness), the two scalar maps as three equal channels (COLOR_GRAY2BGR), image row 0 = texel row 0.  maps: the dict bake_materials
-    returns.  Differences from the reference: lossless PNG instead of JPEG.  -> the path of the OBJ."""
+    returns.  When it holds 'ao' (bake_materials(..., ao={...})), feat3_<cas>.png (ambient occlusion, three equal channels) is written too
+    and the MTL names it in a map_Ka line; without 'ao' the files are what they were.  Differences from the reference: lossless PNG instead of
+    JPEG.  -> the path of the OBJ."""
     os.makedirs(dir, exist_ok=True)
     v = _np(verts, np.float64).reshape(-1, 3)
     f = _np(tris, np.int64).reshape(-1, 3)
@@ -535,7 +659,10 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
     if f.size and (f.min() < 0 or f.max() >= len(v) or fuv.min() < 0 or fuv.max() >= len(uv)):
         raise ValueError('write_textured_obj: a face index is out of range')
     names = _map_names(name)
-    for fname, key in zip(names, ('albedo', 'metallic', 'roughness')):
+    keys = ('albedo', 'metallic', 'roughness')
+    if 'ao' in maps:
+        names, keys = names + [names[0].replace('feat0_', 'feat3_', 1)], keys + ('ao',)
+    for fname, key in zip(names, keys):
         img = np.ascontiguousarray(_np(maps[key]), dtype=np.uint8)
         if img.ndim == 2:
             img = np.repeat(img[..., None], 3, -1)
@@ -551,12 +678,15 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
         np.savetxt(fh, faces, fmt='f %d/%d %d/%d %d/%d')
     with open(os.path.join(dir, name + '.mtl'), 'w') as fh:
         fh.write(f'newmtl defaultMat\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nTr 1\nillum 1\nNs 0\nmap_Kd {names[0]}\n')
+        if 'ao' in maps:
+            fh.write(f'map_Ka {names[3]}\n')
     return obj
 
 
 def read_textured_obj(path, load_maps=True):
     """what write_textured_obj writes -> {'v' float64 [V,3], 'f' int64 [T,3], 'vt' float32 [Vt,2] (the file's 1 - v undone), 'ft' int64 [T,3],
-    'mtllib', 'map_Kd', and with load_maps 'albedo' [h,w,3], 'metallic' [h,w], 'roughness' [h,w] uint8 from the PNGs beside it}"""
+    'mtllib', 'map_Kd', 'map_Ka' (only when the MTL has such a line), and with load_maps 'albedo' [h,w,3], 'metallic' [h,w], 'roughness' [h,w] and, when
+    the MTL has a map_Ka line, 'ao' [h,w] uint8 from the PNGs beside it}"""
     lines = open(path).read().split('\n')
     pick = lambda key: [ln[len(key):] for ln in lines if ln.startswith(key)]
     v = np.array([x.split() for x in pick('v ')], dtype=np.float64).reshape(-1, 3)
@@ -568,12 +698,19 @@ def read_textured_obj(path, load_maps=True):
     out['mtllib'] = out['mtllib'].strip() if out['mtllib'] else None
     d = os.path.dirname(os.path.abspath(path))
     if out['mtllib'] and os.path.exists(os.path.join(d, out['mtllib'])):
-        kd = [ln.split(None, 1)[1].strip() for ln in open(os.path.join(d, out['mtllib'])).read().split('\n') if ln.startswith('map_Kd ')]
+        mtl = open(os.path.join(d, out['mtllib'])).read().split('\n')
+        kd = [ln.split(None, 1)[1].strip() for ln in mtl if ln.startswith('map_Kd ')]
         out['map_Kd'] = kd[0] if kd else None
+        ka = [ln.split(None, 1)[1].strip() for ln in mtl if ln.startswith('map_Ka ')]
+        if ka:
+            out['map_Ka'] = ka[0]
     if load_maps and out['map_Kd'] and out['map_Kd'].startswith('feat0_'):
         for k, key in enumerate(('albedo', 'metallic', 'roughness')):
             p = os.path.join(d, f'feat{k}_' + out['map_Kd'][6:])
             if os.path.exists(p):
                 img = read_png(p)
                 out[key] = img if k == 0 else np.ascontiguousarray(img[..., 0])
+    if load_maps and 'map_Ka' in out and os.path.exists(os.path.join(d, out['map_Ka'])):
+        img = read_png(os.path.join(d, out['map_Ka']))
+        out['ao'] = img if img.ndim == 2 else np.ascontiguousarray(img[..., 0])
     return out

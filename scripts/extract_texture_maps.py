@@ -13,7 +13,9 @@ extract_materials_texture_map.py) through nero_amd.texture -- no xatlas / nvdiff
 small or decimated meshes; `charts`, the projection atlas of nero_amd.texture.chart_atlas (--gutter texels between charts), for a mesh as it
 comes from the clean-up.  With `charts` the number of charts, the scale (texels per world unit), the fill and the texels covered twice are
 printed, a warning is given when any texel is covered twice, and the atlas is saved as <name>_atlas.npz next to the OBJ (vt, ft, vt_vertex,
-vt_chart, chart, rects, scale)."""
+vt_chart, chart, rects, scale).  --ao-samples N (a power of two in [8, 1024]; 0, the default: no AO map) also bakes an ambient-occlusion map
+from N shadow rays per texel, no longer than --ao-radius (default: unbounded) and started --ao-bias above the surface; it is written as
+feat3_<cas>.png and named by a map_Ka line of the MTL."""
 import argparse
 import json
 import os
@@ -45,6 +47,9 @@ def main(argv=None):
     ap.add_argument('--uv', help='.npz holding vt and ft')
     ap.add_argument('--atlas', choices=('triangles', 'charts'), default='triangles', help='the built-in atlas used without --uv')
     ap.add_argument('--gutter', type=int, default=4, help='texels between the charts of --atlas charts')
+    ap.add_argument('--ao-samples', type=int, default=0, help='shadow rays per texel of the ambient-occlusion map; 0: no AO map')
+    ap.add_argument('--ao-radius', type=float, default=None, help='longest shadow ray (default: unbounded)')
+    ap.add_argument('--ao-bias', type=float, default=1e-4, help='shadow rays start this far above the surface')
     ap.add_argument('--out', required=True)
     ap.add_argument('--name', default='mesh_0')
     args = ap.parse_args(argv)
@@ -70,10 +75,13 @@ def main(argv=None):
     info = None
     if vt is None and args.atlas == 'charts':
         vt, ft, info = TX.chart_atlas(net.mesh_vertices, net.mesh_triangles, args.size, gutter=args.gutter)
-    maps = net.extract_texture_maps(vt=vt, ft=ft, size=args.size, ssaa=args.ssaa, pad=args.pad)
+    ao = {'samples': args.ao_samples, 'radius': args.ao_radius, 'bias': args.ao_bias} if args.ao_samples > 0 else None
+    maps = net.extract_texture_maps(vt=vt, ft=ft, size=args.size, ssaa=args.ssaa, pad=args.pad, ao=ao)
     obj = TX.write_textured_obj(args.out, net.mesh_vertices, net.mesh_triangles, maps['vt'], maps['ft'], maps, name=args.name)
     report = {'obj': obj, 'size': args.size, 'ssaa': args.ssaa, 'pad': args.pad, 'triangles': int(len(f)),
               'covered_texels': int(maps['mask'].sum()), 'atlas': 'given' if args.uv else ('chart_atlas' if info else 'simple_atlas')}
+    if ao is not None:
+        report.update(ao_samples=args.ao_samples, ao_radius=args.ao_radius, ao_bias=args.ao_bias)
     if info is not None:
         npz = os.path.join(args.out, args.name + '_atlas.npz')
         host = lambda x: x.cpu().numpy()
