@@ -485,7 +485,8 @@ int nero_mc_split_dead(const float* depth, const unsigned char* dead, int n, int
  *   mat: [2P,5] when has_reg (rows P.. = the materials at the perturbed points), else [P,5]; partials: nero_mat_loss_partials(P) floats.
  *   hinge_weight: 0 = the reg_min_max hinge is off (step >= 2000), otherwise the weight of the hinge SUM (1 for one process; the
  *   data-parallel step passes world size).
- * nero_mat_loss_bwd: gradients of loss[0] * grad_out[0] (grad_out: device scalar, NULL = 1) -> d_mat (same shape as mat), d_rgb_lin, d_dl. */
+ * nero_mat_loss_bwd: gradients of loss[0] * grad_out[0] (grad_out: device scalar, NULL = 1) -> d_mat (same shape as mat), d_rgb_lin, d_dl.
+ * P == 0 (all five calls): NERO_OK, nothing launched, nothing written. */
 typedef struct {
     int rgb_l1;                 /* 0: Charbonnier sqrt(sum d^2 + 1e-3) (default), 1: L1 */
     int reg_mat, reg_change;

@@ -61,7 +61,8 @@ __global__ __launch_bounds__(LB) void head_fwd_kernel(int n5, const float* __res
     if (i >= n5) return;
     const float s = sigmoidf(raw[i]);
     // (separate multiply and add, as the tensor ops of the reference round them: a contracted fma moves the roughness by one ulp, and
-    //  the specular sample directions -- hence every light-MLP gradient -- with it)
+    //  the specular sample directions -- hence every light-MLP gradient -- with it.  What is bit for bit is this affine step on the kernel's
+    //  own sigmoid; the sigmoid itself goes through the device expf and differs from a host float32 sigmoid by an ulp on ~3 % of inputs)
     float r;
     {
 #pragma clang fp contract(off)
@@ -201,10 +202,16 @@ __global__ __launch_bounds__(LB) void loss_sum_kernel(nero_mat_loss_cfg c, int P
     a = block_sum(a, sh); b = block_sum(b, sh); h = block_sum(h, sh); d = block_sum(d, sh);
     if (threadIdx.x == 0) {
         const float inv = 1.f / (float)P;
-        loss[1] = a * inv;
-        loss[2] = b * inv + c.hinge_weight * h;
-        loss[3] = d * inv;
-        loss[0] = loss[1] + loss[2] + loss[3];
+        const float l_rgb = a * inv, l_reg = b * inv + c.hinge_weight * h, l_dl = d * inv;
+        loss[1] = l_rgb;
+        loss[2] = l_reg;
+        loss[3] = l_dl;
+        // (the total is the float32 sum of the three ROUNDED means it is reported with: contracted, a * inv would enter the first add
+        //  unrounded and loss[0] would differ from loss[1] + loss[2] + loss[3] by an ulp)
+        {
+#pragma clang fp contract(off)
+            loss[0] = l_rgb + l_reg + l_dl;
+        }
     }
 }
 __global__ __launch_bounds__(LB) void loss_bwd_kernel(nero_mat_loss_cfg c, int P, int has_reg, const float* __restrict__ mat,
@@ -246,7 +253,8 @@ int nero_mat_loss_partials(int P) { return P > 0 ? 4 * ((P + LB - 1) / LB) : 4; 
 
 int nero_mat_loss_fwd(const nero_mat_loss_cfg* cfg, int P, int has_reg, const float* mat, const float* rgb_lin, const float* dl, const float* gt,
                       float* rgb_pr, float* partials, float* loss, void* stream) {
-    if (!cfg || P <= 0 || !mat || !rgb_lin || !dl || !gt || !partials || !loss) return nero_fail(NERO_ERR_ARG, "nero_mat_loss_fwd: bad argument");
+    if (!cfg || P < 0 || !mat || !rgb_lin || !dl || !gt || !partials || !loss) return nero_fail(NERO_ERR_ARG, "nero_mat_loss_fwd: bad argument");
+    if (P == 0) return NERO_OK;                        // no point, no mean: nothing is launched, loss stays as it is
     const int nb = (P + LB - 1) / LB;
     hipLaunchKernelGGL(loss_fwd_kernel, dim3(nb), dim3(LB), 0, (hipStream_t)stream, *cfg, P, has_reg, mat, rgb_lin, dl, gt, rgb_pr, partials);
     hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(LB), 0, (hipStream_t)stream, *cfg, P, nb, partials, loss);
@@ -255,8 +263,9 @@ int nero_mat_loss_fwd(const nero_mat_loss_cfg* cfg, int P, int has_reg, const fl
 
 int nero_mat_loss_bwd(const nero_mat_loss_cfg* cfg, int P, int has_reg, const float* mat, const float* rgb_lin, const float* dl, const float* gt,
                       const float* grad_out, float* d_mat, float* d_rgb_lin, float* d_dl, void* stream) {
-    if (!cfg || P <= 0 || !mat || !rgb_lin || !dl || !gt || !d_mat || !d_rgb_lin || !d_dl)
+    if (!cfg || P < 0 || !mat || !rgb_lin || !dl || !gt || !d_mat || !d_rgb_lin || !d_dl)
         return nero_fail(NERO_ERR_ARG, "nero_mat_loss_bwd: bad argument");
+    if (P == 0) return NERO_OK;
     if (!(cfg->reg_mat && cfg->reg_change && has_reg) && has_reg)      // rows P..2P-1 of d_mat receive nothing from the kernel
         (void)hipMemsetAsync(d_mat + (size_t)5 * P, 0, sizeof(float) * 5 * (size_t)P, (hipStream_t)stream);
     hipLaunchKernelGGL(loss_bwd_kernel, dim3((P + LB - 1) / LB), dim3(LB), 0, (hipStream_t)stream, *cfg, P, has_reg, mat, rgb_lin, dl, gt, grad_out,
