@@ -191,11 +191,6 @@ int nero_mlp_backward(const nero_bwd_chain* chain /*host*/, int n_rows, void* st
  * Initial value: NERO_F16_PAIRED in the environment, default 3.  Process-wide, not thread-safe against concurrent launches.
  * (No reference counterpart: an execution detail of network/field.py's nn.Linear stacks.) */
 int nero_f16_paired(int mask);
-/* Forward chains that save nothing (no saved activations, no ReLU masks: the sampler's SDF evaluations, forward-only inference) on the
- * row-owner kernel (round 6, mlp_f16r.hip): a wave owns 32 rows and all features, activation planes in registers, weights through an LDS-DMA
- * ring.  Bit-identical results.  mask bit 0 = on for launches of >= 128 rows per CU, bit 1 = whatever the size; < 0 queries; returns the
- * previous selection (default: NERO_F16_ROWOWNER or 0). */
-int nero_f16_rowowner(int mask);
 
 /* ---- weight-gradient GEMM ------------------------------------------------------------------------------------
  * dW[n][k] (+)= sum_r D0[r][n] * B0[r][k] (+ sum_r D1[r][n] * B1[r][k]),  db[n] (+)= sum_r D0[r][n]
@@ -626,9 +621,6 @@ size_t nero_stage1_workspace_bytes(nero_stage1* h, int R);
 size_t nero_stage1_workspace_bytes_for(nero_stage1* h, int R, int n_in, int n_out, int with_sampler);
 /* sampler + render forward only (inference chunks: no nero_stage1_render_bwd on this workspace), worst case over the split */
 size_t nero_stage1_workspace_bytes_fwd(nero_stage1* h, int R);
-/* debug: (device pointer, bytes) of nine intermediates of the last nero_stage1_render_bwd -- d_geo, d_feat, d_sdf4, d_grad, dinv, ehat, adot,
- * d_alpha_inner, d_metallic_raw -- for run-to-run comparisons (scripts/r05/dbg_streams.py) */
-int nero_stage1_debug_buffers(nero_stage1* h, const void** ptrs, size_t* bytes);
 /* z_vals [R, n_samples + n_importance + n_bg_samples]; rand1 [R] / rand_bg [R, n_bg] uniform draws or NULL (no perturbation) */
 int nero_stage1_sample(nero_stage1* h, int R, const float* o, const float* d, const float* near, const float* far, const float* variance,
                        const float* rand1, const float* rand_bg, float* z_vals, void* ws, size_t ws_bytes, void* stream);

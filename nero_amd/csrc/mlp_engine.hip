@@ -811,7 +811,11 @@ __global__ void pack_weight_kernel(const float* __restrict__ W, int nrows, int l
 
 constexpr int DW_MAX_SLICES = 256;          // one row slice per CU
 constexpr int DW_BATCH_SLICES = 1024 + NERO_DW_BATCH_MAX;     // upper bound of slices x jobs of one batched launch (>= DW_MAX_SLICES)
-constexpr int DW_BATCH_ROWS = 131072;                          // batch only below this row count: above it a job alone fills the chip
+// the batching policy of nero_dw_gemm_batch (constants since round 3; the sweep: profiles/r04_dw_batch_sweep.txt)
+constexpr int DW_BATCH_ROWS = 131072;                          // the boundary between its small-row and its large-row regime
+constexpr int DW_SMALL_TOTAL = 256;                            // small rows: slices over a whole group of up to NERO_DW_BATCH_MAX jobs
+constexpr int DW_BIG_TOTAL = 256, DW_BIG_GROUP = 8;            // large rows: slices over a whole group, jobs per group
+static_assert(DW_BIG_TOTAL + NERO_DW_BATCH_MAX + 8 <= DW_BATCH_SLICES && DW_BIG_GROUP <= NERO_DW_BATCH_MAX, "nero_dw_workspace_floats");
 
 inline int dw_rows_per_slice(int n_rows) {
     int rps = (n_rows + DW_MAX_SLICES - 1) / DW_MAX_SLICES;
@@ -919,32 +923,14 @@ int nero_mlp_backward(const nero_bwd_chain* ch, int n_rows, void* stream) {
     return nero_check_launch("nero_mlp_backward");
 }
 
-// the batching policy of nero_dw_gemm_batch (shared with the workspace query below)
-struct DwBatchPolicy { int rows, big_total, big_group, small_total; };
-static const DwBatchPolicy& dw_batch_policy() {
-    static DwBatchPolicy P = {-1, 256, 8, 256};
-    if (P.rows < 0) {
-        const char* e = getenv("NERO_DW_BATCH_ROWS"); P.rows = e ? atoi(e) : DW_BATCH_ROWS;
-        e = getenv("NERO_DW_BATCH_TOTAL"); if (e) P.big_total = atoi(e);
-        e = getenv("NERO_DW_BATCH_GROUP"); if (e) P.big_group = atoi(e);
-        e = getenv("NERO_DW_SMALL_TOTAL"); if (e) P.small_total = atoi(e);
-        P.small_total = P.small_total < 64 ? 64 : (P.small_total > 1024 ? 1024 : P.small_total);
-        P.big_group = P.big_group < 0 ? 0 : (P.big_group > NERO_DW_BATCH_MAX ? NERO_DW_BATCH_MAX : P.big_group);
-        P.big_total = P.big_total < 16 ? 16 : (P.big_total > 1024 ? 1024 : P.big_total);
-    }
-    return P;
-}
-
 int nero_dw_workspace_floats(int n_rows) {
     // Partial matrices ([n_pad][k_pad] + n_pad floats, at most 256 x 256 + 256) of one launch: per-job launches write 256, small-row batches
-    // up to 1024 + 12, large-row batches `big_total` + a few.  The bound must be MONOTONIC in n_rows -- callers size one buffer for the
+    // up to 1024 + 12, large-row batches DW_BIG_TOTAL + a few (fewer: the static_assert above).  The bound must be MONOTONIC in n_rows -- callers size one buffer for the
     // largest row count of a step and hand it to launches over fewer rows, which may sit in the small-row regime -- so it is the
     // maximum over the regimes whatever n_rows is (a round-4 attempt to size it by regime let a 100 k-row launch overrun a buffer sized
     // for 300 k rows: found by tests/test_determinism.py).  One 4 x 256 (+4) partial per 128-row block for nero_head_dw.
     const int rows = n_rows < 1 ? 1 : n_rows;
-    const DwBatchPolicy& P = dw_batch_policy();
-    long mats = DW_BATCH_SLICES;
-    if (P.big_total + NERO_DW_BATCH_MAX + 8 > mats) mats = P.big_total + NERO_DW_BATCH_MAX + 8;
+    const long mats = DW_BATCH_SLICES;
     const long head_blocks = (rows + 127) / 128;
     const long a = mats * (256 * 256 + 256), b = head_blocks * (4 * NERO_HID + 4);
     return (int)(a > b ? a : b);
@@ -994,13 +980,9 @@ int nero_dw_gemm_batch(const nero_dw_job* jobs, int n_jobs, int n_rows, float* p
     // workgroup streams ~9 k rows of one job, and the group writes 8 x 32 partial matrices instead of 8 x 256 -- a job alone spent a
     // fifth of its HBM traffic (67 MB written + read back for 610 MB of operands) and ~11 us of dirty-line write-back at the kernel
     // boundary on them: 31.28 -> 30.75 ms per step at 4096 rays (same box, profiles/r04_dw_batch_sweep.txt).
-    // Experiment switches: NERO_DW_BATCH_ROWS (the regime boundary), NERO_DW_BATCH_TOTAL / NERO_DW_BATCH_GROUP (slices per group / jobs
-    // per group of the large-row regime; 0 rows = the old per-job launches).
-    const DwBatchPolicy& POL = dw_batch_policy();
-    const int batch_rows = POL.rows, big_total = POL.big_total, big_group = POL.big_group;
-    const bool big = rows >= batch_rows;
-    const int batch_total = big ? big_total : POL.small_total, batch_group = big ? big_group : NERO_DW_BATCH_MAX;
-    if (!f16 || n_jobs < 2 || batch_group < 1) {                 // the per-job path: one launch (+ reduction) per job
+    const bool big = rows >= DW_BATCH_ROWS;
+    const int batch_total = big ? DW_BIG_TOTAL : DW_SMALL_TOTAL, batch_group = big ? DW_BIG_GROUP : NERO_DW_BATCH_MAX;
+    if (!f16 || n_jobs < 2) {                                    // the per-job path: one launch (+ reduction) per job
         for (int i = 0; i < n_jobs; ++i) {
             const int rc = nero_dw_gemm(jobs + i, n_rows, partials, stream);
             if (rc != NERO_OK) return rc;

@@ -54,9 +54,9 @@ __device__ __forceinline__ void store_ws4(float* dst, float4 v) {
 constexpr int SCRP_ROWS = 16;
 constexpr int SCRP_BYTES = SCRP_ROWS * SCR_LD * 4;     // 2304 B per wave: store-transposition scratch, 16 rows at a time
 
-// accumulator-layout 32x32 block -> row-major global store, ROWS (16 or 8) rows at a time through the wave-private scratch
-template <int ROWS>
-__device__ __forceinline__ void acc_to_global_rows(float* scr, const float4 (&q)[4], float* __restrict__ gblock, int lane) {
+// accumulator-layout 32x32 block -> row-major global store, 16 rows at a time through the wave-private scratch
+__device__ __forceinline__ void acc_to_global16(float* scr, const float4 (&q)[4], float* __restrict__ gblock, int lane) {
+    constexpr int ROWS = SCRP_ROWS;
     const int i = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int p = 0; p < 32 / ROWS; ++p) {
@@ -72,9 +72,6 @@ __device__ __forceinline__ void acc_to_global_rows(float* scr, const float4 (&q)
         }
         __builtin_amdgcn_wave_barrier();
     }
-}
-__device__ __forceinline__ void acc_to_global16(float* scr, const float4 (&q)[4], float* __restrict__ gblock, int lane) {
-    acc_to_global_rows<16>(scr, q, gblock, lane);
 }
 
 // ---- LDS-DMA ----------------------------------------------------------------------------------------------------------------
@@ -332,34 +329,7 @@ __device__ __forceinline__ void gemm_f16x3(f32x16 (&aH)[2], const uint4* wp, con
     gemm_f16x3_loop(aH, wp, xp, half_bytes, plane_bytes, n, false, wa, wb, wc);
 }
 
-
-// lean k-loop for the kernels that run FOUR waves per SIMD (<= 128 registers per wave; mlp_f16p.hip, NW = 8): weights two steps ahead in a
-// ring of three register sets, fragments one step ahead -- 56 operand registers instead of 64 + 32; the other three waves of the SIMD cover
-// what the shallower ring no longer does.  Same products in the same order as gemm_f16x3_loop.
-__device__ __forceinline__ void gemm_f16x3_lean(f32x16 (&aH)[2], const uint4* wp, const char* xp, int half_bytes,
-                                                int plane_bytes, int n) {
-    if (n <= 0) return;
-    WF w0, w1, w2;
-    XF xa, xb;
-    const int last = n - 1;
-#define NERO_CL(c) ((c) < last ? (c) : last)
-    load_w(w0, wp, 0);
-    load_w(w1, wp, NERO_CL(1));
-    load_x(xa, xp, half_bytes, plane_bytes, 0);
-    NERO_FENCE();
-    for (int c = 0; c < n; c += 6) {
-        load_w(w2, wp, NERO_CL(c + 2)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 1)); NERO_FENCE();
-        ops_compute(aH, w0, xa); NERO_FENCE();
-        if (c + 1 < n) { load_w(w0, wp, NERO_CL(c + 3)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 2)); NERO_FENCE(); ops_compute(aH, w1, xb); NERO_FENCE(); }
-        if (c + 2 < n) { load_w(w1, wp, NERO_CL(c + 4)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 3)); NERO_FENCE(); ops_compute(aH, w2, xa); NERO_FENCE(); }
-        if (c + 3 < n) { load_w(w2, wp, NERO_CL(c + 5)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 4)); NERO_FENCE(); ops_compute(aH, w0, xb); NERO_FENCE(); }
-        if (c + 4 < n) { load_w(w0, wp, NERO_CL(c + 6)); load_x(xb, xp, half_bytes, plane_bytes, NERO_CL(c + 5)); NERO_FENCE(); ops_compute(aH, w1, xa); NERO_FENCE(); }
-        if (c + 5 < n) { load_w(w1, wp, NERO_CL(c + 7)); load_x(xa, xp, half_bytes, plane_bytes, NERO_CL(c + 6)); NERO_FENCE(); ops_compute(aH, w2, xb); NERO_FENCE(); }
-    }
-#undef NERO_CL
-}
-
-// dual-tile k-loop of the paired kernels (mlp_f16p.hip, NW = 4): a wave that owns TWO feature tiles (weights wp0 / wp1) walks the k-steps
+// dual-tile k-loop of the paired kernels (mlp_f16p.hip): a wave that owns TWO feature tiles (weights wp0 / wp1) walks the k-steps
 // once.  One k-step = four activation-fragment reads (shared by both tiles: the second tile's fragments are byte for byte the first's),
 // four weight loads, twelve MFMAs -- half the LDS operand reads, trip count, wait counts and fences of two gemm_f16x3_loop passes, the
 // same weight stream and MFMA count.  Every accumulator sees the products of ops_compute in the same order over ascending k, so the

@@ -33,9 +33,9 @@ namespace {
 
 #include "mlp_f16_util.h"
 
-// NW = waves per workgroup.  4 (round 2 / 5): wave w computes the feature tiles w and w + 4, 256 registers per wave,
-// two waves per SIMD.  8 (round 6): wave w computes tile w only, at most 128 registers per wave, FOUR waves per SIMD from two workgroups --
-// the occupancy at which scripts/probe/rowowner_probe.hip measures today's layer structure 13 % faster than with one workgroup per CU.
+// waves per workgroup: wave w computes the feature tiles w and w + NW, 256 registers per wave, two waves per SIMD.  (Eight waves of one
+// tile each, 128 registers per wave, measured slower and spilled: docs/experiments.md 14.)
+constexpr int NW = 4;
 
 struct LdsP { char* actp; float* rs_main; float* rs_aux; float* rmax; float* wsc; char* scr; };
 __device__ __forceinline__ LdsP carve_p(char* smem) {
@@ -48,7 +48,7 @@ __device__ __forceinline__ LdsP carve_p(char* smem) {
     l.scr = reinterpret_cast<char*>(l.wsc + 32);
     return l;
 }
-inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + 4 * SCRP_BYTES; }      // 79488 (NW = 8: 8 x 8-row scratch, the same)
+inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + NW * SCRP_BYTES; }     // 79488
 
 // the per-lane addresses of the chain's OUTPUTS (d_init, d_aux: written once, by the first layer) are formed from a row index the compiler
 // cannot see through: otherwise it hoists them out of the layer loop and they occupy registers -- or scratch -- through every GEMM
@@ -56,7 +56,6 @@ inline int p_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + 4 * SCRP_BYTES
 struct Ctx { LdsP S; int wave, lane, i, h, row0, n_rows; float* scr; };
 
 // rows [row0, row0+64) x first k columns of a row-major fp32 matrix -> scaled plane pairs + per-row scale (NW threads per row)
-template <int NW>
 __device__ __forceinline__ void load_planes_scaled_p(char* planes, float* rs, const float* __restrict__ src, int ld, int k, int row0,
                                                      int n_rows, int tid) {
     constexpr int NV = 64 / NW;
@@ -74,7 +73,7 @@ __device__ __forceinline__ void load_planes_scaled_p(char* planes, float* rs, co
         if (c4 < k) v[j] = *reinterpret_cast<const float4*>(rowp + c4);
         m = fmaxf(m, amax4(v[j]));
     }
-    m = NW == 8 ? max_8lanes(m) : max_4lanes(m);
+    m = max_4lanes(m);
     const int e = scale_exp(m);
     const float inv = pow2i(-e);
 #pragma unroll
@@ -84,7 +83,6 @@ __device__ __forceinline__ void load_planes_scaled_p(char* planes, float* rs, co
 }
 
 // per-row scale of the aux operand (its planes are built on the fly, gemm_aux_global)
-template <int NW>
 __device__ __forceinline__ void aux_row_scales_p(float* rs, const float* __restrict__ src, int ld, int k, int row0, int n_rows, int tid) {
     const int r = tid / NW, q = tid % NW;
     int gr = row0 + r;
@@ -92,7 +90,7 @@ __device__ __forceinline__ void aux_row_scales_p(float* rs, const float* __restr
     const float* rowp = src + (size_t)gr * ld;
     float m = 0.f;
     for (int c4 = 4 * q; c4 < k; c4 += 4 * NW) m = fmaxf(m, amax4(*reinterpret_cast<const float4*>(rowp + c4)));
-    m = NW == 8 ? max_8lanes(m) : max_4lanes(m);
+    m = max_4lanes(m);
     if (q == 0) rs[r] = pow2i(scale_exp(m));
 }
 
@@ -177,7 +175,6 @@ __device__ __forceinline__ void gemm_aux_global2(f32x16 (&aH0)[2], f32x16 (&aH1)
 }
 
 // aux part then main part of the feature tiles t and t + NW together; the units U are those of gemm_tile (they do not depend on the tile)
-template <int NW>
 __device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aH1)[2], float (&U)[2], const Ctx& c,
                                            int t, const float* w_main, const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx,
                                            const float* aux, int ld_aux, int k_aux_cols) {
@@ -208,7 +205,6 @@ __device__ __forceinline__ void gemm_tile2(f32x16 (&aH0)[2], f32x16 (&aH1)[2], f
 }
 
 // aux part (its own unit) then main part of one feature tile; U = unit of the result per 32-row half
-template <int NW>
 __device__ __forceinline__ void gemm_tile(f32x16 (&aH)[2], float (&U)[2], const Ctx& c, int t, const float* w_main,
                                           const float* w_aux, float wsc_main, float wsc_aux, int sm, int sx, const float* aux, int ld_aux,
                                           int k_aux_cols) {
@@ -231,13 +227,11 @@ __device__ __forceinline__ void gemm_tile(f32x16 (&aH)[2], float (&U)[2], const 
         U[0] = u0;
         U[1] = u1;
         const uint4* wp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_main) + HDR_BYTES) + (size_t)t * sm * 128 + c.lane;
-        if (NW == 8) gemm_f16x3_lean(aH, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
-        else gemm_f16x3(aH, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
+        gemm_f16x3(aH, wp, c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, sm);
     }
 }
 
-// VALU head on the current activation planes (8 threads per row; NW = 4: two passes of 32 rows)
-template <int NW>
+// VALU head on the current activation planes (8 threads per row: two passes of 32 rows)
 __device__ __forceinline__ void eval_head_p(const char* planes, const float* rs, const float* __restrict__ w, const float* __restrict__ b,
                                             float* __restrict__ out, int n_head, int hk, int row0, int tid) {
     const int q = tid & 7;
@@ -267,7 +261,6 @@ __device__ __forceinline__ void eval_head_p(const char* planes, const float* rs,
 
 // shared tail: barrier (row maxima of all 8 tiles visible, every wave done reading the input planes), rescale + store the two
 // tiles of this wave as plane pairs, new row scales, barrier
-template <int NW>
 __device__ __forceinline__ void commit_planes_p(const Ctx& c, const float4 (&v0)[2][4], const float4 (&v1)[2][4], bool live0, bool live1) {
     __syncthreads();
     const int e0 = scale_exp(row_max8(c.S.rmax, c.i)), e1 = scale_exp(row_max8(c.S.rmax, 32 + c.i));
@@ -280,7 +273,7 @@ __device__ __forceinline__ void commit_planes_p(const Ctx& c, const float4 (&v0)
             store_planes4h(dst + 32 * SA + 16 * g, PLANE_A, scale4(v0[1][g], inv1));
         }
     }
-    if (NW == 4 && live1) {
+    if (live1) {
         char* dst = c.S.actp + c.i * SA + (32 * (c.wave + NW) + 4 * c.h) * 2;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -292,7 +285,6 @@ __device__ __forceinline__ void commit_planes_p(const Ctx& c, const float4 (&v0)
     __syncthreads();
 }
 
-template <int NW>
 __device__ __forceinline__ Ctx make_ctx(char* smem, int n_rows) {
     Ctx c;
     c.S = carve_p(smem);
@@ -302,7 +294,7 @@ __device__ __forceinline__ Ctx make_ctx(char* smem, int n_rows) {
     c.h = c.lane >> 5;
     c.row0 = blockIdx.x * 64;
     c.n_rows = n_rows;
-    c.scr = reinterpret_cast<float*>(c.S.scr + c.wave * (NW == 8 ? SCRP_BYTES / 2 : SCRP_BYTES));     // 8 / 16 rows at a time
+    c.scr = reinterpret_cast<float*>(c.S.scr + c.wave * SCRP_BYTES);     // 16 rows at a time
     return c;
 }
 
@@ -317,7 +309,6 @@ __device__ __forceinline__ void fwd_load_bias(float4 (&bq)[4], const nero_fwd_la
 }
 
 // epilogue of one feature tile: bias + activation -> val, row-major save, ReLU sign words, row maxima
-template <int NW>
 __device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
                                              const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4], float (&m)[2] PH_PARAM) {
     if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, bq, U, val, m);
@@ -326,8 +317,8 @@ __device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx&
     PH(3);
     if (L.save) {
         float* sblock = L.save + (size_t)c.row0 * NERO_HID + 32 * t;
-        acc_to_global_rows<64 / NW>(c.scr, val[0], sblock, c.lane);
-        acc_to_global_rows<64 / NW>(c.scr, val[1], sblock + (size_t)32 * NERO_HID, c.lane);
+        acc_to_global16(c.scr, val[0], sblock, c.lane);
+        acc_to_global16(c.scr, val[1], sblock + (size_t)32 * NERO_HID, c.lane);
     }
     if (L.relu_mask) {                              // sign bits of this lane's 2 x 16 outputs -> one word per (row, tile)
 #pragma unroll
@@ -348,7 +339,6 @@ __device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx&
     PH(4);
 }
 
-template <int NW>
 __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fwd_layer& L, int l, const Ctx& c, int t, float4 (&val)[2][4],
                                          float (&m)[2] PH_PARAM) {
     m[0] = m[1] = 0.f;
@@ -356,13 +346,12 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
         f32x16 aH[2];
         zero2(aH);
         float4 bq[4];
-        if (NW == 4) fwd_load_bias(bq, L, c, t);        // (NW = 8: behind the GEMM -- 16 registers its 128 have no room for)
+        fwd_load_bias(bq, L, c, t);
         float U[2] = {1.f, 1.f};
         PH(1);
-        gemm_tile<NW>(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
-        if (NW == 8) { NERO_FENCE(); fwd_load_bias(bq, L, c, t); }
+        gemm_tile(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
         PH(2);
-        fwd_epilogue<NW>(L, c, t, aH, bq, U, val, m PH_ARG);
+        fwd_epilogue(L, c, t, aH, bq, U, val, m PH_ARG);
     } else {
         publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
         PH(4);
@@ -371,7 +360,6 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
 
 // the feature tiles t and t + NW of one wave (both exist): ONE walk over the k-steps for both (gemm_tile2), then the two epilogues one
 // after the other -- an accumulator set becomes its `val` registers only when its epilogue runs
-template <int NW>
 __device__ __forceinline__ void fwd_tile_pair(const nero_fwd_chain& ch, const nero_fwd_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
                                               float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2] PH_PARAM) {
     f32x16 aH0[2], aH1[2];
@@ -381,19 +369,18 @@ __device__ __forceinline__ void fwd_tile_pair(const nero_fwd_chain& ch, const ne
     fwd_load_bias(bq, L, c, t);
     float U[2] = {1.f, 1.f};
     PH(1);
-    gemm_tile2<NW>(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+    gemm_tile2(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
                    ch.ld_aux, ch.k_aux);
     float4 bq1[4];                                     // (behind the GEMM: its round trip passes under the first tile's epilogue)
     fwd_load_bias(bq1, L, c, t + NW);
     PH(2);
-    fwd_epilogue<NW>(L, c, t, aH0, bq, U, v0, m0 PH_ARG);
-    fwd_epilogue<NW>(L, c, t + NW, aH1, bq1, U, v1, m1 PH_ARG);
+    fwd_epilogue(L, c, t, aH0, bq, U, v0, m0 PH_ARG);
+    fwd_epilogue(L, c, t + NW, aH1, bq1, U, v1, m1 PH_ARG);
 }
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain ch, int n_rows) {
+__global__ __launch_bounds__(NW * 64, 2) void fwd_p_kernel(nero_fwd_chain ch, int n_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Ctx c = make_ctx<NW>(smem, n_rows);
+    const Ctx c = make_ctx(smem, n_rows);
     const int tid = threadIdx.x;
     PH_DECL;
 #ifdef F16_PHASE_TIMING
@@ -401,24 +388,24 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
 #endif
     WscRegs wr;
     wsc_request(wr, ch, [](const nero_fwd_layer& Lx, const float*& pm, const float*& pa) { pm = Lx.k_main > 0 && Lx.n_tiles > 0 ? Lx.w_main : nullptr; pa = Lx.k_aux > 0 && Lx.n_tiles > 0 ? Lx.w_aux : nullptr; });
-    if (ch.init) load_planes_scaled_p<NW>(c.S.actp, c.S.rs_main, ch.init, ch.ld_init, ch.k_init, c.row0, n_rows, tid);
-    if (ch.aux) aux_row_scales_p<NW>(c.S.rs_aux, ch.aux, ch.ld_aux, ch.k_aux, c.row0, n_rows, tid);
+    if (ch.init) load_planes_scaled_p(c.S.actp, c.S.rs_main, ch.init, ch.ld_init, ch.k_init, c.row0, n_rows, tid);
+    if (ch.aux) aux_row_scales_p(c.S.rs_aux, ch.aux, ch.ld_aux, ch.k_aux, c.row0, n_rows, tid);
     wsc_commit(c.S.wsc, wr, tid);
     __syncthreads();
     PH(0);
     for (int l = 0; l < ch.n_layers; ++l) {
         const nero_fwd_layer L = load_layer(ch, l);
-        if (L.n_head > 0) eval_head_p<NW>(c.S.actp, c.S.rs_main, L.head_w, L.head_b, L.head_out, L.n_head, L.head_k, c.row0, tid);
+        if (L.n_head > 0) eval_head_p(c.S.actp, c.S.rs_main, L.head_w, L.head_b, L.head_out, L.n_head, L.head_k, c.row0, tid);
         if (L.n_tiles == 0) continue;
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
         // (wave-uniform: no second tile for n_tiles <= 4 -- the 128-wide layers -- and for wave 3 of the 217-wide SDF layer)
-        if (NW == 4 && c.wave + NW < L.n_tiles) fwd_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1 PH_ARG);
+        if (c.wave + NW < L.n_tiles) fwd_tile_pair(ch, L, l, c, c.wave, v0, v1, m0, m1 PH_ARG);
         else {
-            fwd_tile<NW>(ch, L, l, c, c.wave, v0, m0 PH_ARG);
-            if (NW == 4) fwd_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
+            fwd_tile(ch, L, l, c, c.wave, v0, m0 PH_ARG);
+            fwd_tile(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
         }
-        commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
+        commit_planes_p(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
         PH(5);
     }
 #ifdef F16_PHASE_TIMING
@@ -432,7 +419,6 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void fwd_p_kernel(nero_fwd_chain c
 // tangent chain (softplus networks):  adot_l = s_l * (W_l adot_{l-1}),  inj_l = gbar_l * beta (1-s_l) * zdot_l
 // ---------------------------------------------------------------------------------------------------------------------
 // epilogue of one feature tile of a tangent layer: adot = s * zdot (and the finished injection when the chain asks for it), row maxima
-template <int NW>
 __device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
                                              const float (&U)[2], float4 (&val)[2][4], float (&m)[2]) {
     const size_t goff = (size_t)(c.row0 + c.i) * NERO_HID + 32 * t + 4 * c.h;     // + r*32*HID + 8g
@@ -474,21 +460,20 @@ __device__ __forceinline__ void tan_epilogue(const nero_tan_layer& L, const Ctx&
             adq[g] = live ? ad : make_float4(0.f, 0.f, 0.f, 0.f);
             ijq[g] = ij;
         }
-        acc_to_global_rows<64 / NW>(scr, adq, L.adot + boff + (size_t)r * 32 * NERO_HID, c.lane);
-        if (want_inj) acc_to_global_rows<64 / NW>(scr, ijq, L.inj + boff + (size_t)r * 32 * NERO_HID, c.lane);
+        acc_to_global16(scr, adq, L.adot + boff + (size_t)r * 32 * NERO_HID, c.lane);
+        if (want_inj) acc_to_global16(scr, ijq, L.inj + boff + (size_t)r * 32 * NERO_HID, c.lane);
     }
     publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
 }
 
-template <int NW>
 __device__ __forceinline__ void tan_tile(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&val)[2][4],
                                          float (&m)[2]) {
     if (t < L.n_tiles) {
         f32x16 aH[2];
         zero2(aH);
         float U[2] = {1.f, 1.f};
-        gemm_tile<NW>(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
-        tan_epilogue<NW>(L, c, t, aH, U, val, m);
+        gemm_tile(aH, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux, ch.ld_aux, ch.k_aux);
+        tan_epilogue(L, c, t, aH, U, val, m);
     } else {
         m[0] = m[1] = 0.f;
         publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
@@ -496,40 +481,38 @@ __device__ __forceinline__ void tan_tile(const nero_tan_chain& ch, const nero_ta
 }
 
 // both feature tiles of a wave in one walk over the k-steps (fwd_tile_pair)
-template <int NW>
 __device__ __forceinline__ void tan_tile_pair(const nero_tan_chain& ch, const nero_tan_layer& L, int l, const Ctx& c, int t, float4 (&v0)[2][4],
                                               float4 (&v1)[2][4], float (&m0)[2], float (&m1)[2]) {
     f32x16 aH0[2], aH1[2];
     zero2(aH0);
     zero2(aH1);
     float U[2] = {1.f, 1.f};
-    gemm_tile2<NW>(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
+    gemm_tile2(aH0, aH1, U, c, t, L.w_main, L.w_aux, c.S.wsc[2 * l], c.S.wsc[2 * l + 1], L.k_main >> 4, L.k_aux >> 4, ch.aux,
                    ch.ld_aux, ch.k_aux);
-    tan_epilogue<NW>(L, c, t, aH0, U, v0, m0);
-    tan_epilogue<NW>(L, c, t + NW, aH1, U, v1, m1);
+    tan_epilogue(L, c, t, aH0, U, v0, m0);
+    tan_epilogue(L, c, t + NW, aH1, U, v1, m1);
 }
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64, NW / 2) void tan_p_kernel(nero_tan_chain ch, int n_rows) {
+__global__ __launch_bounds__(NW * 64, 2) void tan_p_kernel(nero_tan_chain ch, int n_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Ctx c = make_ctx<NW>(smem, n_rows);
+    const Ctx c = make_ctx(smem, n_rows);
     const int tid = threadIdx.x;
     WscRegs wr;
     wsc_request(wr, ch, [](const nero_tan_layer& Lx, const float*& pm, const float*& pa) { pm = Lx.k_main > 0 ? Lx.w_main : nullptr; pa = Lx.k_aux > 0 ? Lx.w_aux : nullptr; });
-    if (ch.init) load_planes_scaled_p<NW>(c.S.actp, c.S.rs_main, ch.init, ch.ld_init, ch.k_init, c.row0, n_rows, tid);
-    if (ch.aux) aux_row_scales_p<NW>(c.S.rs_aux, ch.aux, ch.ld_aux, ch.k_aux, c.row0, n_rows, tid);
+    if (ch.init) load_planes_scaled_p(c.S.actp, c.S.rs_main, ch.init, ch.ld_init, ch.k_init, c.row0, n_rows, tid);
+    if (ch.aux) aux_row_scales_p(c.S.rs_aux, ch.aux, ch.ld_aux, ch.k_aux, c.row0, n_rows, tid);
     wsc_commit(c.S.wsc, wr, tid);
     __syncthreads();
     for (int l = 0; l < ch.n_layers; ++l) {
         const nero_tan_layer L = load_layer(ch, l);
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
-        if (NW == 4 && c.wave + NW < L.n_tiles) tan_tile_pair<NW>(ch, L, l, c, c.wave, v0, v1, m0, m1);
+        if (c.wave + NW < L.n_tiles) tan_tile_pair(ch, L, l, c, c.wave, v0, v1, m0, m1);
         else {
-            tan_tile<NW>(ch, L, l, c, c.wave, v0, m0);
-            if (NW == 4) tan_tile<NW>(ch, L, l, c, c.wave + NW, v1, m1);
+            tan_tile(ch, L, l, c, c.wave, v0, m0);
+            tan_tile(ch, L, l, c, c.wave + NW, v1, m1);
         }
-        commit_planes_p<NW>(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
+        commit_planes_p(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
     }
 }
 
@@ -550,7 +533,7 @@ __device__ __forceinline__ void combine_acc(float4 (&gq)[2][4], const f32x16 (&a
 // (nero_bwd_layer.mask_prev) or the identity: the material / light predictors and the NeRF++ networks.  Compiled without the softplus path the
 // tile keeps 2 sign words instead of 32 activation registers, and the kernel fits its 256 registers without the 14-16 spills of the generic
 // bwd_p_kernel (which lost to the 512-thread kernel for exactly that reason).
-template <int NW, bool MASKS>
+template <bool MASKS>
 __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bwd_layer& L, int l, const Ctx& c, int t, bool first, float rs0, float rs1,
                                          float4 (&val)[2][4], float (&m)[2]) {
     m[0] = m[1] = 0.f;
@@ -589,8 +572,7 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
         if (ch.d_aux && L.w_aux_t && t < L.k_aux_tiles) {
             zero2(aH);
             const float wsc = c.S.wsc[2 * l + 1];
-            if (NW == 8) gemm_f16x3_lean(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
-            else gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
+            gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
                        xp, 32 * SA, PLANE_A, steps);
             const float u[2] = {wsc * rs0, wsc * rs1};
             combine_acc(gq, aH, u);
@@ -610,8 +592,7 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
         NERO_FENCE();
         zero2(aH);
         const float wsc = c.S.wsc[2 * l];
-        if (NW == 8) gemm_f16x3_lean(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane, xp, 32 * SA, PLANE_A, steps);
-        else gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
+        gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
                    xp, 32 * SA, PLANE_A, steps);
         const float u[2] = {wsc * rs0, wsc * rs1};
         combine_acc(gq, aH, u);
@@ -655,20 +636,20 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
     else if (!MASKS && L.act_prev == NERO_ACT_SOFTPLUS100) bwd_values_h<NERO_ACT_SOFTPLUS100, false>(gq, pa, goff, has_inj, L, c.row0, c.i, fbase, c.n_rows, val, m, ijp);
     else bwd_values_h<NERO_ACT_NONE, false>(gq, pa, goff, has_inj, L, c.row0, c.i, fbase, c.n_rows, val, m, ijp);
     if (L.delta_prev) {
-        acc_to_global_rows<64 / NW>(c.scr, val[0], L.delta_prev + boff, c.lane);
-        acc_to_global_rows<64 / NW>(c.scr, val[1], L.delta_prev + boff + (size_t)32 * NERO_HID, c.lane);
+        acc_to_global16(c.scr, val[0], L.delta_prev + boff, c.lane);
+        acc_to_global16(c.scr, val[1], L.delta_prev + boff + (size_t)32 * NERO_HID, c.lane);
     }
     publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
 }
 
-template <int NW, bool MASKS>
-__global__ __launch_bounds__(NW * 64, NW / 2) void bwd_p_kernel(nero_bwd_chain ch, int n_rows) {
+template <bool MASKS>
+__global__ __launch_bounds__(NW * 64, 2) void bwd_p_kernel(nero_bwd_chain ch, int n_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Ctx c = make_ctx<NW>(smem, n_rows);
+    const Ctx c = make_ctx(smem, n_rows);
     const int tid = threadIdx.x;
     WscRegs wr;
     wsc_request(wr, ch, [](const nero_bwd_layer& Lx, const float*& pm, const float*& pa) { pm = Lx.n_out > 0 ? Lx.w_main_t : nullptr; pa = Lx.n_out > 0 ? Lx.w_aux_t : nullptr; });
-    if (ch.dy) load_planes_scaled_p<NW>(c.S.actp, c.S.rs_main, ch.dy, ch.ld_dy, ch.k_dy, c.row0, n_rows, tid);
+    if (ch.dy) load_planes_scaled_p(c.S.actp, c.S.rs_main, ch.dy, ch.ld_dy, ch.k_dy, c.row0, n_rows, tid);
     else {
         for (int idx = tid; idx < 2 * PLANE_A / 16; idx += NW * 64) reinterpret_cast<uint4*>(c.S.actp)[idx] = make_uint4(0u, 0u, 0u, 0u);
         if (tid < 64) c.S.rs_main[tid] = 1.f;
@@ -683,18 +664,16 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void bwd_p_kernel(nero_bwd_chain c
         const float rs0 = c.S.rs_main[c.i], rs1 = c.S.rs_main[32 + c.i];
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
-        bwd_tile<NW, MASKS>(ch, L, l, c, c.wave, first, rs0, rs1, v0, m0);
-        if (NW == 4) bwd_tile<NW, MASKS>(ch, L, l, c, c.wave + NW, first, rs0, rs1, v1, m1);
+        bwd_tile<MASKS>(ch, L, l, c, c.wave, first, rs0, rs1, v0, m0);
+        bwd_tile<MASKS>(ch, L, l, c, c.wave + NW, first, rs0, rs1, v1, m1);
         if (first) break;
-        commit_planes_p<NW>(c, v0, v1, c.wave < L.k_main_tiles, c.wave + NW < L.k_main_tiles);
+        commit_planes_p(c, v0, v1, c.wave < L.k_main_tiles, c.wave + NW < L.k_main_tiles);
     }
 }
 
 }  // namespace
 
 // ---- host side (dispatched from mlp_engine.hip) ------------------------------------------------------------------------------
-#include <stdio.h>
-#include <stdlib.h>
 #ifdef F16_PHASE_TIMING
 extern "C" int nero_debug_phases_p(unsigned long long* out16, int reset) {
     hipDeviceSynchronize();
@@ -703,42 +682,16 @@ extern "C" int nero_debug_phases_p(unsigned long long* out16, int reset) {
     return 0;
 }
 #endif
-static void report_occupancy(const void* f, const char* name) {      // NERO_DEBUG_OCC=1: resident workgroups per CU as the runtime sees it
-    if (!getenv("NERO_DEBUG_OCC")) return;
-    for (int lds = 32768; lds <= 81920; lds += 2048 * 3) {
-        int nb = -1;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, 256, lds);
-        fprintf(stderr, "[nero] %s: dynamic LDS %d -> %d workgroups per CU (err %d)\n", name, lds, nb, (int)e);
-    }
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, 256, p_lds_bytes());
-    fprintf(stderr, "[nero] %s: dynamic LDS %d -> %d workgroups per CU\n", name, p_lds_bytes(), nb);
-}
-// waves per workgroup of the paired kernels: NERO_F16_PW = 4 | 8, per pass as a decimal digit string "fwd tan bwd" (e.g. 848)
-constexpr int NERO_F16_PW_DEFAULT = 4;
-static int nero_pw(int kind) {
-    static int sel[3] = {-1, -1, -1};
-    if (sel[0] < 0) {
-        const char* e = getenv("NERO_F16_PW");
-        int v = e ? atoi(e) : NERO_F16_PW_DEFAULT;
-        if (v < 10) v = v * 111;
-        sel[0] = (v / 100) % 10 == 8 ? 8 : 4; sel[1] = (v / 10) % 10 == 8 ? 8 : 4; sel[2] = v % 10 == 8 ? 8 : 4;
-    }
-    return sel[kind];
-}
-template <class K, class CH> static void launch_p(K k4, K k8, int nw, const CH* ch, int n_rows, hipStream_t stream) {
-    NERO_ONCE(hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, p_lds_bytes()));
-    NERO_ONCE(hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, p_lds_bytes()));
+template <auto K, class CH> static void launch_p(const CH* ch, int n_rows, hipStream_t stream) {      // (K a template argument: one NERO_ONCE per kernel)
+    NERO_ONCE(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, p_lds_bytes()));
     nero_prof_mark_paired();
-    if (nw == 8) hipLaunchKernelGGL(k8, dim3((n_rows + 63) / 64), dim3(512), p_lds_bytes(), stream, *ch, n_rows);
-    else hipLaunchKernelGGL(k4, dim3((n_rows + 63) / 64), dim3(256), p_lds_bytes(), stream, *ch, n_rows);
+    hipLaunchKernelGGL(K, dim3((n_rows + 63) / 64), dim3(NW * 64), p_lds_bytes(), stream, *ch, n_rows);
 }
 int nero_f16p_forward(const nero_fwd_chain* ch, int n_rows, hipStream_t stream) {
     for (int l = 0; l < ch->n_layers; ++l)
         if ((ch->layer[l].k_main | ch->layer[l].k_aux) & 15)
             return nero_fail(NERO_ERR_ARG, "nero_mlp_forward(f16x3p): k_main / k_aux must be multiples of 16");
-    NERO_ONCE(report_occupancy((const void*)fwd_p_kernel<4>, "fwd_p_kernel<4>"));
-    launch_p(fwd_p_kernel<4>, fwd_p_kernel<8>, nero_pw(0), ch, n_rows, stream);
+    launch_p<fwd_p_kernel>(ch, n_rows, stream);
     return NERO_OK;
 }
 
@@ -746,7 +699,7 @@ int nero_f16p_tangent(const nero_tan_chain* ch, int n_rows, hipStream_t stream) 
     for (int l = 0; l < ch->n_layers; ++l)
         if ((ch->layer[l].k_main | ch->layer[l].k_aux) & 15)
             return nero_fail(NERO_ERR_ARG, "nero_mlp_tangent(f16x3p): k_main / k_aux must be multiples of 16");
-    launch_p(tan_p_kernel<4>, tan_p_kernel<8>, nero_pw(1), ch, n_rows, stream);
+    launch_p<tan_p_kernel>(ch, n_rows, stream);
     return NERO_OK;
 }
 
@@ -766,7 +719,7 @@ int nero_f16p_backward(const nero_bwd_chain* ch, int n_rows, hipStream_t stream)
         if (ch->layer[l].n_out & 15) return nero_fail(NERO_ERR_ARG, "nero_mlp_backward(f16x3p): n_out must be a multiple of 16");
     if (ch->d_aux && (ch->ld_daux & 3)) return nero_fail(NERO_ERR_ARG, "nero_mlp_backward(f16x3p): ld_daux must be a multiple of 4");
     if (ch->d_init && (ch->ld_dinit & 3)) return nero_fail(NERO_ERR_ARG, "nero_mlp_backward(f16x3p): ld_dinit must be a multiple of 4");
-    if (nero_f16p_masks_only(ch)) launch_p(bwd_p_kernel<4, true>, bwd_p_kernel<8, true>, nero_pw(2), ch, n_rows, stream);
-    else launch_p(bwd_p_kernel<4, false>, bwd_p_kernel<8, false>, nero_pw(2), ch, n_rows, stream);
+    if (nero_f16p_masks_only(ch)) launch_p<bwd_p_kernel<true>>(ch, n_rows, stream);
+    else launch_p<bwd_p_kernel<false>>(ch, n_rows, stream);
     return NERO_OK;
 }

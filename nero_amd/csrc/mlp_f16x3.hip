@@ -473,8 +473,8 @@ inline int bwd_lds_bytes() { return 2 * PLANE_A + LDS_SMALL_BYTES + BWD_PA_BYTES
 // no spill -- instead of reading them in the epilogue: the second-order reverse pass went from 1.74 to 2.69 ms.  vmcnt retires in
 // order, so the weight stream of the next GEMM queued behind eight 1 KB HBM loads per wave, exactly what the LDS-DMA of the saved
 // activations had been introduced to avoid; there is no LDS left for a second DMA target: 135.7 of 160 KB.)
-template <bool FIXED, bool WALK>
-__global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int n_rows, int n_tiles_total) {
+template <bool FIXED>
+__global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int n_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Lds S;
     S.actp = smem;
@@ -494,10 +494,7 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
         wsc_commit(S.wsc, wr, tid);                        // (published by the first tile's barrier)
     }
     const unsigned pa_addr = __builtin_amdgcn_readfirstlane(lds_offset_of(pa_lds));
-    // PERSISTENT walk (round 5; NERO_F16_PERSIST bit 1): with the second accumulator set gone (mlp_f16_util.h) the tile loop fits the
-    // register budget -- round 4 measured it 2-5 % SLOWER because it spilled 12-20 VGPRs.  n_tiles_total = 0: one tile per workgroup.
-    for (int tile = blockIdx.x; tile < (WALK ? n_tiles_total : (int)gridDim.x); tile += gridDim.x) {
-    const int row0 = tile * 64;
+    const int row0 = blockIdx.x * 64;                  // one tile per workgroup (a persistent walk measured slower: docs/experiments.md 14)
     const size_t goff = (size_t)(row0 + i) * NERO_HID + 32 * wave + 4 * h;
     unsigned mbits[2] = {0u, 0u};                      // ReLU sign masks of the layer being processed
     // request what the epilogue of layer `Ln` needs of its input activation: the sign words (registers) or the fp32 tile (LDS-DMA)
@@ -652,9 +649,6 @@ __global__ __launch_bounds__(512, 1) void bwd_f16_kernel(nero_bwd_chain ch, int 
         PH(6);
     }
     PH_END;
-    if (!WALK) break;
-    __syncthreads();                                       // (the next tile's dy overwrites the planes every wave has just read)
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -749,14 +743,11 @@ static int nero_cu_count() {
     }
     return n;
 }
-// workgroups of a chain launch over n_tiles tiles.  NERO_F16_PERSIST (bit 0 = the forward kernel, default 1; the reverse and tangent kernels measured 2-5 % SLOWER as persistent walks
-// -- their register budget has no room for the loop state: 12-20 spilled VGPRs, 40-50 spilled SGPRs -- and stayed as they were) is an experiment
-// switch: a cleared bit launches one workgroup per tile, i.e. the same kernel without the persistent walk.
-static int nero_chain_grid(int n_tiles, int kind_bit) {
-    static int mask = -1;
-    if (mask < 0) { const char* e = getenv("NERO_F16_PERSIST"); mask = e ? atoi(e) : 1; }
+// workgroups of a forward launch over n_tiles tiles: persistent once there are more tiles than CUs.  (The reverse and tangent kernels
+// launch one workgroup per tile: their register budget has no room for the loop state, docs/experiments.md 14.)
+static int nero_fwd_grid(int n_tiles) {
     const int cus = nero_cu_count();
-    return ((mask >> kind_bit) & 1) && n_tiles > cus ? cus : n_tiles;
+    return n_tiles > cus ? cus : n_tiles;
 }
 
 // NERO_F16_PAIRED: bit 0 / 1 / 2 = the forward / tangent / reverse pass runs on the two-workgroups-per-CU kernels of mlp_f16p.hip when the
@@ -789,33 +780,10 @@ static void launch_fwd(const nero_fwd_chain* ch, int n_rows, int n_tiles, dim3 g
     hipLaunchKernelGGL((fwd_f16_kernel<WIDE, NVI>), grid, dim3(512), f16_lds_bytes(WIDE ? 1 : 0), stream, *ch, n_rows, n_tiles);
 }
 
-// NERO_F16_ROWOWNER: forward chains WITHOUT saves / masks on the row-owner kernel of mlp_f16r.hip (a wave owns 32 rows and all features, planes
-// in registers, weights through an LDS-DMA ring): 1 = launches of at least 128 rows per CU, 3 = every launch (tests), 0 = off.
-constexpr int NERO_F16_ROWOWNER_DEFAULT = 0;
-static int g_rowowner = -1;
-static int nero_rowowner_mask() {
-    if (g_rowowner < 0) { const char* e = getenv("NERO_F16_ROWOWNER"); g_rowowner = (e ? atoi(e) : NERO_F16_ROWOWNER_DEFAULT) & 3; }
-    return g_rowowner;
-}
-extern "C" int nero_f16_rowowner(int mask) {           // mask >= 0: select; returns the previous selection (include/nero_hip.h)
-    const int prev = nero_rowowner_mask();
-    if (mask >= 0) g_rowowner = mask & 3;
-    return prev;
-}
-
 int nero_f16_forward(const nero_fwd_chain* ch, int n_rows, hipStream_t stream) {
-    {
-        const int m = nero_rowowner_mask();
-        if ((m & 1) && ((m & 2) || n_rows >= 128 * nero_cu_count()) && nero_f16r_covers(ch)) {
-            for (int l = 0; l < ch->n_layers; ++l)
-                if ((ch->layer[l].k_main | ch->layer[l].k_aux) & 15)
-                    return nero_fail(NERO_ERR_ARG, "nero_mlp_forward(f16x3): k_main / k_aux must be multiples of 16");
-            return nero_f16r_forward(ch, n_rows, stream);
-        }
-    }
     if (nero_paired(0, n_rows) && !ch->aux_wide) return nero_f16p_forward(ch, n_rows, stream);
-    const int n_tiles = (n_rows + 63) / 64, cus = nero_cu_count();
-    const dim3 grid(nero_chain_grid(n_tiles, 0));
+    const int n_tiles = (n_rows + 63) / 64;
+    const dim3 grid(nero_fwd_grid(n_tiles));
     for (int l = 0; l < ch->n_layers; ++l)
         if ((ch->layer[l].k_main | ch->layer[l].k_aux) & 15)
             return nero_fail(NERO_ERR_ARG, "nero_mlp_forward(f16x3): k_main / k_aux must be multiples of 16");
@@ -823,7 +791,6 @@ int nero_f16_forward(const nero_fwd_chain* ch, int n_rows, hipStream_t stream) {
     // launch has more tiles than workgroups
     constexpr bool F16_TILE_AHEAD = true;
     const bool ahead = F16_TILE_AHEAD && (!ch->init || ch->k_init <= 128) && (int)grid.x < n_tiles;
-    (void)cus;
     if (ch->aux_wide) { if (ahead) launch_fwd<true, 4>(ch, n_rows, n_tiles, grid, stream); else launch_fwd<true, 0>(ch, n_rows, n_tiles, grid, stream); }
     else              { if (ahead) launch_fwd<false, 4>(ch, n_rows, n_tiles, grid, stream); else launch_fwd<false, 0>(ch, n_rows, n_tiles, grid, stream); }
     return NERO_OK;
@@ -841,13 +808,9 @@ int nero_f16_tangent(const nero_tan_chain* ch, int n_rows, hipStream_t stream) {
     return NERO_OK;
 }
 
-// NERO_F16_PAIRED_MASKS (round 6; default 1): reverse chains that need sign words only (ReLU / identity: the predictors, the NeRF++ networks)
-// on the paired kernel's MASKS instantiation when the launch is large; the softplus chains keep the 512-thread kernel and its LDS-DMA.
-static bool nero_paired_masks(int n_rows) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("NERO_F16_PAIRED_MASKS"); on = e ? atoi(e) : 1; }
-    return on && ((on & 2) || (n_rows + 63) / 64 > 4 * nero_cu_count());
-}
+// reverse chains that need sign words only (ReLU / identity: the predictors, the NeRF++ networks) run on the paired kernel's MASKS
+// instantiation when the launch is large; the softplus chains keep the 512-thread kernel and its LDS-DMA.
+static bool nero_paired_masks(int n_rows) { return (n_rows + 63) / 64 > 4 * nero_cu_count(); }
 int nero_f16_backward(const nero_bwd_chain* ch, int n_rows, hipStream_t stream) {
     if (nero_paired(2, n_rows)) return nero_f16p_backward(ch, n_rows, stream);
     if (nero_paired_masks(n_rows) && nero_f16p_masks_only(ch)) return nero_f16p_backward(ch, n_rows, stream);
@@ -858,18 +821,9 @@ int nero_f16_backward(const nero_bwd_chain* ch, int n_rows, hipStream_t stream) 
     if (ch->d_init && (ch->ld_dinit & 3)) return nero_fail(NERO_ERR_ARG, "nero_mlp_backward(f16x3): ld_dinit must be a multiple of 4");
     bool fixed = true;
     for (int l = 0; l < ch->n_layers; ++l) fixed = fixed && (ch->layer[l].n_out == 0 || ch->layer[l].n_out == 256);
-    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
-    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
-    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
-    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
-    const int n_tiles = (n_rows + 63) / 64;
-    const dim3 pgrid(nero_chain_grid(n_tiles, 1));
-    if ((int)pgrid.x < n_tiles) {
-        if (fixed) hipLaunchKernelGGL((bwd_f16_kernel<true, true>), pgrid, block, bwd_lds_bytes(), stream, *ch, n_rows, n_tiles);
-        else hipLaunchKernelGGL((bwd_f16_kernel<false, true>), pgrid, block, bwd_lds_bytes(), stream, *ch, n_rows, n_tiles);
-    } else {
-        if (fixed) hipLaunchKernelGGL((bwd_f16_kernel<true, false>), grid, block, bwd_lds_bytes(), stream, *ch, n_rows, n_tiles);
-        else hipLaunchKernelGGL((bwd_f16_kernel<false, false>), grid, block, bwd_lds_bytes(), stream, *ch, n_rows, n_tiles);
-    }
+    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
+    NERO_ONCE(hipFuncSetAttribute((const void*)bwd_f16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_bytes()));
+    if (fixed) hipLaunchKernelGGL(bwd_f16_kernel<true>, grid, block, bwd_lds_bytes(), stream, *ch, n_rows);
+    else hipLaunchKernelGGL(bwd_f16_kernel<false>, grid, block, bwd_lds_bytes(), stream, *ch, n_rows);
     return NERO_OK;
 }

@@ -548,7 +548,7 @@ __global__ void shade_combine_bwd_kernel(const float* __restrict__ geo, const fl
     // Whole 32-byte rows, and d_NoV travels in dmat[k][5] (round 5): rounds 1-4 dropped it into d_geo[k][3] here, a 4-byte store per
     // 32-byte row into a buffer a memset had zeroed and shade_encode_bwd then completed with seven more scalar stores -- three kernels
     // building the same cache lines from byte-masked pieces.  With a second stream's kernels running beside the step (NERO_STREAMS=3)
-    // sdf_alpha_bwd then occasionally read 16-row blocks of d_geo WITHOUT shade_encode_bwd's part (scripts/r05/dbg_streams.py: d_grad off by
+    // sdf_alpha_bwd then occasionally read 16-row blocks of d_geo WITHOUT shade_encode_bwd's part (round 5's intermediate-by-intermediate comparison of repeated steps: d_grad off by
     // exactly the size of those terms, the buffer itself final and identical afterwards).  Now every row of d_geo is written once, by
     // one kernel, as two float4 stores.
     float4* dm = reinterpret_cast<float4*>(dmat + (size_t)k * 8);

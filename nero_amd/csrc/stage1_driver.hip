@@ -51,9 +51,6 @@ struct nero_stage1 {
     // kernel classes are bound by different things -- the weight-gradient GEMM streams its operands from HBM (4.9 TB/s), the chain kernels
     // issue MFMA + VALU -- and their workgroups interleave over the CUs: fewer weight-gradient workgroups at a time compete for HBM.  The
     // price is memory: a chain's deltas cannot be released while its jobs may still read them (no arena release in this mode).
-    // debug: (pointer, bytes) of the backward's intermediates of the last step, for scripts/r05/dbg_streams.py (nero_stage1_debug_buffers)
-    const void* dbg_ptr[12] = {};
-    size_t dbg_bytes[12] = {};
     hipStream_t s3 = nullptr;
     static constexpr int N_DW_EV = 12;                     // one event per fork of a step (never re-recorded while a wait on it may be pending)
     hipEvent_t ev_dw[N_DW_EV] = {}, ev_dw_done = nullptr;
@@ -495,16 +492,9 @@ int do_backward(nero_stage1* h, Arena& A, const float* d_rgb, const float* d_ger
             RC(h->mat[j].weight_grads(A, M, h->f_mat[j], mb, n_in, S.feat, NERO_HID, h->x8, 8, hd, nullptr, nullptr, partials, (void*)fork_dw(h, A, hs)));
             if (!three) A.release(mk);
         }
-        // Where the weight-gradient stream is joined: behind the SDF network's own jobs (default), i.e. the tangent / second-order reverse
-        // passes run beside the material MLPs' jobs.  HISTORY (round 5): the first version of this did not reproduce its SDF gradients bit for
-        // bit (2 repeats of 9 differed by 1e-7 ... 1e-5).  scripts/r05/dbg_streams.py narrowed it to ONE kernel: sdf_alpha_bwd, with identical
-        // inputs, returned 16-row blocks of d_grad a few ulp off whenever the narrow weight-gradient kernel shared its SIMDs -- packed fp32
-        // VALU instructions next to another wave's MFMAs (common.h).  With the library built without them every join position is
-        // bit-reproducible (8 x 9 repeats each).  NERO_DW_JOIN = e | j | t | b | l moves the join for experiments (early: in front of
-        // sdf_alpha_bwd; j: in front of the tangent chain; t / b: behind the tangent / reverse launch; l: late, the default).
-        static const char join_at = [] { const char* e = getenv("NERO_DW_JOIN"); return e ? e[0] : 'l'; }();
-        const bool late_join = join_at == 'l';
-        if (join_at == 'e') join_dw(h, A, hs);
+        // The weight-gradient stream is joined behind the SDF network's own jobs (below): sdf_alpha_bwd and the tangent / second-order
+        // reverse passes run beside the material MLPs' jobs.  That is bit-reproducible only because the library holds no packed fp32
+        // VALU instructions (-fno-slp-vectorize, common.h; the story: docs/experiments.md 14).
         float* d_sdf4 = A.f32((size_t)rpi * 4);
         float* d_grad = A.f32((size_t)rpi * 3);
         float* dinv = A.f32(rpi);
@@ -522,14 +512,7 @@ int do_backward(nero_stage1* h, Arena& A, const float* d_rgb, const float* d_ger
         float* ehat = A.f32((size_t)rpi * LD_PE);
         float* tbuf = A.f32((size_t)8 * rpi * NERO_HID);               // adot_0..7 (the injections are formed inside the reverse kernel)
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_bwd: workspace too small");
-        if (!A.dry) {
-            const void* ps[9] = {d_geo, d_feat, d_sdf4, d_grad, dinv, ehat, tbuf, d_ai, dmr};
-            const size_t bs[9] = {(size_t)rpi * 32, (size_t)rpi * NERO_HID * 4, (size_t)rpi * 16, (size_t)n_in * 12, (size_t)n_in * 4, (size_t)rpi * LD_PE * 4,
-                                  (size_t)8 * rpi * NERO_HID * 4, (size_t)n_in * 4, (size_t)rpi * 16};
-            for (int i = 0; i < 9; ++i) { h->dbg_ptr[i] = ps[i]; h->dbg_bytes[i] = bs[i]; }
-        }
         LAUNCH(nero_pe_jvp(S.x4, 4, d_grad, 3, N_FREQ, n_in, ehat, LD_PE, stream));
-        if (join_at == 'j') join_dw(h, A, hs);                 // (behind sdf_alpha_bwd + pe_jvp, in front of the tangent chain)
         nero_tan_chain tc;
         memset(&tc, 0, sizeof(tc));
         tc.init = ehat; tc.ld_init = LD_PE; tc.k_init = LD_PE; tc.aux = ehat; tc.ld_aux = LD_PE; tc.k_aux = LD_PE;
@@ -557,15 +540,12 @@ int do_backward(nero_stage1* h, Arena& A, const float* d_rgb, const float* d_ger
         tc.macs_per_row = macs;
         head_extra[8] = tbuf + (size_t)7 * rpi * NERO_HID;
         LAUNCH(nero_mlp_tangent(&tc, n_in, stream));
-        if (join_at == 't') join_dw(h, A, hs);
         const float* sd[MAXL] = {};
         sd[8] = d_sdf4;
         Bwd sb;
         RC(sc.backward(A, M, h->f_sdf, n_in, d_feat, NERO_HID, sd, false, false, injs, nullptr, 0, false, false, sb, stream, adots));
-        if (join_at == 'b') join_dw(h, A, hs);
-        RC(sc.weight_grads(A, M, h->f_sdf, sb, n_in, h->pe40, LD_PE, h->pe40, LD_PE, sd, second, head_extra, partials,
-                           late_join ? (void*)fork_dw(h, A, hs) : stream));
-        if (late_join) join_dw(h, A, hs);
+        RC(sc.weight_grads(A, M, h->f_sdf, sb, n_in, h->pe40, LD_PE, h->pe40, LD_PE, sd, second, head_extra, partials, (void*)fork_dw(h, A, hs)));
+        join_dw(h, A, hs);
         float* part = A.f32(128);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_bwd: workspace too small");
         if (d_inv_s_sum && !A.dry) {
@@ -777,14 +757,6 @@ int nero_stage1_render_bwd(nero_stage1* h, const float* d_rgb, const float* d_ge
     if (wrong_device(h)) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_bwd: the current device is not the one the handle was created on");
     h->A.release(h->step_mark);
     return drain_on_error(h, do_backward(h, h->A, d_rgb, d_gerr, d_occ, grads, d_inv_s_sum, stream));
-}
-
-// debug (scripts/r05/dbg_streams.py): device pointers + sizes of nine intermediates of the last render_bwd, in the order
-// d_geo, d_feat, d_sdf4, d_grad, dinv, ehat, adot (8 layers), d_alpha_inner, d_metallic_raw
-int nero_stage1_debug_buffers(nero_stage1* h, const void** ptrs, size_t* bytes) {
-    if (!h || !ptrs || !bytes) return nero_fail(NERO_ERR_ARG, "nero_stage1_debug_buffers: bad argument");
-    for (int i = 0; i < 9; ++i) { ptrs[i] = h->dbg_ptr[i]; bytes[i] = h->dbg_bytes[i]; }
-    return NERO_OK;
 }
 
 int nero_stage1_get_state(nero_stage1* h, nero_stage1_state* out) {

@@ -183,26 +183,14 @@ class MCShade(torch.autograd.Function):
         L.check(lib.nero_mc_point_setup(_p(pts), _p(view), _p(normals), _p(mat5), _p(rd), _p(rs), Pn, _p(pt), st))
         dirs, orig = torch.empty((Pn * D, 3), **f32), torch.empty((Pn * D, 3), **f32)
         L.check(lib.nero_mc_dirs(_p(pt), _p(K.tab_d), _p(K.tab_s), Pn, Dd, Ds, _p(dirs), _p(orig), st))
-        # closest hit, depth >= 10 <=> miss.  A tracer that takes a launch-order hint starts the specular chunks of every point first
-        # (nero_bvh_trace_grouped: same outputs); any other RayTracer-shaped object (tests, a reference-side tracer) gets the plain call
-        # Round 6: rays whose estimator weight is exactly zero (GGX directions below the shading horizon under the Schlick geometry term:
-        # mc_shade.hip, DEAD_SLOT) are flagged, not traversed by a tracer that takes the flags, and left out of both light MLPs
         N = Pn * D
         geom = GEOMETRY_TYPES[cfg['geometry_type']]
         dead = None
         if geom == 0 and os.environ.get('NERO_MC_SKIP_DEAD', '1') != '0':
             dead = torch.empty(N, dtype=torch.uint8, device=dev)
             L.check(lib.nero_mc_dead_rays(_p(pt), _p(dirs), Pn, Dd, Ds, geom, _p(dead), st))
-        tg = getattr(tracer, 'trace_grouped', None)
-        tm = getattr(tracer, 'trace_masked', None)
-        from .stage2 import descending_chunks
-        order = descending_chunks(D) if tm is not None else None
-        if tm is not None and (dead is not None or order is not None):
-            pos, fnrm, depth = tm(orig, dirs, dead, chunk_order=order)
-        elif tg is not None and os.environ.get('NERO_TRACE_ORDER', 'descending') == 'grouped':
-            pos, fnrm, depth = tg(orig, dirs, D, Dd)
-        else:
-            pos, fnrm, depth = tracer.trace(orig, dirs)
+        from .stage2 import trace_secondary
+        pos, fnrm, depth = trace_secondary(tracer, orig, dirs, D, dead)      # (dead: the zero-weight rays, flagged above)
         # hit / miss split on the device (ordered compaction, nero_mc_split): the index lists torch.nonzero would give + the slot map
         depth = depth.contiguous().reshape(-1)
         i32 = dict(dtype=torch.int32, device=dev)

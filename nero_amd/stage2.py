@@ -3,7 +3,6 @@ predict_materials and the Monte-Carlo shader (MCShadingNetwork.shade_mixed / get
 calls instead of the ~120 launches nero_amd/material_step.py sequences from Python.  The mesh tracer stays a Python-visible call between
 nero_stage2_rays and nero_stage2_shade_fwd (nero_amd.raytracing.RayTracer in production, the oracle tracer in teacher-forced tests)."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -140,10 +139,24 @@ def descending_chunks(D):
     """launch order of the 64-ray chunks of a surface point's D secondary rays for RayTracer.trace_masked: descending.  Both direction tables run
     from the pole of their lobe outwards (network/field.py:741-749), so the later entries -- of the cosine table and of the GGX table alike -- are
     the grazing directions, the long BVH traversals; started first, they no longer end the launch on a handful of resident waves (tracer
-    0.69 -> 0.57 ms per C4 step; same outputs).  None when D is not a whole number of chunks (<= 32), or with NERO_TRACE_ORDER=natural."""
-    if D % 64 or D // 64 > 32 or D // 64 < 2 or os.environ.get('NERO_TRACE_ORDER', 'descending') == 'natural':
+    0.69 -> 0.57 ms per C4 step; same outputs).  None when D is not a whole number of chunks (<= 32)."""
+    if D % 64 or D // 64 > 32 or D // 64 < 2:
         return None
     return list(range(D // 64 - 1, -1, -1))
+
+
+def trace_secondary(tracer, orig, dirs, D, dead):
+    """closest hit of the [point][direction] secondary rays of the Monte-Carlo shading pass, depth >= 10 <=> miss: (pos, face normal, depth).
+    `dead` (flags or None) marks the rays whose estimator weight is exactly zero (GGX directions below the shading horizon under the Schlick
+    geometry term: mc_shade.hip, DEAD_SLOT).  A tracer that takes the flags (RayTracer.trace_masked) does not traverse them -- they are the
+    longest rays of the launch, and the shading pass leaves them out of both light MLPs whatever the tracer reported -- and starts the
+    chunks of every point in descending order (descending_chunks: same outputs); any other RayTracer-shaped object (tests, a reference-side
+    tracer) gets the plain call."""
+    tm = getattr(tracer, 'trace_masked', None)
+    order = descending_chunks(D) if tm is not None else None
+    if tm is not None and (dead is not None or order is not None):
+        return tm(orig, dirs, dead, chunk_order=order)
+    return tracer.trace(orig, dirs)
 
 
 class MCShadeC(torch.autograd.Function):
@@ -165,21 +178,7 @@ class MCShadeC(torch.autograd.Function):
         orig, dirs = torch.empty((Pn * D, 3), **f32), torch.empty((Pn * D, 3), **f32)
         L.check(_lib.nero_stage2_rays(drv.h, Pn, _p(pts), _p(view), _p(normals), _p(mat5), _p(rd), _p(rs), _p(drv.tab_d), _p(drv.tab_s), _p(orig),
                                       _p(dirs), L.stream_ptr()))
-        # closest hit, depth >= 10 <=> miss.  A tracer that takes a launch-order hint starts the specular chunks of every point first
-        # (nero_bvh_trace_grouped: same outputs); any other RayTracer-shaped object (tests, a reference-side tracer) gets the plain call
-        # Round 6: the driver flags the rays whose estimator weight is exactly zero (GGX directions below the shading horizon under the
-        # Schlick geometry term: mc_shade.hip, DEAD_SLOT); a tracer that takes the flags does not traverse them (they are the longest rays of
-        # the launch), and shade_fwd leaves them out of both light MLPs whatever the tracer reported
-        tg = getattr(tracer, 'trace_grouped', None)
-        tm = getattr(tracer, 'trace_masked', None)
-        dead = _lib.nero_stage2_dead_rays(drv.h)
-        order = descending_chunks(D) if tm is not None else None
-        if tm is not None and (dead or order is not None):
-            pos, fnrm, depth = tm(orig, dirs, dead, chunk_order=order)
-        elif tg is not None and os.environ.get('NERO_TRACE_ORDER', 'descending') == 'grouped':
-            pos, fnrm, depth = tg(orig, dirs, D, drv.Dd)
-        else:
-            pos, fnrm, depth = tracer.trace(orig, dirs)
+        pos, fnrm, depth = trace_secondary(tracer, orig, dirs, D, _lib.nero_stage2_dead_rays(drv.h) or None)     # (the driver's flags)
         pos, fnrm, depth = pos.contiguous(), fnrm.contiguous(), depth.contiguous().reshape(-1)
         rgb, dl, sl, sp = (torch.empty((Pn, 3), **f32) for _ in range(4))
         n_miss, n_hit = C.c_int(0), C.c_int(0)

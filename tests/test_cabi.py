@@ -106,7 +106,7 @@ def test_every_declared_symbol_is_bound():
     hdr = open(os.path.join(ROOT, 'include', 'nero_hip.h')).read()
     names = sorted(set(re.findall(r'\b(nero_[a-z0-9_]+)\s*\(', hdr)))         # the rule of test_library_exports_every_declared_symbol
     protos = _prototypes()
-    assert sorted(protos) == names and len(names) == 174
+    assert sorted(protos) == names and len(names) == 172
     for n in names:
         fn = getattr(L.lib, n)
         assert fn.argtypes is not None and len(fn.argtypes) == protos[n][1], (n, fn.argtypes, protos[n])

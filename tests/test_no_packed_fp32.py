@@ -60,9 +60,7 @@ def test_paired_chain_kernels_fit_two_workgroups_per_cu():
         name = nm.group(1)
         meta[name] = {m.group(1): int(m.group(2)) for m in
                       re.finditer(r'\.(vgpr_count|vgpr_spill_count|private_segment_fixed_size|max_flat_workgroup_size):\s+(\d+)', entry)}
-    # (the 8-wave instantiations <8> -- four waves per SIMD at 128 registers, NERO_F16_PW=8 -- are a measured-and-dropped experiment of
-    #  round 6 and do spill; the default organisation is <4>)
-    for k in ('fwd_p_kernelILi4E', 'tan_p_kernelILi4E'):
+    for k in ('fwd_p_kernelE', 'tan_p_kernelE'):
         hit = [v for n, v in meta.items() if k in n]
         assert len(hit) == 1, (k, list(meta))
         v = hit[0]
