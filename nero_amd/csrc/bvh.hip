@@ -200,18 +200,22 @@ int nero_bvh_create(const float* verts, int nV, const int* tris, int nT, void** 
     h->b.n_nodes = (int)B.nodes.size();
     h->b.n_tris = nT;
     const size_t nb = std::max<size_t>(1, B.nodes.size()) * sizeof(Node);
-    if (hipMalloc(&h->b.d_nodes, nb) != hipSuccess || hipMalloc(&h->b.d_tris, (size_t)nT * sizeof(Tri)) != hipSuccess) {
+    if (hipMalloc(&h->b.d_nodes, nb) != hipSuccess || hipMalloc(&h->b.d_tris, (size_t)nT * sizeof(Tri)) != hipSuccess ||
+        hipMalloc(&h->b.d_face, (size_t)nT * sizeof(int)) != hipSuccess) {
         (void)hipFree(h->b.d_nodes);
         (void)hipFree(h->b.d_tris);
+        (void)hipFree(h->b.d_face);
         delete h;
         return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create: hipMalloc failed");
     }
     hipError_t e0 = hipSuccess;
     if (!B.nodes.empty()) e0 = hipMemcpy(h->b.d_nodes, B.nodes.data(), B.nodes.size() * sizeof(Node), hipMemcpyHostToDevice);
     const hipError_t e1 = hipMemcpy(h->b.d_tris, T.data(), (size_t)nT * sizeof(Tri), hipMemcpyHostToDevice);
-    if (e0 != hipSuccess || e1 != hipSuccess) {
+    const hipError_t e2 = hipMemcpy(h->b.d_face, B.order.data(), (size_t)nT * sizeof(int), hipMemcpyHostToDevice);
+    if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess) {
         (void)hipFree(h->b.d_nodes);
         (void)hipFree(h->b.d_tris);
+        (void)hipFree(h->b.d_face);
         delete h;
         return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create: hipMemcpy of the BVH failed");
     }
@@ -306,6 +310,7 @@ int nero_bvh_destroy(void* handle) {
     Handle* h = (Handle*)handle;
     (void)hipFree(h->b.d_nodes);
     (void)hipFree(h->b.d_tris);
+    (void)hipFree(h->b.d_face);
     delete h;
     return NERO_OK;
 }

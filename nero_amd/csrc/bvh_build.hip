@@ -376,15 +376,18 @@ int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int 
     h->b.n_nodes = plan.n_nodes;
     h->b.n_tris = nT;
     const size_t nb = (plan.n_nodes > 0 ? (size_t)plan.n_nodes : 1) * sizeof(Node);
-    if (hipMalloc(&h->b.d_nodes, nb) != hipSuccess || hipMalloc(&h->b.d_tris, (size_t)nT * sizeof(Tri)) != hipSuccess) {
+    if (hipMalloc(&h->b.d_nodes, nb) != hipSuccess || hipMalloc(&h->b.d_tris, (size_t)nT * sizeof(Tri)) != hipSuccess ||
+        hipMalloc(&h->b.d_face, (size_t)nT * sizeof(int)) != hipSuccess) {
         (void)hipFree(h->b.d_nodes);
         (void)hipFree(h->b.d_tris);
+        (void)hipFree(h->b.d_face);
         delete h;
         return nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: hipMalloc failed");
     }
     auto drop = [h](int rc) {                                  // (the message is nero_fail's already)
         (void)hipFree(h->b.d_nodes);
         (void)hipFree(h->b.d_tris);
+        (void)hipFree(h->b.d_face);
         delete h;
         return rc;
     };
@@ -408,6 +411,10 @@ int nero_bvh_create_device(const float* d_verts, int nV, const int* d_tris, int 
         hipLaunchKernelGGL(emit_level_kernel, dim3(blocks_of((size_t)1 << l)), dim3(256), 0, s, plan, l, ord, bmin, bmax, heap, h->b.d_nodes);
     hipLaunchKernelGGL(emit_tris_kernel, dim3(blocks_of(nT)), dim3(256), 0, s, d_verts, d_tris, ord, nT, h->b.d_tris);
     mark(EV_EMIT, s);
+    // the face table: the final leaf order (face indices below 2^27: the same bits as ints), copied on the build's stream before the caller
+    // may reuse the workspace
+    if (hipMemcpyAsync(h->b.d_face, ord, (size_t)nT * sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return drop(nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: copying the face table failed"));
     if (hipGetLastError() != hipSuccess) return drop(nero_fail(NERO_ERR_LAUNCH, "nero_bvh_create_device: a kernel launch failed"));
     g_ev_valid = g_ev_made;
     *handle = h;

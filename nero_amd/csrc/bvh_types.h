@@ -16,6 +16,7 @@ struct Tri { float v0[3], e1[3], e2[3], pad[3]; };   // 48 bytes, leaf order
 struct Bvh {
     Node* d_nodes = nullptr;
     Tri* d_tris = nullptr;
+    int* d_face = nullptr;    // [n_tris] leaf slot -> the caller's face index (the builders' leaf-order permutation)
     int n_nodes = 0, n_tris = 0;
 };
 

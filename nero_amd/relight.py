@@ -1,0 +1,367 @@
+"""Relighting of the Stage-II mesh under an HDR environment map on the GPU: what the reference's relight.py hands to Blender Cycles, as
+direct lighting with shadows on the mesh tracer's BVH (include/nero_hip_relight.h, nero_amd/csrc/relight.hip).
+
+Camera rays go through nero_bvh_trace_faces (depth, face, barycentrics), the per-vertex materials are interpolated at the hits, and
+nero_bvh_relight evaluates the reference's shade_mixed estimator with "environment radiance if the shadow ray is free, zero if it is
+blocked" for the light -- one fused kernel that never stores a ray.  NOT modelled: inter-reflection (a blocked direction is black), texture
+maps as input, smooth normals unless the caller supplies per-vertex ones.  This is not Cycles.
+
+ROUGHNESS: extract_materials.py stores -- and predict_materials_of_vertices returns -- the PERCEPTUAL roughness (the square root of what
+the network predicts); the estimator takes alpha = roughness^2.  Everything here carries the perceptual value, as a renderer's vertex
+attribute would, and estimator_materials() below squares it: the one place."""
+import ctypes as C
+import os
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .raytracing import RayTracer
+from .renderer import linear_to_srgb
+from .texture import _png_chunk
+
+HEADER_PATH = os.path.join(os.path.dirname(L.HEADER_PATH), 'nero_hip_relight.h')
+CONVENTIONS = {'nero': 0, 'nero_real': 1, 'blender': 2}          # nero_env_lookup's `convention`
+GEOMETRY_TYPES = {'schlick': 0, 'ggx_smith': 1}                  # as nero_amd.stage2
+MISS_DEPTH = 10.0
+MAX_LANES = 2 ** 31 - 64                                         # (point, padded sample) lanes of one nero_bvh_relight call
+DEFAULT_CHUNK_LANES = 1 << 26
+
+
+def _bind():
+    """restype / argtypes of the third header's entry points on the library _lib loaded (the header is not part of _lib.HEADER_PATHS: this
+    module binds it).  -> {function: (restype, argtypes)}"""
+    with open(HEADER_PATH) as f:
+        sigs = L.parse_header(f.read())
+    for fn, (restype, argtypes) in sigs.items():
+        try:
+            f = getattr(L.lib, fn)
+        except AttributeError:
+            raise ImportError(f'{L.LIB_PATH} does not export {fn}, which nero_hip_relight.h declares: rebuild the library') from None
+        setattr(f, 'restype', restype)
+        setattr(f, 'argtypes', argtypes)
+    return sigs
+
+
+SIGNATURES = _bind()
+_lib = L.lib
+
+
+# ---- cameras --------------------------------------------------------------------------------------------------------------------------------
+def relighting_poses(num, azimuth, elevation, dist):
+    """the orbit of the reference's generate_relghting_poses (blender_backend/blender_utils.py:101-116): `num` world-to-camera poses [num,3,4]
+    (float64) on half a turn around the azimuth (degrees) at one elevation (degrees), every camera looking at the origin from `dist`; the
+    object frame is turned by 90 degrees about x against the camera orbit's (R_trans), as there"""
+    az = np.deg2rad(azimuth) + np.linspace(-np.pi / 2, np.pi / 2, num)
+    el = np.ones_like(az) * np.deg2rad(elevation)
+    cam = np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], -1)
+    up = np.asarray([0.0, 0.0, 1.0])
+    z = -cam / np.linalg.norm(cam, axis=1, keepdims=True)
+    y = -(up[None] - np.sum(z * up[None], 1, keepdims=True) * z)
+    y = y / np.linalg.norm(y, axis=1, keepdims=True)
+    x = np.cross(y, z)
+    rot = np.stack([x, y, z], 1) @ np.asarray([[1.0, 0, 0], [0, 0, -1], [0, 1, 0]])[None]
+    t = np.repeat(np.asarray([0.0, 0.0, float(dist)])[None, :, None], num, 0)
+    return np.concatenate([rot, t], -1)
+
+
+R_BLENDER = np.asarray([[1.0, 0, 0], [0, 0, -1], [0, 1, 0]])       # x_blender = R_BLENDER x_world (blender_utils.set_camera_by_pose)
+
+
+def poses_in_mesh_frame(poses):
+    """the poses of relighting_poses as cameras over the mesh's OWN coordinates.  The reference imports the mesh into Blender untouched and
+    places the camera of a pose [R | t] at rotation R R_BLENDER^T (set_camera_by_pose): Blender's frame is the mesh's, and the turn inside
+    the poses (R_trans = R_BLENDER) cancels -- the cameras orbit the mesh's z axis, z up.  [n,3,4] -> [n,3,4]"""
+    poses = np.asarray(poses, np.float64)
+    return np.concatenate([poses[:, :, :3] @ R_BLENDER.T[None], poses[:, :, 3:]], -1)
+
+
+def default_K(h, w):
+    """Blender's default camera (50 mm lens on a 36 mm sensor) for an h x w image: focal w 50 / 36, principal point at the centre"""
+    f = w * 50.0 / 36.0
+    return np.asarray([[f, 0.0, w / 2.0], [0.0, f, h / 2.0], [0.0, 0.0, 1.0]], np.float32)
+
+
+# ---- materials ------------------------------------------------------------------------------------------------------------------------------
+def load_materials(path):
+    """metallic.npy [V,1], roughness.npy [V,1] (PERCEPTUAL, as stored), albedo.npy [V,3] of a directory extract_materials.py wrote -> the
+    dict predict_materials_of_vertices returns.  Nothing is squared here (estimator_materials does that)."""
+    out = {k: np.asarray(np.load(os.path.join(path, k + '.npy')), np.float32) for k in ('metallic', 'roughness', 'albedo')}
+    n = out['albedo'].shape[0]
+    out['metallic'], out['roughness'], out['albedo'] = out['metallic'].reshape(n, 1), out['roughness'].reshape(n, 1), out['albedo'].reshape(n, 3)
+    return out
+
+
+def estimator_materials(mat5):
+    """[n,5] (metallic, PERCEPTUAL roughness, albedo) -> [n,5] (metallic, alpha = roughness^2, albedo): THE place where the stored roughness
+    is squared, once, for the estimator (nero_mc_point_setup's mat5)"""
+    return torch.cat([mat5[:, 0:1], mat5[:, 1:2] * mat5[:, 1:2], mat5[:, 2:5]], -1)
+
+
+# ---- RGBA PNG -------------------------------------------------------------------------------------------------------------------------------
+def rgba_png_bytes(img):
+    """uint8 [h, w, 4] -> the bytes of a non-interlaced 8-bit RGBA PNG (colour type 6, filter 0 on every row; straight alpha)"""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError(f'rgba_png_bytes: [h, w, 4] expected, got {img.shape}')
+    h, w = img.shape[:2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, -1)], 1)
+    ihdr = struct.pack('>IIBBBBB', w, h, 8, 6, 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + _png_chunk(b'IHDR', ihdr) + _png_chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + _png_chunk(b'IEND', b'')
+
+
+def write_rgba_png(path, img):
+    if torch.is_tensor(img):
+        img = img.detach().cpu().numpy()
+    with open(path, 'wb') as fh:
+        fh.write(rgba_png_bytes(img))
+
+
+# ---- sample tables, hashes ------------------------------------------------------------------------------------------------------------------
+def sample_table(n, device=None):
+    """the relighter's (azimuth, elevation) table of n directions in [0,1]^2, float32 [n,2]: elevation (j + 0.5) / n, azimuth frac(j (sqrt(5)
+    - 1) / 2) -- a golden-ratio lattice.  sample_diffuse_directions reads the elevation as sin^2(theta) and sample_specular_directions as
+    the uniform variate of the GGX lobe, so a table UNIFORM in elevation makes the first cosine-weighted and the second GGX-distributed, as
+    the estimator's densities assume.  The training tables (network/field.py:741-749: 1 - 2 arcsin(z) / pi over a Fibonacci sphere) are not
+    uniform in it -- the mean of a constant light is still the light, but a half-blocked hemisphere is weighed wrongly -- so they are not
+    used here."""
+    j = np.arange(n, dtype=np.float64)
+    tab = np.stack([np.mod(j * ((np.sqrt(5.0) - 1.0) / 2.0), 1.0), (j + 0.5) / n], -1).astype(np.float32)
+    out = torch.from_numpy(tab).contiguous()
+    return out if device is None else out.to(device)
+
+
+def _lowbias32(x):
+    m = 0xffffffff
+    x = x ^ (x >> 16)
+    x = (x * 0x7feb352d) & m
+    x = x ^ (x >> 15)
+    x = (x * 0x846ca68b) & m
+    return x ^ (x >> 16)
+
+
+def pixel_rotations(index, seed):
+    """two azimuth rotations in [0,1) per pixel from a counter hash of (pixel index, seed) -- a function of the pixel alone, so the same for
+    every chunking: h1 = lowbias32(index 0x9E3779B9 + seed), h2 = lowbias32(h1 + 0x68E31DA4), r = (h >> 8) 2^-24.  index: int64 tensor"""
+    m = 0xffffffff
+    h1 = _lowbias32((index.long() * 0x9E3779B9 + (int(seed) & m)) & m)
+    h2 = _lowbias32((h1 + 0x68E31DA4) & m)
+    return (h1 >> 8).float() * 2.0 ** -24, (h2 >> 8).float() * 2.0 ** -24
+
+
+def padded_samples(Dd, Ds):
+    return (Dd + Ds + 63) // 64 * 64
+
+
+# ---- thin wrappers of the entry points ------------------------------------------------------------------------------------------------------
+def _rot_arg(rot):
+    if rot is None:
+        return None
+    r = np.asarray(rot.detach().cpu().numpy() if torch.is_tensor(rot) else rot, np.float32).reshape(9)
+    return (C.c_float * 9)(*[float(x) for x in r])
+
+
+def export_faces(tracer):
+    """leaf slot -> face index of the tracer's tree, int32 numpy [n_tris] (nero_bvh_export_faces)"""
+    n = tracer.info()['n_tris']
+    out = np.empty(n, np.int32)
+    L.check(_lib.nero_bvh_export_faces(tracer._handle(), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def trace_faces(tracer, rays_o, rays_d):
+    """closest hit with the face (nero_bvh_trace_faces): rays [n,3] CUDA float32 -> depth [n] (10: miss), face [n] int32 (-1: miss), bary [n,2]"""
+    rays_o, rays_d = rays_o.float().contiguous(), rays_d.float().contiguous()
+    n = rays_o.shape[0]
+    depth = torch.empty(n, dtype=torch.float32, device=rays_o.device)
+    face = torch.empty(n, dtype=torch.int32, device=rays_o.device)
+    bary = torch.empty(n, 2, dtype=torch.float32, device=rays_o.device)
+    with torch.cuda.device(rays_o.device):
+        L.check(_lib.nero_bvh_trace_faces(tracer._handle(), L.ptr(rays_o), L.ptr(rays_d), n, L.ptr(depth), L.ptr(face), L.ptr(bary), L.stream_ptr()))
+    return depth, face, bary
+
+
+def env_lookup(env, dirs, convention=2, rot=None, clamp=None):
+    """bilinear radiance of the lat-long map env [h,w,3] in the directions dirs [n,3] (nero_env_lookup) -> [n,3]"""
+    env, dirs = env.float().contiguous(), dirs.float().contiguous()
+    n = dirs.shape[0]
+    out = torch.empty(n, 3, dtype=torch.float32, device=dirs.device)
+    with torch.cuda.device(dirs.device):
+        L.check(_lib.nero_env_lookup(L.ptr(env), env.shape[0], env.shape[1], int(CONVENTIONS.get(convention, convention)), _rot_arg(rot),
+                                     L.ptr(dirs), n, float(clamp or 0.0), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def relight_rays(pt, tab_d, tab_s, geometry_type=0):
+    """the sample set of relight_points (nero_relight_rays) -> rays_o, rays_d [P D,3], dead [P D] uint8"""
+    P, Dd, Ds = pt.shape[0], tab_d.shape[0], tab_s.shape[0]
+    n = P * (Dd + Ds)
+    ro = torch.empty(n, 3, dtype=torch.float32, device=pt.device)
+    rd = torch.empty_like(ro)
+    dead = torch.empty(n, dtype=torch.uint8, device=pt.device)
+    with torch.cuda.device(pt.device):
+        L.check(_lib.nero_relight_rays(L.ptr(pt), L.ptr(tab_d), L.ptr(tab_s), P, Dd, Ds, int(geometry_type), L.ptr(ro), L.ptr(rd), L.ptr(dead),
+                                       L.stream_ptr()))
+    return ro, rd, dead
+
+
+def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=None, geometry_type=0, chunk=None):
+    """the fused kernel (nero_bvh_relight) over the point records pt [P,32], in chunks of `chunk` points (None: as many as fit
+    DEFAULT_CHUNK_LANES lanes; always within the per-call limit) -> rgb_lin, diffuse_lin, spec_lin [P,3].  Same bits for every chunk."""
+    P, Dd, Ds = pt.shape[0], tab_d.shape[0], tab_s.shape[0]
+    pad = padded_samples(Dd, Ds)
+    most = max(1, MAX_LANES // pad)
+    chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
+    chunk = max(1, min(chunk, most))
+    dev = pt.device
+    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(3)]
+    env = env.float().contiguous()
+    conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
+    with torch.cuda.device(dev):
+        need = int(_lib.nero_relight_workspace_bytes(min(chunk, max(P, 1)), Dd, Ds))
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+        for i in range(0, P, chunk):
+            n = min(chunk, P - i)
+            L.check(_lib.nero_bvh_relight(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), n, Dd, Ds, int(geometry_type),
+                                          L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0),
+                                          L.ptr(out[0][i:i + n]), L.ptr(out[1][i:i + n]), L.ptr(out[2][i:i + n]), L.ptr(ws), ws.numel(),
+                                          L.stream_ptr()))
+    return tuple(out)
+
+
+def point_records(pts, view, normals, mat5, rand_d, rand_s):
+    """nero_mc_point_setup -> pt [P,32]; mat5 carries alpha (estimator_materials)"""
+    P = pts.shape[0]
+    pt = torch.empty(P, 32, dtype=torch.float32, device=pts.device)
+    args = [t.float().contiguous() for t in (pts, view, normals, mat5)]
+    rd = None if rand_d is None else rand_d.float().contiguous()
+    rs = None if rand_s is None else rand_s.float().contiguous()
+    with torch.cuda.device(pts.device):
+        L.check(_lib.nero_mc_point_setup(*[L.ptr(t) for t in args], L.ptr(rd), L.ptr(rs), P, L.ptr(pt), L.stream_ptr()))
+    return pt
+
+
+# ---- the relighter --------------------------------------------------------------------------------------------------------------------------
+class Relighter:
+    """verts [V,3], tris [T,3]; materials: {'metallic' [V,1], 'roughness' [V,1] PERCEPTUAL, 'albedo' [V,3]} (load_materials,
+    predict_materials_of_vertices); env: linear radiance [h,w,3] (array, tensor) or the path of a Radiance .hdr; convention: 'blender'
+    (the equirectangular mapping of an .hdr made for relight.py --hdr), 'nero' / 'nero_real' (this project's env_light grid, is_real = 0 /
+    1); env_rotation: 3 x 3, applied to a direction before the lookup; tracer: a RayTracer over the same mesh to share, else one is built
+    (`build`); normals: per-vertex [V,3] for smooth shading, else flat face normals turned towards the camera."""
+
+    def __init__(self, verts, tris, materials, env, convention='blender', env_rotation=None, tracer=None, build='device',
+                 geometry_type='schlick', normals=None, device=None):
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        as_t = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
+        self.device = dev
+        self.verts, self.tris = as_t(verts, torch.float32).reshape(-1, 3), as_t(tris, torch.int64).reshape(-1, 3)
+        V = self.verts.shape[0]
+        self.mat5 = torch.cat([as_t(materials[k], torch.float32).reshape(V, -1) for k in ('metallic', 'roughness', 'albedo')], -1)   # perceptual
+        assert self.mat5.shape[1] == 5, self.mat5.shape
+        self.normals = None if normals is None else as_t(normals, torch.float32).reshape(V, 3)
+        if isinstance(env, (str, os.PathLike)):
+            from .envlight import read_hdr
+            env = read_hdr(env)
+        self.env = as_t(env, torch.float32)
+        assert self.env.ndim == 3 and self.env.shape[2] == 3, self.env.shape
+        if convention not in CONVENTIONS:
+            raise ValueError(f'convention {convention!r}: one of {sorted(CONVENTIONS)}')
+        if geometry_type not in GEOMETRY_TYPES:
+            raise ValueError(f'geometry_type {geometry_type!r}: one of {sorted(GEOMETRY_TYPES)}')
+        self.convention, self.geometry_type = CONVENTIONS[convention], GEOMETRY_TYPES[geometry_type]
+        self.rot = None if env_rotation is None else np.asarray(
+            env_rotation.detach().cpu().numpy() if torch.is_tensor(env_rotation) else env_rotation, np.float32).reshape(3, 3)
+        self.tracer = tracer if tracer is not None else RayTracer(self.verts, self.tris.int(), build=build)
+        self._tabs = {}
+
+    def _table(self, n):
+        if n not in self._tabs:
+            self._tabs[n] = sample_table(n, self.device)
+        return self._tabs[n]
+
+    def camera_rays(self, pose, K, h, w):
+        """pixel centres +0.5, the arithmetic of NeROMaterialRenderer._trace_views -> rays_o, rays_d [h w,3]"""
+        dev = self.device
+        pose = torch.as_tensor(np.asarray(pose.cpu() if torch.is_tensor(pose) else pose), dtype=torch.float32).to(dev).reshape(1, 3, 4)
+        K = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K), dtype=torch.float32).to(dev).reshape(1, 3, 3)
+        ys, xs = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing='ij')
+        coords = torch.stack([xs + 0.5, ys + 0.5, torch.ones_like(xs, dtype=torch.float32)], -1).reshape(1, h * w, 3).float()
+        Rm, t = pose[:, :, :3], pose[:, :, 3:]
+        rays_d = torch.nn.functional.normalize((coords @ torch.inverse(K).permute(0, 2, 1)) @ Rm, dim=-1)
+        rays_o = (-Rm.permute(0, 2, 1) @ t).permute(0, 2, 1).repeat(1, h * w, 1)
+        return rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+
+    def surface(self, rays_o, rays_d):
+        """trace and interpolate -> dict: depth [n], hit [n] bool, idx [m] (the hit rays), and for those pts, normal, mat5 (PERCEPTUAL
+        roughness) [m,.]"""
+        depth, face, bary = trace_faces(self.tracer, rays_o, rays_d)
+        hit = face >= 0
+        idx = torch.nonzero(hit)[:, 0]
+        f = self.tris[face[idx].long()]                                                      # [m,3]
+        u, v = bary[idx, 0:1], bary[idx, 1:2]
+        wts = torch.stack([1.0 - u - v, u, v], 1)                                            # [m,3,1]
+        corner = self.verts[f]                                                               # [m,3,3]
+        pts = (wts * corner).sum(1)
+        mat5 = (wts * self.mat5[f]).sum(1)
+        if self.normals is None:
+            # the flat normal on the side the ray came from: the meshes of extract_mesh.py are wound inwards (the reference's trace() negates the
+            # tracer's normals), others outwards -- the side a camera ray meets of a closed mesh is its outside either way
+            nrm = torch.linalg.cross(corner[:, 1] - corner[:, 0], corner[:, 2] - corner[:, 0])
+            nrm = torch.where((nrm * rays_d[idx]).sum(-1, keepdim=True) > 0, -nrm, nrm)
+        else:
+            nrm = (wts * self.normals[f]).sum(1)
+        nrm = torch.nn.functional.normalize(nrm, dim=-1)
+        return {'depth': depth, 'hit': hit, 'idx': idx, 'pts': pts, 'normal': nrm, 'mat5': mat5}
+
+    def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None):
+        """one view -> dict of device tensors [h,w,C]: rgb_lin (linear), rgb (linear_to_srgb, clipped to [0,1]), alpha (coverage), albedo,
+        metallic, roughness (perceptual), normal, depth (10 where nothing is hit), and rgba8 uint8 [h,w,4] (straight alpha).  samples = (Dd,
+        Ds) directions per pixel; ssaa = s renders s h x s w and box-filters with premultiplied alpha; chunk: hit pixels per kernel call (any
+        value gives the same bits); clamp: cap on the environment's radiance per channel (firefly control); background: linear rgb [3] or
+        [h,w,3] behind the uncovered part of a pixel (None: zeros there, rgb_lin is the straight colour)."""
+        s = int(ssaa)
+        assert s >= 1
+        H, W = s * h, s * w
+        Ks = np.diag([float(s), float(s), 1.0]).astype(np.float32) @ np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float32).reshape(3, 3)
+        with torch.no_grad():
+            rays_o, rays_d = self.camera_rays(pose, Ks, H, W)
+            sf = self.surface(rays_o, rays_d)
+            idx, m = sf['idx'], int(sf['idx'].numel())
+            Dd, Ds = int(samples[0]), int(samples[1])
+            rgb = torch.zeros(H * W, 3, device=self.device)
+            if m > 0:
+                rand_d, rand_s = pixel_rotations(idx, seed)
+                pt = point_records(sf['pts'], -rays_d[idx], sf['normal'], estimator_materials(sf['mat5']), rand_d, rand_s)
+                rgb[idx] = relight_points(self.tracer, pt, self._table(Dd), self._table(Ds), self.env, self.convention, self.rot, clamp,
+                                          self.geometry_type, chunk)[0]
+            alpha = sf['hit'].float().reshape(H * W, 1)
+            full = lambda x: torch.zeros(H * W, x.shape[1], device=self.device).index_copy_(0, idx, x)
+            planes = torch.cat([rgb, full(sf['mat5']), full(sf['normal']), (sf['depth'].reshape(-1, 1) * alpha), alpha], -1)    # premultiplied
+            planes = planes.reshape(h, s, w, s, planes.shape[1]).mean((1, 3))
+            a = planes[..., 12:13]
+            straight = planes[..., :12] / torch.clamp(a, min=1e-12)
+            straight = torch.where(a > 0, straight, torch.zeros_like(straight))
+            rgb_lin = straight[..., 0:3]
+            if background is not None:
+                bg = torch.as_tensor(np.asarray(background.cpu() if torch.is_tensor(background) else background), dtype=torch.float32).to(self.device)
+                rgb_lin = planes[..., 0:3] + (1.0 - a) * bg.expand(h, w, 3)
+            srgb = torch.clamp(linear_to_srgb(rgb_lin), 0.0, 1.0)
+            rgba8 = torch.round(torch.cat([srgb, a], -1) * 255.0).to(torch.uint8)
+            nrm = torch.nn.functional.normalize(straight[..., 8:11], dim=-1)
+            depth = torch.where(a > 0, straight[..., 11:12], torch.full_like(a, MISS_DEPTH))
+        return {'rgb_lin': rgb_lin, 'rgb': srgb, 'alpha': a, 'albedo': straight[..., 5:8], 'metallic': straight[..., 3:4],
+                'roughness': straight[..., 4:5], 'normal': nrm, 'depth': depth, 'rgba8': rgba8}
+
+    def render_orbit(self, out_dir, num=360, azimuth=0.0, elevation=30.0, dist=3.0, h=800, w=800, K=None, **kw):
+        """the reference's relighting orbit: view k of relighting_poses(num, azimuth, elevation, dist), as Blender sees it over the mesh's own
+        frame (poses_in_mesh_frame) -> out_dir/k.png (RGBA).  -> the paths"""
+        os.makedirs(out_dir, exist_ok=True)
+        K = default_K(h, w) if K is None else K
+        paths = []
+        for k, pose in enumerate(poses_in_mesh_frame(relighting_poses(num, azimuth, elevation, dist))):
+            out = self.render(pose, K, h, w, **kw)
+            paths.append(os.path.join(out_dir, f'{k}.png'))
+            write_rgba_png(paths[-1], out['rgba8'])
+        return paths

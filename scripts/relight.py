@@ -1,0 +1,75 @@
+"""Relight a Stage-I mesh with its Stage-II materials under an HDR environment map, on the GPU: the reference's relight.py without Blender
+(nero_amd.relight; direct lighting with shadows, no inter-reflection -- DESIGN.md 9.12).
+
+    python scripts/relight.py --mesh M.ply --material DIR --hdr E.hdr --name N
+    python scripts/relight.py --mesh M.ply --cfg configs/material/x.yaml --model model.pth --hdr E.hdr --name N
+
+--material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
+materials are predicted from the trained Stage-II network instead.  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--mesh', required=True)
+    ap.add_argument('--material', help='directory with metallic.npy, roughness.npy, albedo.npy')
+    ap.add_argument('--cfg', help='Stage-II yaml config (with --model), instead of --material')
+    ap.add_argument('--model', help='Stage-II checkpoint')
+    ap.add_argument('--hdr', required=True)
+    ap.add_argument('--name', required=True)
+    ap.add_argument('--trans', action='store_true', help="the reference's 90 degree turn about x, applied to the vertices")
+    ap.add_argument('--width', type=int, default=800)
+    ap.add_argument('--height', type=int, default=800)
+    ap.add_argument('--samples', type=int, nargs='+', default=[128, 128], help='diffuse and specular directions per pixel (one number: both)')
+    ap.add_argument('--num', type=int, default=360)
+    ap.add_argument('--azimuth', type=float, default=0.0)
+    ap.add_argument('--elevation', type=float, default=30.0)
+    ap.add_argument('--cam_dist', type=float, default=3.0)
+    ap.add_argument('--ssaa', type=int, default=1)
+    ap.add_argument('--clamp', type=float, default=None, help="cap on the environment's radiance per channel (firefly control)")
+    ap.add_argument('--convention', default='blender', choices=['blender', 'nero', 'nero_real'],
+                    help="how the map is laid out: Blender's equirectangular image, or this project's env_light grid (is_real 0 / 1)")
+    ap.add_argument('--out', default='data/relight')
+    a = ap.parse_args(argv)
+
+    import torch
+    from nero_amd.mesh import read_ply
+    from nero_amd.relight import Relighter, load_materials
+    verts, tris = read_ply(a.mesh)
+    verts = np.asarray(verts, np.float32)
+    if a.material:
+        materials = load_materials(a.material)
+    elif a.cfg and a.model:
+        import yaml
+        from nero_amd.renderer import NeROMaterialRenderer
+        with open(a.cfg) as fh:
+            cfg = yaml.safe_load(fh)
+        net = NeROMaterialRenderer(cfg, is_train=False, mesh=(verts, np.asarray(tris, np.int32)))
+        ckpt = torch.load(a.model, map_location='cpu')
+        net.load_state_dict(ckpt.get('network_state_dict', ckpt))
+        net = net.cuda().eval()
+        materials = net.predict_materials_of_vertices(torch.from_numpy(verts).cuda())
+    else:
+        ap.error('give --material DIR, or --cfg and --model')
+    if materials['albedo'].shape[0] != verts.shape[0]:
+        raise SystemExit(f"{materials['albedo'].shape[0]} material rows for {verts.shape[0]} vertices: --material does not belong to --mesh")
+    if a.trans:                                                           # (x, y, z) -> (x, -z, y)
+        verts = verts @ np.asarray([[1, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32).T
+    samples = (a.samples * 2)[:2]
+    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention)
+    out_dir = os.path.join(a.out, a.name)
+    paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
+                            samples=samples, ssaa=a.ssaa, clamp=a.clamp)
+    print(f'{len(paths)} views of {a.width} x {a.height} at {samples[0]}+{samples[1]} samples -> {out_dir}')
+
+
+if __name__ == '__main__':
+    main()
