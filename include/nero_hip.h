@@ -250,7 +250,10 @@ int nero_wn_forward_batch(const nero_wn_job* jobs /*host*/, int n_jobs, void* st
 /* The weight-norm backward ALONE, for hosts that keep their own optimiser (the drop-in renderers under torch.optim.Adam: round 6): given
  * dL/dW_eff of every weight-normed matrix, dg = <dW, v> inv_norm and dv = g inv_norm (dW - <dW, v> inv_norm^2 v) in ONE launch -- what
  * autograd does per Linear through torch._weight_norm_interface_backward (nn.utils.weight_norm, network/field.py:118-119, 323-331).
- * inv_norm: the row norms nero_wn_forward_batch left behind. */
+ * inv_norm: the row norms nero_wn_forward_batch left behind.
+ * All three calls: n_jobs / n_wn in [0, NERO_MAX_WN_JOBS], n_plain >= 0 (any number: chunks of NERO_MAX_ADAM_JOBS), step >= 1, a job array
+ * with a positive count and every pointer a call uses non-NULL, rows, cols and n > 0; anything else is NERO_ERR_ARG before the first launch,
+ * nothing written (nero_wn_adam_batch checks the plain jobs before it launches the weight-norm ones). */
 typedef struct {
     const float* v; const float* g; const float* inv_norm; const float* dW;
     float* dv; float* dg;                /* out: [rows, cols], [rows]                                                                 */

@@ -151,6 +151,15 @@ int nero_wn_backward_batch(const nero_wn_grad_job* jobs, int n_jobs, void* strea
 int nero_wn_adam_batch(const nero_wn_job* wn, int n_wn, const nero_adam_job* plain, int n_plain, float lr, float beta1, float beta2,
                        float eps, int step, void* stream) {
     if (n_wn < 0 || n_plain < 0 || n_wn > NERO_MAX_WN_JOBS || step < 1) return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: bad argument");
+    if ((n_wn > 0 && !wn) || (n_plain > 0 && !plain)) return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: job array is NULL");
+    // every job of both kinds is validated before the first launch: a refused call changes nothing
+    for (int i = 0; i < n_wn; ++i)
+        if (!wn[i].v_rw || !wn[i].g_rw || !wn[i].dW || !wn[i].inv_norm || !wn[i].m_v || !wn[i].v_v || !wn[i].m_g || !wn[i].v_g ||
+            wn[i].rows <= 0 || wn[i].cols <= 0)
+            return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: bad weight-norm job");
+    for (int i = 0; i < n_plain; ++i)
+        if (!plain[i].p || !plain[i].grad || !plain[i].m || !plain[i].v || plain[i].n <= 0)
+            return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: bad Adam job");
     AdamHyper H;
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     H.lr_over_bc1 = (float)(lr / bc1);
@@ -160,8 +169,6 @@ int nero_wn_adam_batch(const nero_wn_job* wn, int n_wn, const nero_adam_job* pla
         WnBatch B;
         int max_rows = 1;
         for (int i = 0; i < n_wn; ++i) {
-            if (!wn[i].v_rw || !wn[i].g_rw || !wn[i].dW || !wn[i].inv_norm || !wn[i].m_v || !wn[i].v_v || !wn[i].m_g || !wn[i].v_g)
-                return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: bad weight-norm job");
             B.job[i] = wn[i];
             max_rows = wn[i].rows > max_rows ? wn[i].rows : max_rows;
         }
@@ -172,10 +179,8 @@ int nero_wn_adam_batch(const nero_wn_job* wn, int n_wn, const nero_adam_job* pla
         AdamBatch A;
         int max_n = 1;
         for (int i = 0; i < n; ++i) {
-            const nero_adam_job& J = plain[i0 + i];
-            if (!J.p || !J.grad || !J.m || !J.v || J.n <= 0) return nero_fail(NERO_ERR_ARG, "nero_wn_adam_batch: bad Adam job");
-            A.job[i] = J;
-            max_n = J.n > max_n ? J.n : max_n;
+            A.job[i] = plain[i0 + i];
+            max_n = A.job[i].n > max_n ? A.job[i].n : max_n;
         }
         int bx = (max_n + 255) / 256;
         bx = bx > 64 ? 64 : bx;
