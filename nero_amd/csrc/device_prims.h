@@ -1,5 +1,6 @@
 // device_prims.h -- wave and workgroup reductions, the order-preserving float image and the concurrent union-find shared by the mesh
-// kernels (mesh_clean, mesh_simplify, mesh_atlas, bvh_build, geom_eval, mcubes, texture).  Wavefronts are 64 lanes (gfx950).
+// kernels (mesh_clean, mesh_simplify, mesh_atlas, bvh_build, geom_eval, mcubes, texture), and the fixed-order float tree sum of the loss
+// kernels (mat_loss, step_glue).  Wavefronts are 64 lanes (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +63,23 @@ __device__ __forceinline__ int block_sum(int v, int* part) {
     for (int q = 0; q < THREADS / 64; ++q) tot += part[q];
     __syncthreads();
     return tot;
+}
+
+// float sum of v over the THREADS threads of the workgroup as a binary tree in LDS, in every thread; sh: THREADS shared floats.  Not an
+// overload of block_sum: it pairs thread t with t + THREADS / 2, t + THREADS / 4, ..., an order of its own that the loss values are pinned
+// to (the same bits every run, whatever the scheduling).  Ends with a barrier, so `sh` may be reused by the next call.
+template <int THREADS>
+__device__ __forceinline__ float block_tree_sum(float v, float* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const float r = sh[0];
+    __syncthreads();
+    return r;
 }
 
 // One atomic per wave and group, not per lane: a surface with floaters is one component that holds nearly every vertex, and per-lane

@@ -16,12 +16,14 @@
 #include <stdint.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
-#include "ide.h"                                     // IDE_N, ide_forward, rows_put / rows_flush (rows.h)
+#include "ide.h"                                     // IDE_N, ide_forward and the table check, rows_put / rows_flush (rows.h)
+#include "shade_math.h"                              // exp_head, srgb_f
 
 namespace {
 
+using namespace nero_shade;
+
 constexpr int ENV_MAX_SIZE = 16384;
-constexpr float SRGB_EPS = 1.1920928955078125e-07f;     // torch.finfo(float32).eps
 
 // pixel p = row r, column c of an h x w panorama: az = linspace(1, 0, w)[c] 2 pi - pi / 2, el = linspace(1, -1, h)[r] pi / 2
 // (a one-element linspace is its start value)
@@ -63,10 +65,6 @@ __global__ __launch_bounds__(ROW_BLOCK) void env_encode_kernel(const float* __re
     if (sphere) rows_flush<72>(stage, X, ld, 72, row0, n_pad);
 }
 
-__device__ __forceinline__ float env_srgb(float x) {         // utils/raw_utils.py:4-10
-    return x <= 0.0031308f ? (323.f / 25.f) * x : (211.f * powf(fmaxf(x, SRGB_EPS), 5.f / 12.f) - 11.f) / 200.f;
-}
-
 // raw [rows, 4] (the head of the chain: 3 of 4 columns) -> rgb [n, 3]
 __global__ __launch_bounds__(256) void env_finish_kernel(const float* __restrict__ raw, int64_t n3, float exp_max, int gamma,
                                                          float* __restrict__ rgb) {
@@ -74,8 +72,8 @@ __global__ __launch_bounds__(256) void env_finish_kernel(const float* __restrict
     if (i >= n3) return;
     const int64_t r = i / 3;
     const int c = (int)(i - r * 3);
-    const float v = expf(fminf(raw[r * 4 + c], exp_max));
-    rgb[i] = gamma ? env_srgb(v) : v;
+    const float v = exp_head(raw[r * 4 + c], exp_max);
+    rgb[i] = gamma ? srgb_f(v) : v;
 }
 
 // Radiance RGBE: v = max(r, g, b) = m 2^e, m in [0.5, 1); byte = trunc(c 2^(8 - e)), fourth byte e + 128.  The scale is a power of two, so
@@ -109,6 +107,7 @@ unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 int launch_encode(const char* fn, const float* src, int h, int w, int64_t first, int n, int is_real, int sphere, float roughness, float* X,
                   float* dirs, void* stream) {
     if (n == 0) return NERO_OK;
+    if (X) NERO_CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     hipLaunchKernelGGL(env_encode_kernel, dim3((unsigned)(n_pad / ROW_BLOCK)), dim3(ROW_BLOCK), 0, (hipStream_t)stream, src, h, w, first, n, n_pad,
                        is_real, sphere, roughness, X, dirs);

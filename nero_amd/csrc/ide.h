@@ -1,8 +1,9 @@
 // ide.h -- the integrated directional encoding (generate_ide_fn(5), utils/ref_utils.py:53-117) with everything the compiler can know
 // at compile time known at compile time: the 36 (l, m) pairs, the 222 polynomial coefficients, every array index.  Included by
-// shade.hip (Stage I, with the roughness attenuation) and mc_shade.hip (Stage II, kappa_inv = 0) inside their anonymous namespaces.
+// shade.hip (Stage I, with the roughness attenuation), mc_shade.hip (Stage II, kappa_inv = 0) and envlight.hip (the panorama's directions).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <type_traits>
 #include "rows.h"                                    // rows_put / rows_flush: the encoders' coalesced row stores
 
@@ -10,7 +11,7 @@ constexpr int IDE_N = 36;
 
 // The same coefficients as COMPILE-TIME constants for the unrolled kernels below (literal operands of the FMAs: 222 run-time scalars
 // loaded from c_ide_mat do not fit the scalar register file -- the compiler parked them in VGPR lanes, 1800 v_readlane per thread).
-// The host initialisers check them against their libm-computed tables bit for bit (ide_tab_equals).
+// ide_check_table (below) checks them against the libm-computed table bit for bit.
 constexpr double cx_fact(int n) { double r = 1.0; for (int i = 2; i <= n; ++i) r *= i; return r; }
 constexpr double cx_binom(double a, int k) { double p = 1.0; for (int i = 0; i < k; ++i) p *= (a - i); return p / cx_fact(k); }
 constexpr double cx_sqrt(double x) { double r = x > 1.0 ? x : 1.0; for (int i = 0; i < 256; ++i) r = 0.5 * (r + x / r); return r; }
@@ -31,12 +32,34 @@ constexpr IdeTab make_ide_tab() {
 }
 __device__ constexpr IdeTab IDE_TAB = make_ide_tab();
 
-inline bool ide_tab_equals(const float* mat /*[17 * IDE_N], k-major*/) {
-    constexpr IdeTab tab = make_ide_tab();
-    for (int q = 0; q < 17 * IDE_N; ++q)
-        if (tab.c[q] != mat[q]) return false;
-    return true;
+// The check of that table (host): the libm evaluation of utils/ref_utils.py:53-82 must give the compile-time table bit for bit.  Evaluated
+// once per process; 0 = equal, -1 = not.  Every entry point that launches a kernel reading IDE_TAB calls it first.
+namespace ide_libm {
+inline double fact(int n) { double r = 1.0; for (int i = 2; i <= n; ++i) r *= i; return r; }
+inline double gen_binom(double a, int k) { double p = 1.0; for (int i = 0; i < k; ++i) p *= (a - i); return p / fact(k); }
+inline double assoc_legendre_coeff(int l, int m, int k) {
+    return ((m & 1) ? -1.0 : 1.0) * pow(2.0, l) * fact(l) / fact(k) / fact(l - k - m) * gen_binom(0.5 * (l + k + m - 1.0), l);
 }
+inline double sph_harm_coeff(int l, int m, int k) {
+    return sqrt((2.0 * l + 1.0) * fact(l - m) / (4.0 * M_PI * fact(l + m))) * assoc_legendre_coeff(l, m, k);
+}
+}  // namespace ide_libm
+inline int ide_check_table() {
+    static bool done = false;
+    if (done) return 0;
+    constexpr IdeTab tab = make_ide_tab();
+    int i = 0;
+    for (int e = 0; e < 5; ++e) {
+        const int l = 1 << e;
+        for (int m = 0; m <= l; ++m, ++i)
+            for (int k = 0; k < 17; ++k)
+                if (tab.c[k * IDE_N + i] != (k <= l - m ? (float)ide_libm::sph_harm_coeff(l, m, k) : 0.f)) return -1;
+    }
+    done = true;
+    return 0;
+}
+// (the refusal, spelled once for every caller; nero_fail: common.h)
+#define NERO_CHECK_IDE() do { if (ide_check_table() != 0) return nero_fail(NERO_ERR_LAUNCH, "IDE coefficient table of ide.h differs from the libm one"); } while (0)
 
 // Compile-time walk over the 36 (l, m) pairs in table order (l = 1, 2, 4, 8, 16; m = 0..l): f(i, e, l, m) with all four as
 // integral constants.  The loop form -- m = c_ide_m[i] read at run time -- indexes re[], im[], dre[] dynamically, which puts those

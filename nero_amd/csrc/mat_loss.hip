@@ -11,25 +11,25 @@
 #include <math.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "device_prims.h"                            // block_tree_sum
+#include "shade_math.h"                              // srgb_f, SRGB_EPS, sgn, sigmoid_f, PI_F
 
 namespace {
+
+using namespace nero_shade;
+using nero_prims::block_tree_sum;
 
 constexpr int LB = 256;
 // (constants as the Python glue of the reference forms them: double arithmetic, then one rounding to fp32 when they meet a tensor)
 constexpr float R_MIN = (float)(0.04 * 0.04);            // roughness range [0.04^2, 1]
 constexpr float R_SPAN = (float)(1.0 - 0.04 * 0.04);
 constexpr float H_R_HI = (float)(0.98 * 0.98), H_R_LO = (float)(0.02 * 0.02), H_M_HI = 0.98f, H_M_LO = 0.02f;
-constexpr float SRGB_EPS = 1.1920928955078125e-07f;     // torch.finfo(float32).eps
 
-__device__ __forceinline__ float srgb(float x) {
-    return x <= 0.0031308f ? (323.f / 25.f) * x : (211.f * powf(fmaxf(x, SRGB_EPS), 5.f / 12.f) - 11.f) / 200.f;
-}
+// (srgb_grad stays local: shade_math.h says why)
 __device__ __forceinline__ float srgb_grad(float x) {
     if (x <= 0.0031308f) return 323.f / 25.f;
     return (211.f / 200.f) * (5.f / 12.f) * powf(fmaxf(x, SRGB_EPS), -7.f / 12.f);       // (x > 0.0031308 > eps: the clamp is inactive)
 }
-__device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ __launch_bounds__(LB) void reg_points_kernel(int P, const float* __restrict__ pts, const float* __restrict__ nrm,
                                                         const float* __restrict__ ang01, const float* __restrict__ eps, float eps_const,
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(LB) void reg_points_kernel(int P, const float* __re
     const float xl = fmaxf(l0 > l1 ? l0 : l1, 1e-12f);
     xx /= xl; xy /= xl; xz /= xl;
     const float yx = ny * xz - nz * xy, yy = nz * xx - nx * xz, yz = nx * xy - ny * xx;
-    const float a = ang01[p] * 3.14159274101257324f * 2.f;
+    const float a = ang01[p] * PI_F * 2.f;
     const float c = cosf(a), s = sinf(a), e = eps ? eps[p] : eps_const;
     out[3 * p] = px; out[3 * p + 1] = py; out[3 * p + 2] = pz;
     float* o = out + (size_t)3 * (P + p);
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(LB) void reg_points_kernel(int P, const float* __re
 __global__ __launch_bounds__(LB) void head_fwd_kernel(int n5, const float* __restrict__ raw, float* __restrict__ mat) {
     const int i = blockIdx.x * LB + threadIdx.x;
     if (i >= n5) return;
-    const float s = sigmoidf(raw[i]);
+    const float s = sigmoid_f(raw[i]);
     // (separate multiply and add, as the tensor ops of the reference round them: a contracted fma moves the roughness by one ulp, and
     //  the specular sample directions -- hence every light-MLP gradient -- with it.  What is bit for bit is this affine step on the kernel's
     //  own sigmoid; the sigmoid itself goes through the device expf and differs from a host float32 sigmoid by an ulp on ~3 % of inputs)
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(LB) void head_fwd_kernel(int n5, const float* __res
 __global__ __launch_bounds__(LB) void head_bwd_kernel(int n5, const float* __restrict__ raw, const float* __restrict__ d_mat, float* __restrict__ d_raw) {
     const int i = blockIdx.x * LB + threadIdx.x;
     if (i >= n5) return;
-    const float s = sigmoidf(raw[i]);
+    const float s = sigmoid_f(raw[i]);
     const float g = d_mat[i] * ((i % 5 == 1) ? R_SPAN : 1.f);
     d_raw[i] = g * (1.f - s) * s;
 }
@@ -93,7 +93,7 @@ __device__ __forceinline__ PointLoss point_terms(const nero_mat_loss_cfg& c, int
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         x[k] = rgb_lin[3 * p + k];
-        sr[k] = srgb(x[k]);
+        sr[k] = srgb_f(x[k]);
         df[k] = sr[k] - gt[3 * p + k];
         if (!GRAD && rgb_pr) rgb_pr[3 * p + k] = sr[k];
     }
@@ -144,7 +144,7 @@ __device__ __forceinline__ PointLoss point_terms(const nero_mat_loss_cfg& c, int
         float y[3], v[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            y[k] = srgb(dl[3 * p + k]);
+            y[k] = srgb_f(dl[3 * p + k]);
             v[k] = fminf(fmaxf(y[k], 0.f), 1.f);
         }
         const float mean = (v[0] + v[1] + v[2]) / 3.f;
@@ -166,19 +166,6 @@ __device__ __forceinline__ PointLoss point_terms(const nero_mat_loss_cfg& c, int
     return L;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {          // fixed-order tree over the 256 threads
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = LB / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(LB) void loss_fwd_kernel(nero_mat_loss_cfg c, int P, int has_reg, const float* __restrict__ mat,
                                                       const float* __restrict__ rgb_lin, const float* __restrict__ dl, const float* __restrict__ gt,
                                                       float* __restrict__ rgb_pr, float* __restrict__ partials) {
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(LB) void loss_fwd_kernel(nero_mat_loss_cfg c, int P
     const int p = blockIdx.x * LB + threadIdx.x;
     PointLoss L = {0.f, 0.f, 0.f, 0.f};
     if (p < P) L = point_terms<false>(c, P, has_reg, p, mat, rgb_lin, dl, gt, rgb_pr, 0.f, 0.f, nullptr, nullptr, nullptr);
-    const float a = block_sum(L.rgb, sh), b = block_sum(L.reg, sh), h = block_sum(L.hinge, sh), d = block_sum(L.dl, sh);
+    const float a = block_tree_sum<LB>(L.rgb, sh), b = block_tree_sum<LB>(L.reg, sh), h = block_tree_sum<LB>(L.hinge, sh), d = block_tree_sum<LB>(L.dl, sh);
     if (threadIdx.x == 0) {
         float* o = partials + 4 * blockIdx.x;
         o[0] = a; o[1] = b; o[2] = h; o[3] = d;
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(LB) void loss_sum_kernel(nero_mat_loss_cfg c, int P
     for (int i = threadIdx.x; i < nb; i += LB) {
         a += partials[4 * i]; b += partials[4 * i + 1]; h += partials[4 * i + 2]; d += partials[4 * i + 3];
     }
-    a = block_sum(a, sh); b = block_sum(b, sh); h = block_sum(h, sh); d = block_sum(d, sh);
+    a = block_tree_sum<LB>(a, sh); b = block_tree_sum<LB>(b, sh); h = block_tree_sum<LB>(h, sh); d = block_tree_sum<LB>(d, sh);
     if (threadIdx.x == 0) {
         const float inv = 1.f / (float)P;
         const float l_rgb = a * inv, l_reg = b * inv + c.hinge_weight * h, l_dl = d * inv;

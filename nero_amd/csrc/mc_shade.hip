@@ -12,34 +12,12 @@
 #include <math.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
-#include "ide.h"                                     // IDE_N, the compile-time coefficient table, ide_forward / ide_backward
+#include "ide.h"                                     // IDE_N, the compile-time coefficient table and its check, ide_forward / ide_backward
+#include "shade_math.h"                              // sat, TWO_PI / PI_F / HALF_PI, exp_head, pe3, human_geom, put_inner_row
 
-// IDE helpers live in shade.hip's translation unit; re-declare the small pieces needed here (same formulas, own TU).
 namespace {
 
-
-double fact(int n) { double r = 1.0; for (int i = 2; i <= n; ++i) r *= i; return r; }
-double gen_binom(double a, int k) { double p = 1.0; for (int i = 0; i < k; ++i) p *= (a - i); return p / fact(k); }
-double sph_coeff(int l, int m, int k) {
-    const double al = ((m & 1) ? -1.0 : 1.0) * pow(2.0, l) * fact(l) / fact(k) / fact(l - k - m) * gen_binom(0.5 * (l + k + m - 1.0), l);
-    return sqrt((2.0 * l + 1.0) * fact(l - m) / (4.0 * M_PI * fact(l + m))) * al;
-}
-int init_tables() {
-    static bool done = false;
-    if (done) return 0;
-    float mat[17 * IDE_N];
-    for (int i = 0; i < 17 * IDE_N; ++i) mat[i] = 0.f;
-    int i = 0;
-    for (int e = 0; e < 5; ++e) {
-        const int l = 1 << e;
-        for (int m = 0; m <= l; ++m, ++i) {
-            for (int k = 0; k <= l - m; ++k) mat[k * IDE_N + i] = (float)sph_coeff(l, m, k);
-        }
-    }
-    if (!ide_tab_equals(mat)) return -1;               // the compile-time table of ide.h must be this libm one, bit for bit
-    done = true;
-    return 0;
-}
+using namespace nero_shade;
 
 // IDE with kappa_inv = 0 (no attenuation): ide_forward<false> / ide_backward<false> of ide.h
 __device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -55,10 +33,7 @@ __device__ __forceinline__ void ortho3(const float* d, float* o) {            //
 __device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {
     o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ float sat(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 __device__ __forceinline__ float satg(float x) { return (x >= 0.f && x <= 1.f) ? 1.f : 0.f; }   // gradient gate of clamp(x,0,1)
-
-constexpr float TWO_PI = 6.283185307179586f;
 
 // per-point record (field.py:1014-1017, 951-957)
 __global__ void mc_point_setup_kernel(const float* __restrict__ pts, const float* __restrict__ view, const float* __restrict__ normals,
@@ -158,25 +133,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void mc_encode_miss_kernel(const float* 
 }
 
 // human light input for miss rows (get_human_light, field.py:820-834): zero-variance IPE of the hit on the z=0 plane of the
-// per-point human frame.  Xh [rows,24], hmask[rows]
-struct HumanGeom { float px, py, pz, dx, dy, dz, dzp, dist, ix, iy, h; bool hits0; };
-__device__ __forceinline__ HumanGeom human_geom(const float* __restrict__ pose, const float* p, const float* rf) {
-    HumanGeom g;
-    g.px = pose[0] * p[0] + pose[1] * p[1] + pose[2] * p[2] + pose[3];
-    g.py = pose[4] * p[0] + pose[5] * p[1] + pose[6] * p[2] + pose[7];
-    g.pz = pose[8] * p[0] + pose[9] * p[1] + pose[10] * p[2] + pose[11];
-    g.dx = pose[0] * rf[0] + pose[1] * rf[1] + pose[2] * rf[2];
-    g.dy = pose[4] * rf[0] + pose[5] * rf[1] + pose[6] * rf[2];
-    g.dz = pose[8] * rf[0] + pose[9] * rf[1] + pose[10] * rf[2];
-    g.hits0 = fabsf(g.dz) > 1e-4f;
-    g.dzp = g.hits0 ? g.dz : 1e-4f;
-    g.dist = -g.pz / g.dzp;
-    g.ix = g.px + g.dist * g.dx;
-    g.iy = g.py + g.dist * g.dy;
-    const float mx = g.ix * 0.3f, my = g.iy * 0.3f;
-    g.h = (g.hits0 && sqrtf(mx * mx + my * my) < 1.5f && g.dist > 0.f) ? 1.f : 0.f;
-    return g;
-}
+// per-point human frame (human_geom: shade_math.h).  Xh [rows,24], hmask[rows]
 __global__ void mc_human_encode_kernel(const float* __restrict__ dirs, const int* __restrict__ idx, const float* __restrict__ pt, int D,
                                        const float* __restrict__ poses, int n, int n_pad, float* __restrict__ Xh, float* __restrict__ hmask) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -188,7 +145,7 @@ __global__ void mc_human_encode_kernel(const float* __restrict__ dirs, const int
     const float mean[2] = {g.ix * 0.3f * g.h, g.iy * 0.3f * g.h};
     float sc = 1.f;
     for (int s = 0; s < 6; ++s) {
-        for (int c = 0; c < 2; ++c) { o[2 * s + c] = sinf(mean[c] * sc); o[12 + 2 * s + c] = sinf(mean[c] * sc + 1.5707963267948966f); }
+        for (int c = 0; c < 2; ++c) { o[2 * s + c] = sinf(mean[c] * sc); o[12 + 2 * s + c] = sinf(mean[c] * sc + HALF_PI); }
         sc *= 2.f;
     }
     hmask[k] = g.h;
@@ -214,40 +171,12 @@ __global__ __launch_bounds__(ROW_BLOCK) void mc_encode_hit_kernel(const float* _
     const float z = live ? 1.f : 0.f;
     const int row = idx[live ? k : 0];
     const float* x = pos + (size_t)row * 3;
-    // X row = [PE-8(x_hit) 51 | IDE(reflect(-w, n_hit)) 72 | 0 x 5], written as columns 0..63 and 64..127
     float pe[51];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pe[c] = x[c];
-    {
-        float f = 1.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) pe[3 + 6 * i + c] = sinf(x[c] * f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) pe[3 + 6 * i + 3 + c] = cosf(x[c] * f);
-            f *= 2.f;
-        }
-    }
+    pe3<8>(x, pe);
     float nh[3], vv[3], refl[3], e[72];
     hit_reflection(dirs + (size_t)row * 3, fnrm + (size_t)row * 3, nh, vv, refl);
     ide_forward<false>(refl[0], refl[1], refl[2], 0.f, e);
-    rows_put<64, 0, 51>(stage, pe, z);
-    {
-        float h[13];
-#pragma unroll
-        for (int c = 0; c < 13; ++c) h[c] = e[c];
-        rows_put<64, 51, 13>(stage, h, z);
-    }
-    rows_flush<64>(stage, X, 128, 0, row0, n_pad);
-    {
-        float h[59];
-#pragma unroll
-        for (int c = 0; c < 59; ++c) h[c] = e[13 + c];
-        rows_put<64, 0, 59>(stage, h, z);
-    }
-    rows_zero<64, 59, 5>(stage);
-    rows_flush<64>(stage, X, 128, 64, row0, n_pad);
+    put_inner_row(stage, pe, e, z, X, row0, n_pad);       // [PE-8(x_hit) 51 | IDE(reflect(-w, n_hit)) 72 | 0 x 5]
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -283,9 +212,9 @@ __device__ __forceinline__ void brdf_terms(const float* q, const float* w, bool 
         b.G = 2.f / (b.sv + b.sl);
     }
     b.t = b.noh * b.noh * (a2 - 1.f) + 1.f;
-    b.dden = 3.14159265358979f * b.t * b.t + 1e-4f;
+    b.dden = PI_F * b.t * b.t + 1e-4f;
     b.dg = a2 / b.dden;
-    b.prob = diffuse ? b.nol / 3.14159265358979f * wd : b.dg * b.noh / (4.f * b.hov + 1e-5f) * ws;
+    b.prob = diffuse ? b.nol / PI_F * wd : b.dg * b.noh / (4.f * b.hov + 1e-5f) * ws;
     b.N = b.dg * b.G;
     b.Q = 4.f * nov * b.prob + 1e-5f;
     b.W = b.N / b.Q;
@@ -310,17 +239,17 @@ __device__ __forceinline__ void light_value(int s, const Lights& P_, float near,
     if (s == DEAD_SLOT) {
         for (int c = 0; c < 3; ++c) L[c] = 0.f;
     } else if (s >= 0) {
-        for (int c = 0; c < 3; ++c) outer[c] = expf(fminf(P_.outer_raw[(size_t)s * 4 + c], P_.emax));
+        for (int c = 0; c < 3; ++c) outer[c] = exp_head(P_.outer_raw[(size_t)s * 4 + c], P_.emax);
         if (P_.human_raw && s < P_.n_hum) {                 // (miss rows [0, n_hum) own a row of the human-light MLP: nero_mc_split_classes)
             const float hm = P_.hmask[s];
-            for (int c = 0; c < 3; ++c) hl[c] = expf(fminf(P_.human_raw[(size_t)s * 4 + c], 0.f)) * hm;
-            hw_raw = expf(fminf(P_.human_raw[(size_t)s * 4 + 3], 0.f)) * hm;
+            for (int c = 0; c < 3; ++c) hl[c] = exp_head(P_.human_raw[(size_t)s * 4 + c], 0.f) * hm;
+            hw_raw = exp_head(P_.human_raw[(size_t)s * 4 + 3], 0.f) * hm;
             hw = sat(hw_raw);
         }
         for (int c = 0; c < 3; ++c) L[c] = (outer[c] * (1.f - hw) + hl[c] * hw) * near;
     } else {
         const int k = -s - 1;
-        for (int c = 0; c < 3; ++c) L[c] = expf(fminf(P_.inner_raw[(size_t)k * 4 + c], P_.imax)) * near;
+        for (int c = 0; c < 3; ++c) L[c] = exp_head(P_.inner_raw[(size_t)k * 4 + c], P_.imax) * near;
     }
 }
 
@@ -417,22 +346,22 @@ __global__ __launch_bounds__(64) void mc_combine_bwd_kernel(const float* __restr
             float dhw = 0.f;
             for (int c = 0; c < 3; ++c) {
                 const float dl_ = dL[c] * near;
-                o4[c] = LP.outer_raw[(size_t)s * 4 + c] <= LP.emax ? dl_ * (1.f - hw) * ou[c] : 0.f;
+                o4[c] = exp_head_gate(LP.outer_raw[(size_t)s * 4 + c], LP.emax) ? dl_ * (1.f - hw) * ou[c] : 0.f;
                 if (LP.human_raw && s < LP.n_hum) {
-                    h4[c] = LP.human_raw[(size_t)s * 4 + c] <= 0.f ? dl_ * hw * hl[c] : 0.f;
+                    h4[c] = exp_head_gate(LP.human_raw[(size_t)s * 4 + c], 0.f) ? dl_ * hw * hl[c] : 0.f;
                     dhw += dl_ * (hl[c] - ou[c]);
                 }
             }
             reinterpret_cast<float4*>(d_outer_raw)[s] = make_float4(o4[0], o4[1], o4[2], 0.f);
             if (LP.human_raw && s < LP.n_hum) {
                 const float g = (hwr >= 0.f && hwr <= 1.f) ? dhw : 0.f;
-                h4[3] = LP.human_raw[(size_t)s * 4 + 3] <= 0.f ? g * hwr : 0.f;
+                h4[3] = exp_head_gate(LP.human_raw[(size_t)s * 4 + 3], 0.f) ? g * hwr : 0.f;
                 reinterpret_cast<float4*>(d_human_raw)[s] = make_float4(h4[0], h4[1], h4[2], h4[3]);
             }
         } else {
             const int kk = -s - 1;
             float o4[3];
-            for (int c = 0; c < 3; ++c) o4[c] = LP.inner_raw[(size_t)kk * 4 + c] <= LP.imax ? dL[c] * L[c] : 0.f;
+            for (int c = 0; c < 3; ++c) o4[c] = exp_head_gate(LP.inner_raw[(size_t)kk * 4 + c], LP.imax) ? dL[c] * L[c] : 0.f;
             reinterpret_cast<float4*>(d_inner_raw)[kk] = make_float4(o4[0], o4[1], o4[2], 0.f);
         }
         // W = N / Q
@@ -462,9 +391,9 @@ __global__ __launch_bounds__(64) void mc_combine_bwd_kernel(const float* __restr
         }
         // Dg(noh, r)
         const float a2 = r * r;
-        const float dDg_da2 = 1.f / b.dden - a2 * (2.f * 3.14159265358979f * b.t * b.noh * b.noh) / (b.dden * b.dden);
+        const float dDg_da2 = 1.f / b.dden - a2 * (2.f * PI_F * b.t * b.noh * b.noh) / (b.dden * b.dden);
         dr += dDg * dDg_da2 * 2.f * r;
-        dnoh += dDg * (-a2 * (2.f * 3.14159265358979f * b.t * 2.f * b.noh * (a2 - 1.f)) / (b.dden * b.dden));
+        dnoh += dDg * (-a2 * (2.f * PI_F * b.t * 2.f * b.noh * (a2 - 1.f)) / (b.dden * b.dden));
         // Fc = clamp(1-hov,0,1)^5
         const float cc = sat(1.f - b.hov);
         dhov += -5.f * cc * cc * cc * cc * dFc;
@@ -532,7 +461,7 @@ __global__ __launch_bounds__(64) void mc_dir_bwd_kernel(const float* __restrict_
                 float sc = 1.f;
                 for (int t = 0; t < 6; ++t) {
                     for (int c = 0; c < 2; ++c)
-                        dmean[c] += sc * (gx[2 * t + c] * cosf(mean[c] * sc) + gx[12 + 2 * t + c] * cosf(mean[c] * sc + 1.5707963267948966f));
+                        dmean[c] += sc * (gx[2 * t + c] * cosf(mean[c] * sc) + gx[12 + 2 * t + c] * cosf(mean[c] * sc + HALF_PI));
                     sc *= 2.f;
                 }
                 const float dix = 0.3f * hg.h * dmean[0], diy = 0.3f * hg.h * dmean[1];
@@ -705,7 +634,6 @@ __global__ __launch_bounds__(256) void mc_split_scatter_kernel(const float* __re
 }  // namespace
 
 #define GRID1D(n) dim3(((n) + 127) / 128), dim3(128), 0, (hipStream_t)stream
-#define CHECK_T() do { if (init_tables() != 0) return nero_fail(NERO_ERR_LAUNCH, "IDE coefficient table of ide.h differs from the libm one"); } while (0)
 
 extern "C" {
 
@@ -723,7 +651,7 @@ int nero_mc_dirs(const float* pt, const float* tab_d, const float* tab_s, int P,
 }
 
 int nero_mc_encode_miss(const float* dirs, const int* idx, const float* pt, int D, int sphere, int n, float* X, void* stream) {
-    CHECK_T();
+    NERO_CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(mc_encode_miss_kernel, dim3((n_pad + ROW_BLOCK - 1) / ROW_BLOCK), dim3(ROW_BLOCK), 0, (hipStream_t)stream, dirs, idx, pt, D, sphere, n, n_pad, X);
@@ -739,7 +667,7 @@ int nero_mc_human_encode(const float* dirs, const int* idx, const float* pt, int
 }
 
 int nero_mc_encode_hit(const float* dirs, const float* pos, const float* face_normals, const int* idx, int n, float* X, void* stream) {
-    CHECK_T();
+    NERO_CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(mc_encode_hit_kernel, dim3((n_pad + ROW_BLOCK - 1) / ROW_BLOCK), dim3(ROW_BLOCK), 0, (hipStream_t)stream, dirs, pos, face_normals, idx, n, n_pad, X);
@@ -786,7 +714,7 @@ int nero_mc_combine_bwd(const float* pt, const float* dirs, const float* depth, 
 int nero_mc_dir_bwd_h(const float* pt, const float* dirs, const float* face_normals, const int* slot, const float* tab_s,
                       const float* dX_miss, const float* dX_hit, const float* d_wspec, int P, int Dd, int Ds, float* d_mat5, int sphere,
                       const float* dXh, const float* poses, int n_hum, void* stream) {
-    CHECK_T();
+    NERO_CHECK_IDE();
     if (P == 0) return NERO_OK;
     hipLaunchKernelGGL(mc_dir_bwd_kernel, dim3(P), dim3(64), 0, (hipStream_t)stream, pt, dirs, face_normals, slot, tab_s, dX_miss, dX_hit,
                        d_wspec, P, Dd, Ds, d_mat5, sphere, dXh, poses, n_hum);

@@ -19,15 +19,16 @@
 #include "bvh_walk.h"
 #include "common.h"
 #include "relight_plan.h"
+#include "shade_math.h"                      // PI_F, TWO_PI, HALF_PI, sat -- and nothing else: the header says why
 
 namespace {
 
 using namespace nero_bvh;
+using nero_shade::PI_F; using nero_shade::TWO_PI; using nero_shade::HALF_PI; using nero_shade::sat;
 using namespace nero_relight;              // samples_ok, total_ok, waves_per_point, workspace_bytes, grid_blocks (relight_plan.h)
 constexpr float MISS_DEPTH = 10.0f;        // the tracer's miss distance
 constexpr int PRIV_THREADS = 256;          // workgroup of the private-stack kernels (as trace_kernel)
 constexpr int ENV_MAX_SIZE = 16384;
-constexpr float PI_F = 3.14159265358979f, TWO_PI = 6.283185307179586f, HALF_PI = 1.5707963267948966f;
 
 // ---- closest hit with the face ----------------------------------------------------------------------------------------------------------
 // (u, v) of tri_test on triangle `best`: the same operations in the same order
@@ -194,8 +195,6 @@ __global__ __launch_bounds__(256) void relight_rays_kernel(const float* __restri
 }
 
 // ---- the estimator ----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sat(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
 // W = D_ggx G / (4 NoV p + 1e-5) and the Fresnel factor fc = (1 - HoV)^5 of direction w at the point q (shade_mixed, field.py:950-998, as
 // brdf_terms of mc_shade.hip states it): geom 0 = Schlick-GGX product (:892-903), 1 = height-correlated Smith (:905-913); p = the pdf of
 // the strategy that drew the sample, weighted by its share wd = Dd / D or ws = Ds / D of the samples

@@ -9,10 +9,13 @@
 #include "../../include/nero_hip.h"
 #include "common.h"
 #include "rows.h"
+#include "shade_math.h"             // sigmoid_f (no product feeds a sum in it: nothing for the pragma below to keep apart)
 
 #pragma clang fp contract(off)      // keep a*b+c un-fused: the oracle's float32 steps are stated without FMA
 
 namespace {
+
+using nero_shade::sigmoid_f;
 
 constexpr int MAXS = 160;   // max z-values per ray handled by the per-thread buffers
 
@@ -25,8 +28,6 @@ __device__ __forceinline__ float linspace_f32(float start, float end, int steps,
     const int half = steps / 2;
     return i < half ? start + step * (float)i : end - step * (float)(steps - i - 1);
 }
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // z[r, i] = near + (far-near) * lin(0,1,n)[i] (+ (rand1-0.5)*2/n)          (renderer.py:411-417)
 __global__ void coarse_z_kernel(const float* __restrict__ near, const float* __restrict__ far, const float* __restrict__ rand1,

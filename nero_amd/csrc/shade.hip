@@ -9,61 +9,14 @@
 #include <math.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
-#include "ide.h"                                     // IDE_N, the compile-time coefficient table, ide_forward / ide_backward
+#include "ide.h"                                     // IDE_N, the compile-time coefficient table and its check, ide_forward / ide_backward
+#include "shade_math.h"                              // sigmoid_f, srgb_f, exp_head, pe3, human_geom, put_inner_row
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------------------
-// IDE (deg_view = 5): 36 (m,l) pairs, l in {1,2,4,8,16}, polynomial coefficients mat[k][i], k <= 16.  The kernels use the
-// compile-time table of ide.h; this libm evaluation of utils/ref_utils.py:53-82 stays as its check (once per process).
-// ------------------------------------------------------------------------------------------------------------------
+using namespace nero_shade;
 
-double fact(int n) { double r = 1.0; for (int i = 2; i <= n; ++i) r *= i; return r; }
-double gen_binom(double a, int k) { double p = 1.0; for (int i = 0; i < k; ++i) p *= (a - i); return p / fact(k); }
-double assoc_legendre_coeff(int l, int m, int k) {
-    return ((m & 1) ? -1.0 : 1.0) * pow(2.0, l) * fact(l) / fact(k) / fact(l - k - m) * gen_binom(0.5 * (l + k + m - 1.0), l);
-}
-double sph_harm_coeff(int l, int m, int k) {
-    return sqrt((2.0 * l + 1.0) * fact(l - m) / (4.0 * M_PI * fact(l + m))) * assoc_legendre_coeff(l, m, k);
-}
-
-int init_ide_tables() {
-    static bool done = false;
-    if (done) return 0;
-    float mat[17 * IDE_N];
-    for (int i = 0; i < 17 * IDE_N; ++i) mat[i] = 0.f;
-    int i = 0;
-    for (int e = 0; e < 5; ++e) {
-        const int l = 1 << e;
-        for (int m = 0; m <= l; ++m, ++i) {
-            for (int k = 0; k <= l - m; ++k) mat[k * IDE_N + i] = (float)sph_harm_coeff(l, m, k);
-        }
-    }
-    if (!ide_tab_equals(mat)) return -1;               // the compile-time table of ide.h must be this libm one, bit for bit
-    done = true;
-    return 0;
-}
-
-template <int N_FREQ>
-__device__ __forceinline__ void pe3(const float* p, float* out) {      // (unrolled: `out` stays in registers)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = p[c];
-    float f = 1.f;
-#pragma unroll
-    for (int k = 0; k < N_FREQ; ++k) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 + 6 * k + c] = sinf(p[c] * f);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 + 6 * k + 3 + c] = cosf(p[c] * f);
-        f *= 2.f;
-    }
-}
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-constexpr float SRGB_EPS = 1.1920928955078125e-07f;
-__device__ __forceinline__ float srgb_f(float x) {
-    return x <= 0.0031308f ? (323.f / 25.f) * x : (211.f * powf(fmaxf(x, SRGB_EPS), 5.f / 12.f) - 11.f) / 200.f;
-}
+// (srgb_grad stays local: shade_math.h says why)
 __device__ __forceinline__ float srgb_grad(float x) {
     if (x <= 0.0031308f) return 323.f / 25.f;
     return x >= SRGB_EPS ? (211.f / 200.f) * (5.f / 12.f) * powf(x, -7.f / 12.f) : 0.f;
@@ -246,23 +199,7 @@ __global__ __launch_bounds__(ROW_BLOCK) void shade_encode_kernel(const float* __
     rows_flush<72>(stage, Xs, ldd, 0, row0, n_pad);
     float pe[51];
     pe3<8>(p, pe);
-    // Xi = [PE-8(p) 51 | IDE(refl, rough) 72 | 0 x 5] as columns 0..63 and 64..127
-    rows_put<64, 0, 51>(stage, pe, z);
-    {
-        float h[13];
-#pragma unroll
-        for (int c = 0; c < 13; ++c) h[c] = e[c];
-        rows_put<64, 51, 13>(stage, h, z);
-    }
-    rows_flush<64>(stage, Xi, 128, 0, row0, n_pad);
-    {
-        float h[59];
-#pragma unroll
-        for (int c = 0; c < 59; ++c) h[c] = e[13 + c];
-        rows_put<64, 0, 59>(stage, h, z);
-    }
-    rows_zero<64, 59, 5>(stage);
-    rows_flush<64>(stage, Xi, 128, 64, row0, n_pad);
+    put_inner_row(stage, pe, e, z, Xi, row0, n_pad);     // Xi = [PE-8(p) 51 | IDE(refl, rough) 72 | 0 x 5]
     // Xo = [PE-8(p) 51 | PE-6(refl) 39 | 0 x 6] as columns 0..47 and 48..95
     float pr[39];
     {
@@ -299,28 +236,8 @@ __global__ __launch_bounds__(ROW_BLOCK) void shade_encode_kernel(const float* __
 // ------------------------------------------------------------------------------------------------------------------
 // human ("photo capturer") light input: intersection of the reflected ray with the z=0 plane of the per-image human
 // frame, IPE of the hit position (predict_human_light / get_camera_plane_intersection / IPE, field.py:348-378, 536-552)
-// Xh [rows,24]; hmask[k] = hit flag (1/0)
+// Xh [rows,24]; hmask[k] = hit flag (1/0).  human_geom: shade_math.h
 // ------------------------------------------------------------------------------------------------------------------
-struct HumanGeom { float px, py, pz, dx, dy, dz, dzp, dist, ix, iy, h; bool hits0; };
-
-__device__ __forceinline__ HumanGeom human_geom(const float* __restrict__ pose, const float* p, const float* rf) {
-    HumanGeom g;
-    g.px = pose[0] * p[0] + pose[1] * p[1] + pose[2] * p[2] + pose[3];
-    g.py = pose[4] * p[0] + pose[5] * p[1] + pose[6] * p[2] + pose[7];
-    g.pz = pose[8] * p[0] + pose[9] * p[1] + pose[10] * p[2] + pose[11];
-    g.dx = pose[0] * rf[0] + pose[1] * rf[1] + pose[2] * rf[2];
-    g.dy = pose[4] * rf[0] + pose[5] * rf[1] + pose[6] * rf[2];
-    g.dz = pose[8] * rf[0] + pose[9] * rf[1] + pose[10] * rf[2];
-    g.hits0 = fabsf(g.dz) > 1e-4f;
-    g.dzp = g.hits0 ? g.dz : 1e-4f;
-    g.dist = -g.pz / g.dzp;
-    g.ix = g.px + g.dist * g.dx;
-    g.iy = g.py + g.dist * g.dy;
-    const float mx = g.ix * 0.3f, my = g.iy * 0.3f;
-    g.h = (g.hits0 && sqrtf(mx * mx + my * my) < 1.5f && g.dist > 0.f) ? 1.f : 0.f;
-    return g;
-}
-
 __global__ void human_encode_kernel(const float* __restrict__ x4, const float* __restrict__ geo, const float* __restrict__ mat,
                                     const int* __restrict__ idx, int T, const float* __restrict__ poses, int n, int n_pad,
                                     float* __restrict__ Xh, float* __restrict__ hmask) {
@@ -342,7 +259,7 @@ __global__ void human_encode_kernel(const float* __restrict__ x4, const float* _
             const float sm = mean[c] * sc, sv = var * sc * sc;
             const float e = expf(-0.5f * sv);
             o[2 * s + c] = e * sinf(sm);
-            o[12 + 2 * s + c] = e * sinf(sm + 1.5707963267948966f);
+            o[12 + 2 * s + c] = e * sinf(sm + HALF_PI);
         }
         sc *= 2.f;
     }
@@ -371,7 +288,7 @@ __global__ __launch_bounds__(128) void human_encode_bwd_kernel(const float* __re
         for (int c = 0; c < 2; ++c) {
             const float sm = mean[c] * sc, sv = var * sc * sc;
             const float e = expf(-0.5f * sv);
-            const float sn = sinf(sm), cs = sinf(sm + 1.5707963267948966f), ms = cosf(sm + 1.5707963267948966f);
+            const float sn = sinf(sm), cs = sinf(sm + HALF_PI), ms = cosf(sm + HALF_PI);
             const float ga = gx[2 * s + c], gb = gx[12 + 2 * s + c];
             dmean[c] += sc * (ga * e * cosf(sm) + gb * e * ms);
             dvar += sc * sc * (-0.5f) * (ga * e * sn + gb * e * cs);
@@ -403,8 +320,8 @@ __global__ void shade_combine_fwd_kernel(const float* __restrict__ geo, const fl
     float hl[3] = {0.f, 0.f, 0.f}, hw = 0.f;
     if (Lh) {
         const float hm = hmask[k];
-        for (int c = 0; c < 3; ++c) hl[c] = expf(fminf(Lh[(size_t)k * 4 + c], 0.f)) * hm;
-        hw = fminf(fmaxf(expf(fminf(Lh[(size_t)k * 4 + 3], 0.f)) * hm, 0.f), 1.f);
+        for (int c = 0; c < 3; ++c) hl[c] = exp_head(Lh[(size_t)k * 4 + c], 0.f) * hm;
+        hw = fminf(fmaxf(exp_head(Lh[(size_t)k * 4 + 3], 0.f) * hm, 0.f), 1.f);
     }
     const float m = mo[0], r = mo[1];
     const float nov = geo[(size_t)k * 8 + 3];
@@ -415,9 +332,9 @@ __global__ void shade_combine_fwd_kernel(const float* __restrict__ geo, const fl
     occ_prob[k] = occ;
     for (int c = 0; c < 3; ++c) {
         const float a = mo[2 + c];
-        const float dl = expf(fminf(Ld[(size_t)k * 4 + c], exp_max));
-        const float direct = expf(fminf(Ls[(size_t)k * 4 + c], exp_max));
-        const float indirect = expf(fminf(Li[(size_t)k * 4 + c], exp_max));
+        const float dl = exp_head(Ld[(size_t)k * 4 + c], exp_max);
+        const float direct = exp_head(Ls[(size_t)k * 4 + c], exp_max);
+        const float indirect = exp_head(Li[(size_t)k * 4 + c], exp_max);
         const float sl = indirect * oc + (hl[c] * hw + direct * (1.f - hw)) * (1.f - oc);
         const float da = (1.f - m) * a, sa = 0.04f * (1.f - m) + m * a;
         const float lin = da * dl + (sa * f0 + f1) * sl;
@@ -443,16 +360,16 @@ __global__ void shade_inter_kernel(const float* __restrict__ geo, const float* _
     float hl[3] = {0.f, 0.f, 0.f}, hw = 0.f;
     if (Lh) {
         const float hm = hmask[k];
-        for (int c = 0; c < 3; ++c) hl[c] = expf(fminf(Lh[(size_t)k * 4 + c], 0.f)) * hm;
-        hw = fminf(fmaxf(expf(fminf(Lh[(size_t)k * 4 + 3], 0.f)) * hm, 0.f), 1.f);
+        for (int c = 0; c < 3; ++c) hl[c] = exp_head(Lh[(size_t)k * 4 + c], 0.f) * hm;
+        hw = fminf(fmaxf(exp_head(Lh[(size_t)k * 4 + 3], 0.f) * hm, 0.f), 1.f);
     }
     const float oc = fminf(fmaxf(Lo[(size_t)k * 4] * 0.5f + 0.5f, 0.f), 1.f);
     float* o = rec + (size_t)k * 32;
     for (int c = 0; c < 3; ++c) {
         const float a = mo[2 + c];
-        const float dl = expf(fminf(Ld[(size_t)k * 4 + c], exp_max));
-        const float direct = expf(fminf(Ls[(size_t)k * 4 + c], exp_max));
-        const float indirect = expf(fminf(Li[(size_t)k * 4 + c], exp_max));
+        const float dl = exp_head(Ld[(size_t)k * 4 + c], exp_max);
+        const float direct = exp_head(Ls[(size_t)k * 4 + c], exp_max);
+        const float indirect = exp_head(Li[(size_t)k * 4 + c], exp_max);
         const float sl = indirect * oc + (hl[c] * hw + direct * (1.f - hw)) * (1.f - oc);
         const float da = (1.f - m) * a, sa = 0.04f * (1.f - m) + m * a;
         const float sref = sa * f0 + f1;
@@ -490,8 +407,8 @@ __global__ void shade_combine_bwd_kernel(const float* __restrict__ geo, const fl
     float hl[3] = {0.f, 0.f, 0.f}, hw = 0.f, hw_raw = 0.f, hm = 0.f;
     if (Lh) {
         hm = hmask[k];
-        for (int c = 0; c < 3; ++c) hl[c] = expf(fminf(Lh[(size_t)k * 4 + c], 0.f)) * hm;
-        hw_raw = expf(fminf(Lh[(size_t)k * 4 + 3], 0.f)) * hm;
+        for (int c = 0; c < 3; ++c) hl[c] = exp_head(Lh[(size_t)k * 4 + c], 0.f) * hm;
+        hw_raw = exp_head(Lh[(size_t)k * 4 + 3], 0.f) * hm;
         hw = fminf(fmaxf(hw_raw, 0.f), 1.f);
     }
     float d_hl[3] = {0.f, 0.f, 0.f}, d_hw = 0.f;
@@ -508,7 +425,7 @@ __global__ void shade_combine_bwd_kernel(const float* __restrict__ geo, const fl
     for (int c = 0; c < 3; ++c) {
         const float a = mo[2 + c];
         const float rd = Ld[(size_t)k * 4 + c], rs = Ls[(size_t)k * 4 + c], ri = Li[(size_t)k * 4 + c];
-        const float dl = expf(fminf(rd, exp_max)), direct = expf(fminf(rs, exp_max)), indirect = expf(fminf(ri, exp_max));
+        const float dl = exp_head(rd, exp_max), direct = exp_head(rs, exp_max), indirect = exp_head(ri, exp_max);
         const float bl = hl[c] * hw + direct * (1.f - hw);
         const float sl = indirect * oc + bl * (1.f - oc);
         const float dalb = (1.f - m) * a, salb = 0.04f * (1.f - m) + m * a;
@@ -522,19 +439,19 @@ __global__ void shade_combine_bwd_kernel(const float* __restrict__ geo, const fl
         d_f1 += d_sref;
         d_m += -a * d_dalb + (a - 0.04f) * d_salb;
         da_out[c] = (1.f - m) * d_dalb + m * d_salb;
-        ld[c] = rd <= exp_max ? d_dl * dl : 0.f;
-        li[c] = ri <= exp_max ? d_sl * oc * indirect : 0.f;
+        ld[c] = exp_head_gate(rd, exp_max) ? d_dl * dl : 0.f;
+        li[c] = exp_head_gate(ri, exp_max) ? d_sl * oc * indirect : 0.f;
         const float d_bl = d_sl * (1.f - oc);
-        ls[c] = rs <= exp_max ? d_bl * (1.f - hw) * direct : 0.f;
+        ls[c] = exp_head_gate(rs, exp_max) ? d_bl * (1.f - hw) * direct : 0.f;
         d_hl[c] = d_bl * hw;
         d_hw += d_bl * (hl[c] - direct);
         d_oc += d_sl * (indirect - bl);
     }
     if (dLh) {
         float o4[4];
-        for (int c = 0; c < 3; ++c) o4[c] = Lh[(size_t)k * 4 + c] <= 0.f ? d_hl[c] * hl[c] : 0.f;        // hl = exp(raw)*hm
+        for (int c = 0; c < 3; ++c) o4[c] = exp_head_gate(Lh[(size_t)k * 4 + c], 0.f) ? d_hl[c] * hl[c] : 0.f;        // hl = exp(raw)*hm
         const float dhw_raw = (hw_raw >= 0.f && hw_raw <= 1.f) ? d_hw : 0.f;
-        o4[3] = Lh[(size_t)k * 4 + 3] <= 0.f ? dhw_raw * hw_raw : 0.f;
+        o4[3] = exp_head_gate(Lh[(size_t)k * 4 + 3], 0.f) ? dhw_raw * hw_raw : 0.f;
         reinterpret_cast<float4*>(dLh)[k] = make_float4(o4[0], o4[1], o4[2], o4[3]);
     }
     float d_occ_tot = (occ >= 0.f && occ <= 1.f) ? d_oc : 0.f;
@@ -625,7 +542,7 @@ __global__ void nerf_head_fwd_kernel(const float* __restrict__ sig4, const float
     const float s = sig4[(size_t)k * 4];
     const float sp = s > 20.f ? s : log1pf(expf(s));
     alpha[k] = 1.0f - expf(-sp * dist[k]);
-    for (int c = 0; c < 3; ++c) color[(size_t)k * 3 + c] = srgb_f(expf(fminf(rgb4[(size_t)k * 4 + c], 5.0f)));
+    for (int c = 0; c < 3; ++c) color[(size_t)k * 3 + c] = srgb_f(exp_head(rgb4[(size_t)k * 4 + c], 5.0f));
 }
 
 __global__ void nerf_head_bwd_kernel(const float* __restrict__ sig4, const float* __restrict__ rgb4, const float* __restrict__ dist,
@@ -642,8 +559,8 @@ __global__ void nerf_head_bwd_kernel(const float* __restrict__ sig4, const float
     float o[3];
     for (int c = 0; c < 3; ++c) {
         const float raw = rgb4[(size_t)k * 4 + c];
-        const float e = expf(fminf(raw, 5.0f));
-        o[c] = raw <= 5.0f ? d_color[(size_t)k * 3 + c] * srgb_grad(e) * e : 0.f;
+        const float e = exp_head(raw, 5.0f);
+        o[c] = exp_head_gate(raw, 5.0f) ? d_color[(size_t)k * 3 + c] * srgb_grad(e) * e : 0.f;
     }
     reinterpret_cast<float4*>(d_rgb4)[k] = make_float4(o[0], o[1], o[2], 0.f);
 }
@@ -809,7 +726,6 @@ __global__ void gather_sample_grads_kernel(const float* __restrict__ d_alphaRT, 
 #define GRID1D(n) dim3(((n) + 127) / 128), dim3(128), 0, (hipStream_t)stream
 // argument contract of every entry point below (include/nero_hip.h): refused before any launch, nothing written
 #define REQUIRE(fn, cond) do { if (!(cond)) return nero_fail(NERO_ERR_ARG, fn ": bad argument (" #cond ")"); } while (0)
-#define CHECK_IDE() do { if (init_ide_tables() != 0) return nero_fail(NERO_ERR_LAUNCH, "IDE coefficient table of ide.h differs from the libm one"); } while (0)
 
 extern "C" {
 
@@ -834,7 +750,7 @@ int nero_sdf_alpha_bwd(const float* sdf4, const float* grad, const float* x4, co
 int nero_shade_encode(const float* x4, const float* geo, const float* m_raw, const float* r_raw, const float* a_raw, int n,
                       float* mat, float* Xd, float* Xs, float* Xi, float* Xo, int sphere_direction, void* stream) {
     REQUIRE("nero_shade_encode", x4 && geo && m_raw && r_raw && a_raw && mat && Xd && Xs && Xi && Xo && n >= 0);
-    CHECK_IDE();
+    NERO_CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(shade_encode_kernel, dim3((n_pad + ROW_BLOCK - 1) / ROW_BLOCK), dim3(ROW_BLOCK), 0, (hipStream_t)stream, x4, geo, m_raw, r_raw, a_raw, n, n_pad, mat, Xd, Xs, Xi, Xo, sphere_direction);
@@ -873,7 +789,7 @@ int nero_shade_encode_bwd(const float* geo, const float* mat, const float* dXd, 
                           int n, float* d_geo, float* dm_raw, float* dr_raw, float* da_raw, const float* extra, const float* x4,
                           int sphere_direction, void* stream) {
     REQUIRE("nero_shade_encode_bwd", geo && mat && dXd && dXs && dXi && dmat && d_geo && dm_raw && dr_raw && da_raw && n >= 0 && (x4 || !sphere_direction));
-    CHECK_IDE();
+    NERO_CHECK_IDE();
     const int n_pad = NERO_ROW_PAD(n);
     if (n_pad == 0) return NERO_OK;
     hipLaunchKernelGGL(shade_encode_bwd_kernel, GRID1D(n_pad), geo, mat, dXd, dXs, dXi, dmat, n, n_pad, d_geo, dm_raw, dr_raw, da_raw, extra, x4,

@@ -20,8 +20,13 @@
 #include <stdint.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
+#include "device_prims.h"                            // block_tree_sum
+#include "shade_math.h"                              // sgn
 
 namespace {
+
+using nero_shade::sgn;
+using nero_prims::block_tree_sum;
 
 constexpr int LB = 256;
 constexpr int SB = 1024;                                 // elements per scan block (LB threads x 4)
@@ -159,7 +164,6 @@ __global__ __launch_bounds__(1024) void occ_l1_kernel(const float* __restrict__ 
         loss[0] = part[0] / (float)kept;
     }
 }
-__device__ __forceinline__ float sgn0(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 // d_occ[cand[k]] = d_loss[0] * sign(occ_prob[cand[k]] - gt[k]) / max(kept, 1) on a d_occ the caller zeroed (candidates are distinct samples)
 __global__ __launch_bounds__(LB) void occ_l1_bwd_kernel(const float* __restrict__ d_loss, const float* __restrict__ occ_prob,
                                                         const int* __restrict__ cand, const int* __restrict__ counts, const float* __restrict__ gt,
@@ -169,22 +173,10 @@ __global__ __launch_bounds__(LB) void occ_l1_bwd_kernel(const float* __restrict_
     const int i = cand[k];
     if (i < 0) return;
     const int kept = counts[0] > 1 ? counts[0] : 1;
-    d_occ[i] = d_loss[0] * sgn0(occ_prob[i] - gt[k]) / (float)kept;
+    d_occ[i] = d_loss[0] * sgn(occ_prob[i] - gt[k]) / (float)kept;
 }
 
 // ---- loss + backward seeds ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-__device__ __forceinline__ float block_sum(float v, float* lds) {                        // LB threads, fixed order; result in every thread
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = LB / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) lds[threadIdx.x] += lds[threadIdx.x + off];
-        __syncthreads();
-    }
-    const float s = lds[0];
-    __syncthreads();
-    return s;
-}
 // thread i: ray i (rgb loss + d_rgb) and inner sample i (eikonal term: d_gerr, zeroed d_occ); partials[2 b] / [2 b + 1] = block sums
 __global__ __launch_bounds__(LB) void loss_rows_kernel(int R, int kind, const float* __restrict__ rgb, const float* __restrict__ gt,
                                                        int n_in, const float* __restrict__ gerr, float eik_w,
@@ -228,7 +220,7 @@ __global__ __launch_bounds__(LB) void loss_rows_kernel(int R, int kind, const fl
         d_gerr[i] = eik_w * (w ? w[0] : 1.f) / (float)n_in;
         if (d_occ) d_occ[i] = 0.f;
     }
-    const float sr = block_sum(lr, lds), sg = block_sum(lg, lds);
+    const float sr = block_tree_sum<LB>(lr, lds), sg = block_tree_sum<LB>(lg, lds);
     if (threadIdx.x == 0) { partials[2 * blockIdx.x] = sr; partials[2 * blockIdx.x + 1] = sg; }
 }
 // ONE block: the sums, the occlusion L1 term over the kept candidates (+ its seeds scattered into d_occ), the weighted total
@@ -240,8 +232,8 @@ __global__ __launch_bounds__(LB) void loss_final_kernel(int R, int n_in, float e
     __shared__ float lds[LB];
     float sr = 0.f, sg = 0.f;
     for (int b = threadIdx.x; b < nb; b += LB) { sr += partials[2 * b]; sg += partials[2 * b + 1]; }
-    sr = block_sum(sr, lds);
-    sg = block_sum(sg, lds);
+    sr = block_tree_sum<LB>(sr, lds);
+    sg = block_tree_sum<LB>(sg, lds);
     const float w_eik = w ? w[0] : 1.f, w_occ = w ? w[1] : 1.f;
     float so = 0.f;
     int kept = 0;
@@ -253,7 +245,7 @@ __global__ __launch_bounds__(LB) void loss_final_kernel(int R, int n_in, float e
             so += fabsf(df);
             d_occ[i] = w_occ * sgn(df) / (float)kept;
         }
-        so = block_sum(so, lds);
+        so = block_tree_sum<LB>(so, lds);
     }
     if (threadIdx.x == 0) {
         const float l_rgb = sr / (float)R;
