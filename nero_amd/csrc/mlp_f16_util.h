@@ -402,6 +402,128 @@ __device__ __forceinline__ void gemm_f16x3_fixed(f32x16 (&aH)[2], const uint4* w
     gemm_f16x3_fixed_hook<N>(aH, wp, xp, half_bytes, plane_bytes, [](auto) {});
 }
 
+// ---- dual-tile k-loop with a compile-time step count and a weight ring the CALLER can prefill (paired kernels, 256-wide layers) ----
+// What gemm_f16x3_dual loses: (1) hipcc forms the address of a ring slot's next request in the registers of that slot's pending
+// request, so three of its six k-steps open with s_waitcnt vmcnt(0) -- the ring is drained before it is refilled and a weight pair is
+// in flight for less than one k-step instead of two; (2) a layer's first requests are issued behind the row stores of the previous
+// layer's epilogue, and vmcnt retires in order: the first k-steps wait until 16 HBM-bound stores are acknowledged.
+// Here the weight requests are inline asm -- the compiler neither counts nor waits for them -- with a uniform base in scalar registers
+// (no per-lane address arithmetic), and every wait is a counted s_waitcnt vmcnt(N) placed by hand:
+//   N = the vector-memory requests issued AFTER the awaited slot's = 4 per later ring request (+ the epilogue's row stores where the
+//   slot was requested ahead of them).  A larger true count only makes the wait conservative; a smaller one would be a race, so every
+//   request of the ring is an asm volatile statement (program order among them is fixed) and the count is written next to each wait.
+// Every destination register stays live from its request to the statement behind its wait that names it (landed_w2q): no request is
+// issued whose result is not consumed (no clamped tail requests), so the compiler can never reuse a register a request is still going
+// to write.  What it MAY do is copy such a register early -- check the ISA after a change here: between a request and its wait no
+// instruction may name the slot's registers (done for this version: none does, in the loop or across the layer boundary).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct WQ2 { u32x4 ah, al, bh, bl; };                 // one k-step's weight planes (h, l) of the wave's tiles a = t and b = t + NW
+constexpr int WQ_STEP_BYTES = 2048, WQ_PLANE_BYTES = 1024;      // load_w: step c at wp + 128 c (uint4), wl 64 uint4 behind wh
+// k-step C of both tiles -> slot o.  voff = 16 * lane, s0 / s1 = the tiles' first fragment (wave-uniform).  (s_nop 4: an SGPR the
+// compiler has just formed -> VMEM address operand inside an asm block, which its hazard recogniser does not see into)
+template <int C, bool ORDER_MEM>
+__device__ __forceinline__ void load_w2q(WQ2& o, unsigned voff, const char* s0, const char* s1) {
+    const char* p0 = s0 + C * WQ_STEP_BYTES;
+    const char* p1 = s1 + C * WQ_STEP_BYTES;
+#define NERO_W2Q_ASM "s_nop 4\n\tglobal_load_dwordx4 %0, %4, %5\n\tglobal_load_dwordx4 %1, %4, %5 offset:1024\n\t" \
+                     "global_load_dwordx4 %2, %4, %6\n\tglobal_load_dwordx4 %3, %4, %6 offset:1024"
+    // ORDER_MEM (the prefill): no store of the epilogue may be moved in front of the requests -- the prefilled waits count them
+    if (ORDER_MEM) asm volatile(NERO_W2Q_ASM : "=&v"(o.ah), "=&v"(o.al), "=&v"(o.bh), "=&v"(o.bl) : "v"(voff), "s"(p0), "s"(p1) : "memory");
+    else asm volatile(NERO_W2Q_ASM : "=&v"(o.ah), "=&v"(o.al), "=&v"(o.bh), "=&v"(o.bl) : "v"(voff), "s"(p0), "s"(p1));
+#undef NERO_W2Q_ASM
+}
+static_assert(WQ_PLANE_BYTES == 1024, "offset:1024 in load_w2q");
+// the wait and, behind it, the point from which the slot may be read.  Two statements on purpose: with the registers named on the wait
+// itself hipcc may copy them IN FRONT of it (seen with one such wait in each arm of a branch) -- a copy of registers whose data has not
+// landed.  The scheduling fence keeps every such copy behind the wait; nothing below `landed_w2q` reads the slot above it.
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N)); }
+__device__ __forceinline__ void landed_w2q(WQ2& w) {
+    NERO_FENCE();
+    asm volatile("" : "+v"(w.ah), "+v"(w.al), "+v"(w.bh), "+v"(w.bl));
+}
+__device__ __forceinline__ void ops_compute2q(f32x16 (&aH0)[2], f32x16 (&aH1)[2], const WQ2& w, const XF& x) {   // = ops_compute2
+    NERO_MFH(aH0[0], w.al, x.xh0); NERO_MFH(aH0[1], w.al, x.xh1);
+    NERO_MFH(aH0[0], w.ah, x.xl0); NERO_MFH(aH0[1], w.ah, x.xl1);
+    NERO_MFH(aH0[0], w.ah, x.xh0); NERO_MFH(aH0[1], w.ah, x.xh1);
+    NERO_MFH(aH1[0], w.bl, x.xh0); NERO_MFH(aH1[1], w.bl, x.xh1);
+    NERO_MFH(aH1[0], w.bh, x.xl0); NERO_MFH(aH1[1], w.bh, x.xl1);
+    NERO_MFH(aH1[0], w.bh, x.xh0); NERO_MFH(aH1[1], w.bh, x.xh1);
+}
+// the caller's prefill: k-steps 0 and 1 of a LATER GEMM into r0 / r1, issued in front of the epilogue's row stores
+__device__ __forceinline__ void prefill_w2q(WQ2& r0, WQ2& r1, unsigned voff, const char* s0, const char* s1) {
+    load_w2q<0, true>(r0, voff, s0, s1);
+    load_w2q<1, true>(r1, voff, s0, s1);
+    NERO_FENCE();
+}
+// r0 / r1 were requested by prefill_w2q; `stores_behind`: at least PRE_STORES vector-memory requests (the row stores of the epilogue
+// in between) were issued behind them.  Same products in the same order as gemm_f16x3_dual: bit-identical.
+constexpr int PRE_STORES = 2 * 2 * (32 / SCRP_ROWS) * (SCRP_ROWS / 8);    // 2 tiles x 2 row halves x acc_to_global16's store_ws4 calls = 16
+template <int N>
+__device__ __forceinline__ void gemm_f16x3_dual_fixed(f32x16 (&aH0)[2], f32x16 (&aH1)[2], unsigned voff, const char* s0, const char* s1,
+                                                      const char* xp, int half_bytes, int plane_bytes, WQ2& r0, WQ2& r1, bool stores_behind) {
+    static_assert(N >= 3, "ring of three");
+    WQ2 r2;
+    XF x[2];
+    load_x(x[0], xp, half_bytes, plane_bytes, 0);
+    NERO_FENCE();
+    static_for<0, N>([&](auto cc) {
+        constexpr int c = cc.value;
+        auto slot = [&](auto k) -> WQ2& { if constexpr (k.value % 3 == 0) return r0; else if constexpr (k.value % 3 == 1) return r1; else return r2; };
+        if constexpr (c + 2 < N) load_w2q<c + 2, false>(slot(IC<c + 2>{}), voff, s0, s1);
+        if constexpr (c + 1 < N) load_x(x[(c + 1) & 1], xp, half_bytes, plane_bytes, c + 1);
+        NERO_FENCE();
+        // requests issued behind slot c's: k-step c + 1's (by the prefill for c = 0, by step c - 1 otherwise) and k-step c + 2's (just
+        // now), four each, where those steps exist; slots 0 and 1 also have the epilogue's PRE_STORES row stores behind them, which
+        // therefore stay in flight under these MFMAs
+        constexpr int later = 4 * ((c + 1 < N ? 1 : 0) + (c + 2 < N ? 1 : 0));
+        if (c < 2 && stores_behind) wait_vm<later + PRE_STORES>();
+        else wait_vm<later>();
+        landed_w2q(slot(cc));
+        ops_compute2q(aH0, aH1, slot(cc), x[c & 1]);
+        NERO_FENCE();
+    });
+}
+
+// the single-tile k-loop on the same terms (the reverse walk of the paired kernels: one feature tile at a time): weights three steps
+// ahead in a ring of four asm-requested slots, two requests per k-step, counted waits.  gemm_f16x3's compiler-managed ring is drained
+// by a vmcnt(0) at the head of every fourth k-step (the same address-in-destination pattern as the dual loop).  Same products in the
+// same order as gemm_f16x3 / ops_compute: bit-identical.
+struct WQ1 { u32x4 h, l; };
+template <int C> __device__ __forceinline__ void load_w1q(WQ1& o, unsigned voff, const char* s) {
+    const char* p = s + C * WQ_STEP_BYTES;
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024"
+                 : "=&v"(o.h), "=&v"(o.l) : "v"(voff), "s"(p));
+}
+__device__ __forceinline__ void landed_w1q(WQ1& w) {
+    NERO_FENCE();
+    asm volatile("" : "+v"(w.h), "+v"(w.l));
+}
+template <int N>
+__device__ __forceinline__ void gemm_f16x3_single_fixed(f32x16 (&aH)[2], unsigned voff, const char* s, const char* xp, int half_bytes,
+                                                        int plane_bytes) {
+    constexpr int WD = 3, WN = WD + 1;
+    static_assert(N > WD, "ring of four");
+    WQ1 w[WN];
+    XF x[2];
+    static_for<0, WD>([&](auto cc) { load_w1q<cc.value>(w[cc.value], voff, s); });
+    load_x(x[0], xp, half_bytes, plane_bytes, 0);
+    NERO_FENCE();
+    static_for<0, N>([&](auto cc) {
+        constexpr int c = cc.value;
+        if constexpr (c + WD < N) load_w1q<c + WD>(w[(c + WD) % WN], voff, s);
+        if constexpr (c + 1 < N) load_x(x[(c + 1) & 1], xp, half_bytes, plane_bytes, c + 1);
+        NERO_FENCE();
+        // requests issued behind k-step c's: those of k-steps c + 1, c + 2, c + 3 where they exist, two each
+        constexpr int later = 2 * ((c + 1 < N ? 1 : 0) + (c + 2 < N ? 1 : 0) + (c + 3 < N ? 1 : 0));
+        wait_vm<later>();
+        landed_w1q(w[c % WN]);
+        NERO_MFH(aH[0], w[c % WN].l, x[c & 1].xh0); NERO_MFH(aH[1], w[c % WN].l, x[c & 1].xh1);
+        NERO_MFH(aH[0], w[c % WN].h, x[c & 1].xl0); NERO_MFH(aH[1], w[c % WN].h, x[c & 1].xl1);
+        NERO_MFH(aH[0], w[c % WN].h, x[c & 1].xh0); NERO_MFH(aH[1], w[c % WN].h, x[c & 1].xh1);
+        NERO_FENCE();
+    });
+}
+
 __device__ __forceinline__ void zero2(f32x16 (&acc)[2]) {
 #pragma unroll
     for (int r = 0; r < 2; ++r)

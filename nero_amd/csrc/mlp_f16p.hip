@@ -12,6 +12,10 @@
 // Measured and dropped here: the next tile's / next layer's first weight fragments requested behind the running GEMM (prefetch_layer of
 // the 512-thread forward kernel): 242 instead of 224 VGPRs, forward class 6.82 -> 6.90 ms in 4 of 4 interleaved runs -- the sibling
 // workgroup already covers that L2 round trip.
+// What did pay (docs/experiments.md 16, profiles/paired_store_drain_ab.txt): weight rings whose requests are inline asm and whose waits
+// are counted by hand (mlp_f16_util.h: gemm_f16x3_dual_fixed, gemm_f16x3_single_fixed) -- the compiler-managed rings were drained by a
+// vmcnt(0) three k-steps out of six -- in the runs of plain 256-wide layers of the forward kernel (fwd_plain_run, the next layer's first
+// two k-steps requested in front of the row stores) and in the mask-only reverse kernel: step 27.07 -> 26.66 ms, 4 of 4 pairs.
 //
 // Why: the 512-thread kernels of mlp_f16x3.hip hold one workgroup per CU, whose 8 waves walk the phases of a layer in lock step
 // (GEMM -> activation / saves -> row-maximum exchange -> plane conversion, two barriers), so the matrix pipe idles through every
@@ -298,6 +302,19 @@ __device__ __forceinline__ Ctx make_ctx(char* smem, int n_rows) {
     return c;
 }
 
+// the same context with the lane index opaque to the compiler: per-lane addresses and offsets formed from it are recomputed where they
+// are used (a few VALU instructions per layer) instead of being hoisted out of the layer loop, where several dozen of them would occupy
+// registers -- or scratch -- through every GEMM (P_LOCAL_V)
+__device__ __forceinline__ Ctx relane(const Ctx& c) {
+    Ctx r = c;
+    int lane = c.lane;
+    P_LOCAL_V(lane);
+    r.lane = lane;
+    r.i = lane & 31;
+    r.h = lane >> 5;
+    return r;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // forward chain
 // ---------------------------------------------------------------------------------------------------------------------
@@ -308,13 +325,15 @@ __device__ __forceinline__ void fwd_load_bias(float4 (&bq)[4], const nero_fwd_la
         bq[g] = L.bias ? *reinterpret_cast<const float4*>(L.bias + 32 * t + 8 * g + 4 * c.h) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// epilogue of one feature tile: bias + activation -> val, row-major save, ReLU sign words, row maxima
-__device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
-                                             const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4], float (&m)[2] PH_PARAM) {
-    if (L.act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, bq, U, val, m);
-    else if (L.act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, bq, U, val, m);
+// epilogue of one feature tile, first half: bias + activation -> val, row maxima of the tile -> m
+__device__ __forceinline__ void fwd_act_values(int act, const f32x16 (&aH)[2], const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4],
+                                               float (&m)[2]) {
+    if (act == NERO_ACT_RELU) fwd_values<NERO_ACT_RELU>(aH, bq, U, val, m);
+    else if (act == NERO_ACT_SOFTPLUS100) fwd_values<NERO_ACT_SOFTPLUS100>(aH, bq, U, val, m);
     else fwd_values<NERO_ACT_NONE>(aH, bq, U, val, m);
-    PH(3);
+}
+// second half: row-major save, ReLU sign words, row maxima published
+__device__ __forceinline__ void fwd_outputs(const nero_fwd_layer& L, const Ctx& c, int t, const float4 (&val)[2][4], const float (&m)[2]) {
     if (L.save) {
         float* sblock = L.save + (size_t)c.row0 * NERO_HID + 32 * t;
         acc_to_global16(c.scr, val[0], sblock, c.lane);
@@ -336,6 +355,12 @@ __device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx&
         }
     }
     publish_rowmax(c.S.rmax, m[0], m[1], t, c.i, c.h);
+}
+__device__ __forceinline__ void fwd_epilogue(const nero_fwd_layer& L, const Ctx& c, int t, const f32x16 (&aH)[2],
+                                             const float4 (&bq)[4], const float (&U)[2], float4 (&val)[2][4], float (&m)[2] PH_PARAM) {
+    fwd_act_values(L.act, aH, bq, U, val, m);
+    PH(3);
+    fwd_outputs(L, c, t, val, m);
     PH(4);
 }
 
@@ -353,6 +378,12 @@ __device__ __forceinline__ void fwd_tile(const nero_fwd_chain& ch, const nero_fw
         PH(2);
         fwd_epilogue(L, c, t, aH, bq, U, val, m PH_ARG);
     } else {
+        // (never read -- commit_planes_p skips a tile that does not exist -- but DEFINED: left unset, the 32 registers become a value the
+        //  compiler carries around the layer loop, through every GEMM)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) val[r][g] = make_float4(0.f, 0.f, 0.f, 0.f);
         publish_rowmax(c.S.rmax, 0.f, 0.f, t, c.i, c.h);
         PH(4);
     }
@@ -378,9 +409,74 @@ __device__ __forceinline__ void fwd_tile_pair(const nero_fwd_chain& ch, const ne
     fwd_epilogue(L, c, t + NW, aH1, bq1, U, v1, m1 PH_ARG);
 }
 
+// ---- runs of plain 256-wide layers: the weight ring carried from layer to layer ----------------------------------------------------
+// A "plain" layer for a wave: 256 resident columns, no aux operand, no head, and the wave owns a tile PAIR (the hidden layers of every
+// network of the step).  Consecutive plain layers are walked by fwd_plain_run, whose GEMM (gemm_f16x3_dual_fixed) starts from a ring the
+// previous layer filled in front of its row stores; every other layer takes the general body of fwd_p_kernel unchanged.  The decision is
+// per wave (wave 3 of the 217-wide SDF layer has no second tile) -- both bodies pass the same two barriers per layer.
+__device__ __forceinline__ bool fwd_plain_layer(const nero_fwd_chain& ch, int l, int wave) {
+    return l < ch.n_layers && ch.layer[l].k_main == NERO_HID && ch.layer[l].k_aux == 0 && ch.layer[l].n_head == 0 &&
+           wave + NW < ch.layer[l].n_tiles;
+}
+// first weight fragment of feature tile t of a 16-step image (wave-uniform; the lane's own 16 bytes are at + 16 * lane)
+__device__ __forceinline__ const char* w16_tile(const float* w, int t) {
+    return reinterpret_cast<const char*>(w) + HDR_BYTES + (size_t)t * (NERO_HID / 16) * WQ_STEP_BYTES;
+}
+// layers l, l + 1, ... while they are plain; returns the first layer that is not.  Per layer: GEMM from the filled ring -> values of
+// BOTH tiles (every load the compiler counts is waited for here) -> the next layer's k-steps 0 and 1 requested -> row stores, sign words
+// -> commit.  From the prefill to the next layer's third k-step nothing of this wave waits for the stores.
+__device__ __forceinline__ int fwd_plain_run(const nero_fwd_chain& ch, int l, const Ctx& c0 PH_PARAM) {
+    const Ctx c = relane(c0);
+    const int t = c.wave;
+    const unsigned voff = 16u * c.lane;
+    WQ2 r0, r1;
+    {
+        const float* w = ch.layer[l].w_main;
+        PIN_P(w);
+        prefill_w2q(r0, r1, voff, w16_tile(w, t), w16_tile(w, t + NW));
+    }
+    bool stores_behind = false;
+    for (;;) {
+        const nero_fwd_layer L = load_layer(ch, l);
+        const Ctx c = relane(c0);
+        f32x16 aH0[2], aH1[2];
+        zero2(aH0);
+        zero2(aH1);
+        float4 bq[4];
+        fwd_load_bias(bq, L, c, t);
+        const float wsc = c.S.wsc[2 * l];
+        const float U[2] = {wsc * c.S.rs_main[c.i], wsc * c.S.rs_main[32 + c.i]};
+        PH(1);
+        gemm_f16x3_dual_fixed<NERO_HID / 16>(aH0, aH1, voff, w16_tile(L.w_main, t), w16_tile(L.w_main, t + NW),
+                                             c.S.actp + c.i * SA + 16 * c.h, 32 * SA, PLANE_A, r0, r1, stores_behind);
+        float4 bq1[4];                                 // (behind the GEMM: 16 registers it has no room for)
+        fwd_load_bias(bq1, L, c, t + NW);
+        PH(2);
+        float4 v0[2][4], v1[2][4];
+        float m0[2], m1[2];
+        fwd_act_values(L.act, aH0, bq, U, v0, m0);
+        fwd_act_values(L.act, aH1, bq1, U, v1, m1);
+        PH(3);
+        const bool more = fwd_plain_layer(ch, l + 1, c.wave);
+        if (more) {
+            const float* w = ch.layer[l + 1].w_main;
+            PIN_P(w);
+            prefill_w2q(r0, r1, voff, w16_tile(w, t), w16_tile(w, t + NW));
+        }
+        stores_behind = L.save != nullptr;             // fwd_outputs: 2 tiles x 2 halves x 4 row stores = PRE_STORES (acc_to_global16)
+        fwd_outputs(L, c, t, v0, m0);
+        fwd_outputs(L, c, t + NW, v1, m1);
+        PH(4);
+        commit_planes_p(c, v0, v1, true, true);
+        PH(5);
+        ++l;
+        if (!more) return l;
+    }
+}
+
 __global__ __launch_bounds__(NW * 64, 2) void fwd_p_kernel(nero_fwd_chain ch, int n_rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const Ctx c = make_ctx(smem, n_rows);
+    const Ctx c0 = make_ctx(smem, n_rows), c = c0;
     const int tid = threadIdx.x;
     PH_DECL;
 #ifdef F16_PHASE_TIMING
@@ -393,17 +489,24 @@ __global__ __launch_bounds__(NW * 64, 2) void fwd_p_kernel(nero_fwd_chain ch, in
     wsc_commit(c.S.wsc, wr, tid);
     __syncthreads();
     PH(0);
-    for (int l = 0; l < ch.n_layers; ++l) {
+    for (int l = 0; l < ch.n_layers;) {
+        if (fwd_plain_layer(ch, l, c0.wave)) {
+            l = fwd_plain_run(ch, l, c0 PH_ARG);
+            PIN_S(l);                                  // (opaque: keeps the run a loop of its own, its ring out of the general body)
+            continue;
+        }
         const nero_fwd_layer L = load_layer(ch, l);
+        const Ctx c = relane(c0);
+        ++l;
         if (L.n_head > 0) eval_head_p(c.S.actp, c.S.rs_main, L.head_w, L.head_b, L.head_out, L.n_head, L.head_k, c.row0, tid);
         if (L.n_tiles == 0) continue;
         float4 v0[2][4], v1[2][4];
         float m0[2], m1[2];
         // (wave-uniform: no second tile for n_tiles <= 4 -- the 128-wide layers -- and for wave 3 of the 217-wide SDF layer)
-        if (c.wave + NW < L.n_tiles) fwd_tile_pair(ch, L, l, c, c.wave, v0, v1, m0, m1 PH_ARG);
+        if (c.wave + NW < L.n_tiles) fwd_tile_pair(ch, L, l - 1, c, c.wave, v0, v1, m0, m1 PH_ARG);
         else {
-            fwd_tile(ch, L, l, c, c.wave, v0, m0 PH_ARG);
-            fwd_tile(ch, L, l, c, c.wave + NW, v1, m1 PH_ARG);
+            fwd_tile(ch, L, l - 1, c, c.wave, v0, m0 PH_ARG);
+            fwd_tile(ch, L, l - 1, c, c.wave + NW, v1, m1 PH_ARG);
         }
         commit_planes_p(c, v0, v1, c.wave < L.n_tiles, c.wave + NW < L.n_tiles);
         PH(5);
@@ -528,6 +631,16 @@ __device__ __forceinline__ void combine_acc(float4 (&gq)[2][4], const f32x16 (&a
                                    aH[r][4 * g + 2] * u[r], aH[r][4 * g + 3] * u[r]);
 }
 
+// the GEMM of one feature tile of a reverse layer.  16 k-steps (every 256-wide layer: chain.py pads the reverse contraction to 256) in
+// the mask-only kernel: the loop with the asm-requested ring and counted waits (mlp_f16_util.h); the generic kernel (252 registers) and
+// every other step count keep gemm_f16x3
+template <bool MASKS>
+__device__ __forceinline__ void bwd_gemm(f32x16 (&aH)[2], const float* w_t, int t, int steps, const char* xp, int lane) {
+    if (MASKS && steps == NERO_HID / 16) gemm_f16x3_single_fixed<NERO_HID / 16>(aH, 16u * lane, w16_tile(w_t, t), xp, 32 * SA, PLANE_A);
+    else gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(w_t) + HDR_BYTES) + (size_t)t * steps * 128 + lane, xp,
+                    32 * SA, PLANE_A, steps);
+}
+
 // one feature tile of one reverse layer; `first` = the chain's first dense layer (its input gradient goes to d_init / d_aux)
 // MASKS (round 6): a chain whose reverse pass needs NO saved activation and NO injection -- every act_prev is ReLU with sign words
 // (nero_bwd_layer.mask_prev) or the identity: the material / light predictors and the NeRF++ networks.  Compiled without the softplus path the
@@ -572,8 +685,7 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
         if (ch.d_aux && L.w_aux_t && t < L.k_aux_tiles) {
             zero2(aH);
             const float wsc = c.S.wsc[2 * l + 1];
-            gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_aux_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
-                       xp, 32 * SA, PLANE_A, steps);
+            bwd_gemm<MASKS>(aH, L.w_aux_t, t, steps, xp, c.lane);
             const float u[2] = {wsc * rs0, wsc * rs1};
             combine_acc(gq, aH, u);
             int li = c.i, lf = fbase;
@@ -592,8 +704,7 @@ __device__ __forceinline__ void bwd_tile(const nero_bwd_chain& ch, const nero_bw
         NERO_FENCE();
         zero2(aH);
         const float wsc = c.S.wsc[2 * l];
-        gemm_f16x3(aH, reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(L.w_main_t) + HDR_BYTES) + (size_t)t * steps * 128 + c.lane,
-                   xp, 32 * SA, PLANE_A, steps);
+        bwd_gemm<MASKS>(aH, L.w_main_t, t, steps, xp, c.lane);
         const float u[2] = {wsc * rs0, wsc * rs1};
         combine_acc(gq, aH, u);
         if (first) {
