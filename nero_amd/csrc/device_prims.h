@@ -8,6 +8,14 @@ namespace nero_prims {
 
 __device__ __forceinline__ bool in_range(int a, int n) { return (unsigned)a < (unsigned)n; }
 
+// the counter hash of include/nero_hip_visibility.h (the AO rotations, the surface sampler's variates): a bijection of the 32-bit integers
+__device__ __forceinline__ unsigned lowbias32(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
 // order-preserving image of a float in the unsigned integers (-0 orders below +0)
 __device__ __forceinline__ unsigned f2o(float f) {
     const unsigned b = __float_as_uint(f);

@@ -11,11 +11,13 @@
 #include "bvh_types.h"
 #include "bvh_walk.h"
 #include "common.h"
+#include "device_prims.h"
 #include "visibility_plan.h"
 
 namespace {
 
 using namespace nero_bvh;
+using nero_prims::lowbias32;
 using namespace nero_vis;               // samples_ok, total_ok, log2_of, grid_blocks (visibility_plan.h)
 constexpr float MISS_DEPTH = 10.0f;        // the tracer's miss distance: no query looks further
 constexpr int PRIV_THREADS = 256;          // workgroup of the private-stack kernels (as trace_kernel)
@@ -56,13 +58,6 @@ __global__ __launch_bounds__(OVERLAP ? PL_THREADS : PRIV_THREADS) void occluded_
 }
 
 // ---- the AO sample set --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned lowbias32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352du;
-    x ^= x >> 15; x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // Ray s of S of the point p with unit normal n and hash key `key`: origin o = p + bias n, direction d cosine-distributed around n.
 // Integer-exact up to the square roots and the sine / cosine: (s + 0.5) / S and bitreverse(s) 2^-32 are exact in fp32 for S <= 1024, the
 // two rotations r1, r2 are 24-bit fractions, and each of a, b is ONE fp32 add and one x - floorf(x).  Every product and sum below is

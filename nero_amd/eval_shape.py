@@ -97,6 +97,16 @@ def eval_point_clouds(pts_pr, pts_gt):
     return float(chamfer(pts_pr, pts_gt)[0])
 
 
+def eval_meshes(pr_mesh, gt_mesh, n=500000, seed=0, stratified=True):
+    """the real-shape procedure from two MESHES, each a (vertices, triangles) pair: eval.md samples 500k points on the surface of the
+    predicted and of the ground-truth mesh alike (there with CloudCompare, here with nero_amd.surface.sample_surface: area-weighted,
+    deterministic in n and seed) before eval_real_shape.py takes the Chamfer distance of the two point sets"""
+    from .surface import sample_surface
+    dev = _device(*pr_mesh, *gt_mesh)
+    cloud = lambda m: sample_surface(_points(m[0], dev), m[1], n, seed=seed, stratified=stratified)      # (device tensors: nothing comes back)
+    return eval_point_clouds(cloud(pr_mesh), cloud(gt_mesh))
+
+
 # ---- voxel down-sampling -------------------------------------------------------------------------------------------------------------------
 def voxel_down_sample(points, voxel_size, capacity=None):
     """one point per occupied voxel: the mean of the voxel's points (float64 sum in input order), voxels in ascending (ix, iy, iz) order with

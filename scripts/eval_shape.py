@@ -2,6 +2,9 @@
 
     python scripts/eval_shape.py --pr A.ply --gt B.ply
         eval_real_shape.py: nearest distances between the vertices (or points) of two PLY files.
+    python scripts/eval_shape.py --pr A.ply --gt B.ply --samples 500000 [--seed S] [--iid]
+        eval.md's full recipe for two MESHES: N points sampled on each surface on the GPU (nero_amd/surface.py, what eval.md gives to
+        CloudCompare), then the same distances.  A PLY without faces is used as it is.
     python scripts/eval_shape.py --mesh M.ply --views views.npz (--gt-points P.ply | --gt-depths D.npz)
         eval_synthetic_shape.py: the mesh's depth map in every view of views.npz (poses [n,3,4] world -> camera, Ks [n,3,3], hw [n,2]),
         back-projected and voxel-down-sampled, against the ground-truth points (the data set's eval_pts.ply) or the points made the same way
@@ -22,6 +25,11 @@ def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--pr', type=str, help='predicted mesh or point cloud (PLY)')
     ap.add_argument('--gt', type=str, help='ground-truth mesh or point cloud (PLY)')
+    ap.add_argument('--samples', type=int, default=None, metavar='N',
+                    help='--pr/--gt: sample N points on the surface of every PLY that has faces (eval.md: 500000) instead of taking its '
+                         'vertices; a PLY without faces is used as it is')
+    ap.add_argument('--seed', type=int, default=0, help='--samples: seed of the sampler')
+    ap.add_argument('--iid', action='store_true', help='--samples: independent draws instead of stratified ones')
     ap.add_argument('--mesh', type=str, help='extracted mesh (PLY) for the synthetic procedure')
     ap.add_argument('--views', type=str, help='npz with poses [n,3,4], Ks [n,3,3], hw [n,2]')
     ap.add_argument('--gt-points', type=str, help='ground-truth eval points (PLY)')
@@ -38,12 +46,33 @@ def parse(argv=None):
         ap.error('choose one procedure: --pr A.ply --gt B.ply, or --mesh M.ply --views views.npz with a ground truth')
     if real and (a.pr is None or a.gt is None):
         ap.error('the real-shape procedure needs both --pr and --gt')
+    if a.samples is not None and (syn or a.samples < 1):
+        ap.error('--samples N (N >= 1) belongs to the real-shape procedure, --pr A.ply --gt B.ply')
     if syn:
         if a.mesh is None or a.views is None:
             ap.error('the synthetic procedure needs both --mesh and --views')
         if (a.gt_points is None) == (a.gt_depths is None):
             ap.error('the synthetic procedure needs one ground truth: --gt-points P.ply or --gt-depths D.npz')
     return a
+
+
+def has_faces(path):
+    """whether the PLY file's header declares a non-empty face element"""
+    from nero_amd import mesh as M
+    with open(path, 'rb') as fh:
+        return any(el['name'] == 'face' and el['count'] > 0 for el in M._read_header(fh)[1])
+
+
+def _cloud(path, a):
+    """the point set of one side of --pr/--gt: the file's vertices (or points), or with --samples N points sampled on its surface when it
+    has faces (eval.md: 'sample points on the surface', on both meshes alike)"""
+    from nero_amd import eval_shape as E
+    if a.samples is None or not has_faces(path):
+        return E.read_ply_points(path)
+    from nero_amd import mesh as M
+    from nero_amd.surface import sample_surface
+    v, f = M.read_ply(path)
+    return sample_surface(v, f, a.samples, seed=a.seed, stratified=not a.iid)
 
 
 def main(argv=None):
@@ -55,7 +84,7 @@ def main(argv=None):
     from nero_amd import mesh as M
     if a.pr is not None:
         stem = Path(a.pr).stem
-        chamfer = E.eval_point_clouds(E.read_ply_points(a.pr), E.read_ply_points(a.gt))
+        chamfer = E.eval_point_clouds(_cloud(a.pr, a), _cloud(a.gt, a))
     else:
         stem = Path(a.mesh).stem
         v, f = M.read_ply(a.mesh)
