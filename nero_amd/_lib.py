@@ -1,5 +1,5 @@
-"""ctypes binding of libnero_hip.so (include/nero_hip.h, include/nero_hip_visibility.h).  The library is REQUIRED: there is no PyTorch/CPU fallback for
-the product path -- if it is missing or fails to load, importing this module raises."""
+"""ctypes binding of libnero_hip.so: every public header under include/ (HEADER_PATHS) is bound here and nowhere else.  The library is
+REQUIRED: there is no PyTorch/CPU fallback for the product path -- if it is missing or fails to load, importing this module raises."""
 import ctypes as C
 import os
 import re
@@ -9,8 +9,9 @@ import torch  # noqa: F401  -- must come first: libnero_hip.so has to bind to th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERO_HIP_LIB') or os.path.join(_HERE, 'libnero_hip.so')     # (override: kernel-variant experiments)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip.h')
-# every public header of the library, the first one first; an entry point is declared in exactly one of them
-HEADER_PATHS = (HEADER_PATH, os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip_visibility.h'))
+# every public header of the library, in the order the build lists them; an entry point is declared in exactly one of them
+HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h)
+                     for h in ('nero_hip.h', 'nero_hip_visibility.h', 'nero_hip_relight.h', 'nero_hip_surface.h'))
 
 MAX_LAYERS = 10
 HID = 256

@@ -1,15 +1,21 @@
-// chain_host.h -- host-side machinery shared by the C-level step drivers (stage1_driver.hip, stage2_driver.hip): the workspace arena
-// and the C++ twin of nero_amd/chain.py::Chain (one network as a list of dense / head entries: operand packing, forward, reverse and
-// weight-gradient launches through the library's own entry points).  Include once per translation unit.
+// chain_host.h -- host-side machinery shared by the C-level step drivers (stage1_driver.hip, stage2_driver.hip): the workspace arena,
+// the C++ twin of nero_amd/chain.py::Chain (one network as a list of dense / head entries: operand packing, forward, reverse and
+// weight-gradient launches through the library's own entry points), the packing of a handle's chains and its private side stream.
+// Plain C++ over the HIP host API: no device code, so tests/chain_host_main.cpp builds the planner with the host compiler (the four small
+// kernels the drivers launch themselves are in chain_kernels.h, which the drivers include).  Include once per translation unit.
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <new>
 #include <vector>
 #include "../../include/nero_hip.h"
-#include "common.h"
+
+// (common.h's host declarations, restated: common.h carries device code)
+int nero_fail(int code, const char* msg);
+int nero_check_launch(const char* what);
+bool nero_prof_is_on();
 
 namespace {
 
@@ -28,6 +34,8 @@ struct Arena {
     size_t cap = 0, off = 0, peak = 0;
     bool dry = false;                                  // size query: no memory behind it, nothing is launched
     bool failed = false;
+    Arena() = default;
+    Arena(void* ws, size_t ws_bytes) : base(static_cast<char*>(ws)), cap(ws_bytes) {}       // over a caller's workspace
     void* take(size_t bytes) {
         const size_t a = (off + 255) & ~(size_t)255;
         off = a + bytes;
@@ -41,40 +49,6 @@ struct Arena {
     size_t mark() const { return off; }
     void release(size_t m) { off = m; }
 };
-
-__global__ void x8_from_x4_kernel(const float* __restrict__ x4, float* __restrict__ x8, int n, int n_pad) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_pad) return;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < n) { v = reinterpret_cast<const float4*>(x4)[r]; v.w = 0.f; }      // (rows_pad rows, as x8[:, :3] = x4[:, :3] over the padded buffer)
-    else { v = reinterpret_cast<const float4*>(x4)[r]; v.w = 0.f; }
-    reinterpret_cast<float4*>(x8)[2 * r] = v;
-    reinterpret_cast<float4*>(x8)[2 * r + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-__global__ void ones_col0_kernel(float* __restrict__ b, int n_pad) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n_pad) reinterpret_cast<float4*>(b)[r] = make_float4(1.f, 0.f, 0.f, 0.f);
-}
-// dst[r*ldd + c] = src[r*lds + c]
-__global__ void copy2d_kernel(const float* __restrict__ src, int lds, float* __restrict__ dst, int ldd, int rows, int cols) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * cols) return;
-    const int r = idx / cols, c = idx - r * cols;
-    dst[(size_t)r * ldd + c] = src[(size_t)r * lds + c];
-}
-// out[b] = sum of block b's grid-stride share of v[0..n) (deterministic two-stage reduction: 128 partials, then one block over them)
-__global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-    __shared__ float part[256];
-    float s = 0.f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) s += v[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = part[0];
-}
 
 #define RC(expr) do { const int rc_ = (expr); if (rc_ != NERO_OK) return rc_; } while (0)
 #define LAUNCH(...) do { if (!A.dry) { RC(__VA_ARGS__); } } while (0)
@@ -346,6 +320,89 @@ void predictor_grads(Chain& c, const nero_linear_grad* g, int k0) {
     set_dense_grad(c.e[1], g[1], 256);
     set_dense_grad(c.e[2], g[2], 256);
     set_head_grad(c.e[3], g[3], 256);
+}
+
+// ---- the packed operand images of all chains of a handle: one buffer, every chain at a 64-float boundary -----------------------------------
+size_t pack_floats_total(const std::vector<Chain*>& chains) {
+    size_t t = 0;
+    for (const Chain* c : chains) t += (c->pack_floats() + 63) / 64 * 64;
+    return t;
+}
+// carve every chain's images from `buf` and collect the pack jobs (no launch)
+void carve_chains(const std::vector<Chain*>& chains, float* buf, std::vector<nero_pack_job>& jobs) {
+    for (Chain* c : chains) {
+        float* q = buf;
+        c->pack(q, jobs);
+        buf += (c->pack_floats() + 63) / 64 * 64;
+    }
+}
+// zero-fill `pack_buf` (pack_floats_total floats), carve it and run the pack jobs, NERO_MAX_PACK_JOBS per launch
+int pack_chains(const std::vector<Chain*>& chains, void* pack_buf, void* stream) {
+    (void)hipMemsetAsync(pack_buf, 0, pack_floats_total(chains) * 4, (hipStream_t)stream);
+    std::vector<nero_pack_job> jobs;
+    carve_chains(chains, static_cast<float*>(pack_buf), jobs);
+    for (size_t i0 = 0; i0 < jobs.size(); i0 += NERO_MAX_PACK_JOBS) {
+        const int n = (int)(jobs.size() - i0 < NERO_MAX_PACK_JOBS ? jobs.size() - i0 : NERO_MAX_PACK_JOBS);
+        RC(nero_pack_batch(jobs.data() + i0, n, stream));
+    }
+    return NERO_OK;
+}
+
+// ---- a private stream of a handle for a branch that runs beside the caller's stream, with the events of its fork and its join --------------
+struct SideStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // false, and no stream: no device in reach (the size queries still work) or out of handles -- the handle keeps to the caller's one stream
+    bool create() {
+        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) == hipSuccess)
+            return true;
+        (void)hipGetLastError();
+        destroy();
+        return false;
+    }
+    void destroy() {
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr; ev_fork = ev_join = nullptr;
+    }
+    // the stream of the side branch: this one behind everything `main` holds so far -- or `main` itself (not enabled: dry runs and one-stream
+    // mode; no stream; launches are being timed)
+    hipStream_t fork(hipStream_t main, bool enabled) {
+        if (!enabled || !stream || nero_prof_is_on()) return main;
+        (void)hipEventRecord(ev_fork, main);
+        (void)hipStreamWaitEvent(stream, ev_fork, 0);
+        return stream;
+    }
+    // `main` continues behind everything `side` (what fork returned) holds
+    void join(hipStream_t side, hipStream_t main) {
+        if (side == main) return;
+        (void)hipEventRecord(ev_join, side);
+        (void)hipStreamWaitEvent(main, ev_join, 0);
+    }
+    void drain() { if (stream) (void)hipStreamSynchronize(stream); }
+};
+
+// ---- over a step handle H with `int device`, `bool owns_streams() const` and `void drain_streams()` ------------------------------------------
+// the device a handle's private streams are created on: the current one, -1 without a device in reach
+int current_device() {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); }
+    return dev;
+}
+// the private streams belong to the device that was current at create time: a call under another current device would fork onto it
+template <class H> bool wrong_device(const H* h) {
+    int dev = -1;
+    return h->owns_streams() && hipGetDevice(&dev) == hipSuccess && h->device >= 0 && dev != h->device;
+}
+// A call that fails between a fork and its join would leave work queued on the private streams with nothing ordering it in front of
+// whatever the caller does next with the workspace: every failing exit of the entry points drains them (host-blocking, error path only).
+template <class H> int drain_on_error(H* h, int rc) {
+    if (rc == NERO_OK) return rc;
+    h->drain_streams();
+    (void)hipGetLastError();
+    return rc;
 }
 
 }  // namespace

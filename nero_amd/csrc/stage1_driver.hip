@@ -9,7 +9,7 @@
 // forward keeps its state there for the backward; nero_stage1_get_state exposes the pieces the loss needs (occlusion-loss march,
 // validation extras).  The only host synchronisation is the read-back of the inner / outer sample counts after render_prep
 // (they size every later launch), as in the Python driver.
-#include "chain_host.h"
+#include "chain_kernels.h"
 #include <stdlib.h>
 #ifndef NERO_STREAMS_DEFAULT
 #define NERO_STREAMS_DEFAULT 3
@@ -44,8 +44,7 @@ struct nero_stage1 {
     // work.  NERO_STREAMS=1 restores the single-stream order (also used while launches are timed: nero_prof_enable).
     int n_streams = 1;
     int device = -1;                                   // the device the private streams / events were created on (nero_stage1_create)
-    hipStream_t s2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    SideStream s2;
     // ---- a third stream for the weight-gradient jobs of the SDF / shading branch (round 5, NERO_STREAMS=3): the jobs of a chain depend on
     // that chain's reverse pass only and nothing in the step depends on them, so they run BESIDE the next chain's reverse pass.  The two
     // kernel classes are bound by different things -- the weight-gradient GEMM streams its operands from HBM (4.9 TB/s), the chain kernels
@@ -62,22 +61,16 @@ struct nero_stage1 {
     // NERO_MAT_FORK=1 (three streams only): the three material predictors' forward launches go to s3, idle in the forward, behind the SDF
     // forward -- they need feat and x8 only -- and are joined in front of nero_shade_encode, i.e. they run beside the first-order normal pass
     bool mat_fork = false;
+    bool owns_streams() const { return s2.stream || s3; }             // (wrong_device / drain_on_error, chain_host.h)
+    void drain_streams() {
+        s2.drain();
+        if (s3) (void)hipStreamSynchronize(s3);
+        dw_fork = 0;
+    }
+    hipStream_t fork_side(const Arena& A, hipStream_t main) { return s2.fork(main, !A.dry && n_streams >= 2); }
 };
 
 namespace {
-
-// the stream of the side branch: s2 behind everything `main` holds so far -- or `main` itself (dry runs, one-stream mode, timed launches)
-hipStream_t fork_side(nero_stage1* h, const Arena& A, hipStream_t main) {
-    if (A.dry || h->n_streams < 2 || !h->s2 || nero_prof_is_on()) return main;
-    (void)hipEventRecord(h->ev_fork, main);
-    (void)hipStreamWaitEvent(h->s2, h->ev_fork, 0);
-    return h->s2;
-}
-void join_side(nero_stage1* h, hipStream_t side, hipStream_t main) {
-    if (side == main) return;
-    (void)hipEventRecord(h->ev_join, side);
-    (void)hipStreamWaitEvent(main, h->ev_join, 0);
-}
 
 // the stream of the weight-gradient jobs: s3 behind everything `main` holds so far (the reverse pass that produced their operands)
 hipStream_t fork_dw(nero_stage1* h, const Arena& A, hipStream_t main) {
@@ -92,22 +85,6 @@ void join_dw(nero_stage1* h, const Arena& A, hipStream_t main) {
     (void)hipEventRecord(h->ev_dw_done, h->s3);
     (void)hipStreamWaitEvent(main, h->ev_dw_done, 0);
     h->dw_fork = 0;
-}
-
-// A call that fails between a fork and its join would leave work queued on the private streams with nothing ordering it in front of
-// whatever the caller does next with the workspace: every failing exit of the entry points drains them (host-blocking, error path only).
-int drain_on_error(nero_stage1* h, int rc) {
-    if (rc == NERO_OK) return rc;
-    if (h->s2) (void)hipStreamSynchronize(h->s2);
-    if (h->s3) (void)hipStreamSynchronize(h->s3);
-    h->dw_fork = 0;
-    (void)hipGetLastError();
-    return rc;
-}
-// the private streams belong to the device that was current at create time: a call under another current device would fork onto it
-bool wrong_device(const nero_stage1* h) {
-    int dev = -1;
-    return (h->s2 || h->s3) && hipGetDevice(&dev) == hipSuccess && h->device >= 0 && dev != h->device;
 }
 
 void build_chains(nero_stage1* h, const nero_stage1_weights* w) {
@@ -170,12 +147,6 @@ std::vector<Chain*> all_chains(nero_stage1* h) {
     if (h->cfg.human_light) v.push_back(&h->human_light);
     v.push_back(&h->mat[0]); v.push_back(&h->mat[1]); v.push_back(&h->mat[2]);
     return v;
-}
-
-size_t pack_floats_total(nero_stage1* h) {
-    size_t t = 0;
-    for (Chain* c : all_chains(h)) t += (c->pack_floats() + 63) / 64 * 64;
-    return t;
 }
 
 // no-grad SDF values of PE rows: -> heads [rows_pad, 4], column 0 = sdf   (SDFField.sdf_from_pe)
@@ -242,7 +213,7 @@ int do_forward(nero_stage1* h, Arena& A, int R, int T, int n_in, int n_out, cons
     const bool two = h->n_streams >= 2;                // (memory decisions follow the handle, not the moment: the size query is a dry run)
     hipStream_t so_ = hs;
     if (n_out > 0) {
-        so_ = fork_side(h, A, hs);                     // the NeRF++ branch: behind the compaction and the two memsets
+        so_ = h->fork_side(A, hs);                     // the NeRF++ branch: behind the compaction and the two memsets
         void* so = (void*)so_;
         h->pe88 = A.f32((size_t)rpo * 88); h->pev32 = A.f32((size_t)rpo * 32); h->dist_o = A.f32(rpo);
         if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
@@ -327,7 +298,7 @@ int do_forward(nero_stage1* h, Arena& A, int R, int T, int n_in, int n_out, cons
     }
     S.weights = A.f32((size_t)R * T);
     if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage1_render_fwd: workspace too small");
-    if (!A.dry) join_side(h, so_, hs);                 // both branches have scattered their alpha / colour
+    if (!A.dry) h->s2.join(so_, hs);                   // both branches have scattered their alpha / colour
     LAUNCH(nero_composite_fwd(h->alphaRT, h->colorRT, R, T, S.weights, rgb, stream));
     return NERO_OK;
 }
@@ -384,7 +355,7 @@ int do_backward(nero_stage1* h, Arena& A, const float* d_rgb, const float* d_ger
     LAUNCH(nero_composite_bwd(h->alphaRT, h->colorRT, S.weights, d_rgb, R, T, d_aRT, d_cRT, stream));
     hipStream_t so_ = hs;
     if (n_out > 0) {
-        so_ = fork_side(h, A, hs);                     // the NeRF++ branch of the backward: behind the compositing backward
+        so_ = h->fork_side(A, hs);                     // the NeRF++ branch of the backward: behind the compositing backward
         void* const main_stream = stream;
         stream = (void*)so_;                           // (the block below issues everything on `stream`)
         float* const main_partials = partials;
@@ -555,7 +526,7 @@ int do_backward(nero_stage1* h, Arena& A, const float* d_rgb, const float* d_ger
     } else if (d_inv_s_sum && !A.dry) {
         (void)hipMemsetAsync(d_inv_s_sum, 0, 4, hs);
     }
-    if (!A.dry) join_side(h, so_, hs);                 // the caller's stream continues behind BOTH branches
+    if (!A.dry) h->s2.join(so_, hs);                   // the caller's stream continues behind BOTH branches
     return nero_check_launch("nero_stage1_render_bwd");
 }
 
@@ -580,21 +551,15 @@ int nero_stage1_create(const nero_stage1_cfg* cfg, nero_stage1** out) {
     make_value_chain(h);
     const char* e = getenv("NERO_STREAMS");
     h->n_streams = e ? atoi(e) : NERO_STREAMS_DEFAULT;
-    if (hipGetDevice(&h->device) != hipSuccess) { h->device = -1; (void)hipGetLastError(); }
-    if (h->n_streams >= 2) {
-        if (hipStreamCreateWithFlags(&h->s2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();             // (no device in reach -- the CPU-side size queries still work -- or out of handles: one stream)
-            h->s2 = nullptr;
-        }
-        if (h->s2 && (hipEventCreateWithFlags(&h->ev_occ_in, hipEventDisableTiming) != hipSuccess ||
-                      hipEventCreateWithFlags(&h->ev_occ_out, hipEventDisableTiming) != hipSuccess)) {
-            (void)hipGetLastError();             // (out of handles: nero_stage1_occlusion keeps to the caller's one stream)
-            if (h->ev_occ_in) (void)hipEventDestroy(h->ev_occ_in);
-            h->ev_occ_in = h->ev_occ_out = nullptr;
-        }
+    h->device = current_device();
+    if (h->n_streams >= 2 && h->s2.create() &&
+        (hipEventCreateWithFlags(&h->ev_occ_in, hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(&h->ev_occ_out, hipEventDisableTiming) != hipSuccess)) {
+        (void)hipGetLastError();                 // (out of handles: nero_stage1_occlusion keeps to the caller's one stream)
+        if (h->ev_occ_in) (void)hipEventDestroy(h->ev_occ_in);
+        h->ev_occ_in = h->ev_occ_out = nullptr;
     }
-    const bool have_device = h->s2 != nullptr || h->n_streams < 2;
+    const bool have_device = h->s2.stream != nullptr || h->n_streams < 2;
     if (h->n_streams >= 3) {
         bool ok = hipStreamCreateWithFlags(&h->s3, hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreateWithFlags(&h->ev_dw_done, hipEventDisableTiming) == hipSuccess;
@@ -616,11 +581,9 @@ int nero_stage1_create(const nero_stage1_cfg* cfg, nero_stage1** out) {
 
 void nero_stage1_destroy(nero_stage1* h) {
     if (!h) return;
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_occ_in) (void)hipEventDestroy(h->ev_occ_in);
     if (h->ev_occ_out) (void)hipEventDestroy(h->ev_occ_out);
-    if (h->s2) (void)hipStreamDestroy(h->s2);
+    h->s2.destroy();
     for (int i = 0; i < nero_stage1::N_DW_EV; ++i)
         if (h->ev_dw[i]) (void)hipEventDestroy(h->ev_dw[i]);
     if (h->ev_dw_done) (void)hipEventDestroy(h->ev_dw_done);
@@ -628,25 +591,14 @@ void nero_stage1_destroy(nero_stage1* h) {
     delete h;
 }
 
-size_t nero_stage1_pack_bytes(nero_stage1* h) { return h ? pack_floats_total(h) * 4 : 0; }
+size_t nero_stage1_pack_bytes(nero_stage1* h) { return h ? pack_floats_total(all_chains(h)) * 4 : 0; }
 
 int nero_stage1_pack(nero_stage1* h, const nero_stage1_weights* w, void* pack_buf, void* stream) {
     if (!h || !w || !pack_buf) return nero_fail(NERO_ERR_ARG, "nero_stage1_pack: bad argument");
     build_chains(h, w);
-    const size_t total = pack_floats_total(h);
-    (void)hipMemsetAsync(pack_buf, 0, total * 4, (hipStream_t)stream);
-    std::vector<nero_pack_job> jobs;
-    float* p = static_cast<float*>(pack_buf);
-    for (Chain* c : all_chains(h)) {
-        float* q = p;
-        c->pack(q, jobs);
-        p += (c->pack_floats() + 63) / 64 * 64;
-    }
-    make_value_chain(h);
-    for (size_t i0 = 0; i0 < jobs.size(); i0 += NERO_MAX_PACK_JOBS) {
-        const int n = (int)(jobs.size() - i0 < NERO_MAX_PACK_JOBS ? jobs.size() - i0 : NERO_MAX_PACK_JOBS);
-        RC(nero_pack_batch(jobs.data() + i0, n, stream));
-    }
+    const int rc = pack_chains(all_chains(h), pack_buf, stream);
+    make_value_chain(h);                          // (shares the images just carved, whether or not the pack launches went through)
+    RC(rc);
     h->packed = true;
     return NERO_OK;
 }
@@ -710,8 +662,7 @@ int nero_stage1_sample(nero_stage1* h, int R, const float* o, const float* d, co
     if (!h || !h->packed || !o || !d || !near || !far || !variance || !z_vals || !ws)
         return nero_fail(NERO_ERR_ARG, "nero_stage1_sample: bad argument (pack the weights first)");
     if (R == 0) return NERO_OK;
-    Arena A;
-    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    Arena A(ws, ws_bytes);
     RC(do_sample(h, A, R, o, d, near, far, variance, rand1, rand_bg, z_vals, stream));
     return nero_check_launch("nero_stage1_sample");
 }
@@ -726,8 +677,7 @@ int nero_stage1_render_fwd(nero_stage1* h, int R, const float* o, const float* d
     const nero_stage1_cfg& c = h->cfg;
     const int T = c.n_samples + c.n_importance + c.n_bg_samples;
     Arena& A = h->A;
-    A = Arena();
-    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    A = Arena(ws, ws_bytes);
     nero_stage1_state& S = h->st;
     memset(&S, 0, sizeof(S));
     S.R = R; S.T = T;
@@ -768,8 +718,7 @@ int nero_stage1_get_state(nero_stage1* h, nero_stage1_state* out) {
 int nero_stage1_sdf_from_pe(nero_stage1* h, const float* pe, int n, float* out4, void* ws, size_t ws_bytes, void* stream) {
     if (!h || !h->packed || !pe || !out4 || !ws) return nero_fail(NERO_ERR_ARG, "nero_stage1_sdf_from_pe: bad argument");
     if (n == 0) return NERO_OK;
-    Arena A;
-    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    Arena A(ws, ws_bytes);
     float* res = nullptr;
     RC(sdf_from_pe(h, A, pe, n, res, stream));
     (void)hipMemcpyAsync(out4, res, (size_t)rpad(n) * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream);
@@ -797,7 +746,7 @@ int nero_stage1_occlusion(nero_stage1* h, const float* d, const float* variance,
         return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: needs n_in > 0, 1 <= cap <= 4096, 2 <= sn0 <= 160, 1 <= sn1 <= 32");
     if (wrong_device(h)) return nero_fail(NERO_ERR_ARG, "nero_stage1_occlusion: the current device is not the one the handle was created on");
     hipStream_t sb = (hipStream_t)branch_stream, sj = (hipStream_t)join_stream;
-    const bool side = sb != sj && h->n_streams >= 2 && h->s2 && h->ev_occ_in && h->ev_occ_out && !nero_prof_is_on();
+    const bool side = sb != sj && h->n_streams >= 2 && h->s2.stream && h->ev_occ_in && h->ev_occ_out && !nero_prof_is_on();
     if (sb != sj && !side) {
         // one-stream order: what the caller queued on its branch stream (the key draw) goes in front, everything else on the join stream
         if (!h->ev_occ_out || hipEventRecord(h->ev_occ_out, sb) != hipSuccess || hipStreamWaitEvent(sj, h->ev_occ_out, 0) != hipSuccess) {
@@ -807,8 +756,7 @@ int nero_stage1_occlusion(nero_stage1* h, const float* d, const float* variance,
         sb = sj;
     }
     if (side) (void)hipStreamWaitEvent(sb, h->ev_occ_in, 0);      // behind nero_sdf_alpha_fwd of the forward
-    Arena A;
-    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    Arena A(ws, ws_bytes);
     int rc = do_occlusion(h, A, h->st.n_in, d, variance, keys, thresh, cap, sn0, sn1, cand, counts, occ, (void*)sb);
     if (side) {                                                  // (on a failure too: nothing of the branch stays unordered behind the caller)
         (void)hipEventRecord(h->ev_occ_out, sb);

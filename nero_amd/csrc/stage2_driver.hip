@@ -6,7 +6,7 @@
 // also where the reference calls its third-party tracer (raytracing/raytracer.py:49 from network/field.py:860).
 // Memory: one caller-owned workspace, carved by the same arena as the Stage-I driver; host synchronisation: one read-back of the
 // (miss, hit) ray counts, which size the light-MLP launches.
-#include "chain_host.h"
+#include "chain_kernels.h"
 #include <stdlib.h>
 #ifndef NERO_STREAMS_DEFAULT
 #define NERO_STREAMS_DEFAULT 2
@@ -74,36 +74,15 @@ struct nero_stage2 {
     Fwd f_out, f_in, f_hum;
     const float *dirs = nullptr, *depth = nullptr, *fnrm = nullptr, *poses = nullptr, *tab_s = nullptr;
     // a second stream for the HIT rows (inner-light MLP) beside the MISS rows (outer / human light): the two row sets share nothing
-    // between the compaction and the estimator (forward), resp. between its backward and the direction backward (as stage1_driver.hip)
+    // between the compaction and the estimator (forward), resp. between its backward and the direction backward
     int n_streams = 1;
-    hipStream_t s2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    SideStream s2;
+    bool owns_streams() const { return s2.stream != nullptr; }        // (wrong_device / drain_on_error, chain_host.h)
+    void drain_streams() { s2.drain(); }
+    hipStream_t fork_side(const Arena& A, hipStream_t main) { return s2.fork(main, !A.dry && n_streams >= 2); }
 };
 
 namespace {
-
-// (as stage1_driver.hip) a failing exit between a fork and its join drains the private stream; calls under another current device are refused
-int drain_on_error(nero_stage2* h, int rc) {
-    if (rc == NERO_OK) return rc;
-    if (h->s2) (void)hipStreamSynchronize(h->s2);
-    (void)hipGetLastError();
-    return rc;
-}
-bool wrong_device(const nero_stage2* h) {
-    int dev = -1;
-    return h->s2 && hipGetDevice(&dev) == hipSuccess && h->device >= 0 && dev != h->device;
-}
-hipStream_t fork_side(nero_stage2* h, const Arena& A, hipStream_t main) {
-    if (A.dry || h->n_streams < 2 || !h->s2 || nero_prof_is_on()) return main;
-    (void)hipEventRecord(h->ev_fork, main);
-    (void)hipStreamWaitEvent(h->s2, h->ev_fork, 0);
-    return h->s2;
-}
-void join_side(nero_stage2* h, hipStream_t side, hipStream_t main) {
-    if (side == main) return;
-    (void)hipEventRecord(h->ev_join, side);
-    (void)hipStreamWaitEvent(main, h->ev_join, 0);
-}
 
 void build_chains(nero_stage2* h, const nero_stage2_weights* w) {
     const nero_linear* L = w->lin;
@@ -129,12 +108,6 @@ std::vector<Chain*> all_chains(nero_stage2* h) {
     if (h->cfg.human_lights) v.push_back(&h->human_light);
     v.push_back(&h->mat[0]); v.push_back(&h->mat[1]); v.push_back(&h->mat[2]);
     return v;
-}
-
-size_t pack_floats_total(nero_stage2* h) {
-    size_t t = 0;
-    for (Chain* c : all_chains(h)) t += (c->pack_floats() + 63) / 64 * 64;
-    return t;
 }
 
 int do_predict_fwd(nero_stage2* h, Arena& A, const float* x, int n, float* raw5, void* stream) {
@@ -196,7 +169,7 @@ int do_shade_lights(nero_stage2* h, Arena& A, const float* pos, float* rgb, floa
     h->f_out = Fwd(); h->f_in = Fwd(); h->f_hum = Fwd();
     if (A.failed) return nero_fail(NERO_ERR_ARG, "nero_stage2_shade_fwd: workspace too small");
     // the hit branch starts behind everything the caller's stream holds NOW (before the miss branch is issued on it)
-    const hipStream_t fork_side_early = (n_miss > 0 && n_hit > 0) ? fork_side(h, A, (hipStream_t)stream) : (hipStream_t)stream;
+    const hipStream_t fork_side_early = (n_miss > 0 && n_hit > 0) ? h->fork_side(A, (hipStream_t)stream) : (hipStream_t)stream;
     if (n_miss > 0) {
         LAUNCH(nero_mc_encode_miss(h->dirs, h->miss_idx, h->pt, D, c.sphere_direction, n_miss, h->Xm, stream));
         RC(h->outer_light.forward(A, h->M, h->Xm, h->kout, nullptr, 0, n_miss, true, h->f_out, stream));
@@ -214,7 +187,7 @@ int do_shade_lights(nero_stage2* h, Arena& A, const float* pos, float* rgb, floa
         LAUNCH(nero_mc_encode_hit(h->dirs, pos, h->fnrm, h->hit_idx, n_hit, h->Xh, (void*)side));
         RC(h->inner_light.forward(A, h->M, h->Xh, 128, nullptr, 0, n_hit, true, h->f_in, (void*)side));
     }
-    if (!A.dry) join_side(h, side, (hipStream_t)stream);
+    if (!A.dry) h->s2.join(side, (hipStream_t)stream);
     LAUNCH(nero_mc_combine_fwd_h(h->pt, h->dirs, h->depth, h->slot, n_miss > 0 ? h->f_out.heads[3] : nullptr, n_hit > 0 ? h->f_in.heads[3] : nullptr,
                                  (n_miss > 0 && c.human_lights && h->n_hum > 0) ? h->f_hum.heads[3] : nullptr, h->hmask, h->n_hum, c.light_exp_max,
                                  c.inner_light_exp_max, h->P, c.diffuse_sample_num, c.specular_sample_num, c.geometry_type, rgb, dl, sl, sp, stream));
@@ -253,7 +226,7 @@ int do_shade_bwd(nero_stage2* h, Arena& A, const float* d_rgb, const float* d_dl
                                  d_rgb, d_dl, d_or, d_ir, d_hr, d_mat5, d_w, stream));
     const float* hd[MAXL] = {};
     // the hit branch (inner light) starts behind the estimator's backward, beside the miss branch
-    const hipStream_t side = (n_miss > 0 && n_hit > 0) ? fork_side(h, A, hs) : hs;
+    const hipStream_t side = (n_miss > 0 && n_hit > 0) ? h->fork_side(A, hs) : hs;
     if (n_miss > 0) {
         size_t mk = A.mark();
         predictor_grads(h->outer_light, g + M_OUTER, h->kout);
@@ -281,7 +254,7 @@ int do_shade_bwd(nero_stage2* h, Arena& A, const float* d_rgb, const float* d_dl
         RC(h->inner_light.weight_grads(A, h->M, h->f_in, ib, n_hit, h->Xh, 128, nullptr, 0, hdh, nullptr, nullptr, partials_h, (void*)side));
         if (!two) A.release(mk);
     }
-    if (!A.dry) join_side(h, side, hs);
+    if (!A.dry) h->s2.join(side, hs);
     LAUNCH(nero_mc_dir_bwd_h(h->pt, h->dirs, h->fnrm, h->slot, h->tab_s, dXm, dXh, d_w, P, Dd, Ds, d_mat5, c.sphere_direction, dXhum, h->poses, n_hum, stream));
     return nero_check_launch("nero_stage2_shade_bwd");
 }
@@ -306,43 +279,24 @@ int nero_stage2_create(const nero_stage2_cfg* cfg, nero_stage2** out) {
     h->n_streams = e ? atoi(e) : NERO_STREAMS_DEFAULT;
     const char* sd = getenv("NERO_MC_SKIP_DEAD");
     h->skip_dead = !(sd && atoi(sd) == 0);
-    if (hipGetDevice(&h->device) != hipSuccess) { h->device = -1; (void)hipGetLastError(); }
-    if (h->n_streams >= 2) {
-        if (hipStreamCreateWithFlags(&h->s2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();             // (no device in reach -- the size queries still work -- or out of handles: one stream)
-            h->s2 = nullptr;
-        }
-    }
+    h->device = current_device();
+    if (h->n_streams >= 2) (void)h->s2.create();
     *out = h;
     return NERO_OK;
 }
 
 void nero_stage2_destroy(nero_stage2* h) {
     if (!h) return;
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->s2) (void)hipStreamDestroy(h->s2);
+    h->s2.destroy();
     delete h;
 }
 
-size_t nero_stage2_pack_bytes(nero_stage2* h) { return h ? pack_floats_total(h) * 4 : 0; }
+size_t nero_stage2_pack_bytes(nero_stage2* h) { return h ? pack_floats_total(all_chains(h)) * 4 : 0; }
 
 int nero_stage2_pack(nero_stage2* h, const nero_stage2_weights* w, void* pack_buf, void* stream) {
     if (!h || !w || !pack_buf) return nero_fail(NERO_ERR_ARG, "nero_stage2_pack: bad argument");
     build_chains(h, w);
-    (void)hipMemsetAsync(pack_buf, 0, pack_floats_total(h) * 4, (hipStream_t)stream);
-    std::vector<nero_pack_job> jobs;
-    float* p = static_cast<float*>(pack_buf);
-    for (Chain* c : all_chains(h)) {
-        float* q = p;
-        c->pack(q, jobs);
-        p += (c->pack_floats() + 63) / 64 * 64;
-    }
-    for (size_t i0 = 0; i0 < jobs.size(); i0 += NERO_MAX_PACK_JOBS) {
-        const int n = (int)(jobs.size() - i0 < NERO_MAX_PACK_JOBS ? jobs.size() - i0 : NERO_MAX_PACK_JOBS);
-        RC(nero_pack_batch(jobs.data() + i0, n, stream));
-    }
+    RC(pack_chains(all_chains(h), pack_buf, stream));
     h->packed = true;
     return NERO_OK;
 }
@@ -383,8 +337,7 @@ size_t nero_stage2_workspace_bytes(nero_stage2* h, int n_pred, int P) {
 int nero_stage2_predict_fwd(nero_stage2* h, const float* x, int n, float* raw5, void* ws, size_t ws_bytes, void* stream) {
     if (!h || !h->packed || !x || !raw5 || !ws || n <= 0) return nero_fail(NERO_ERR_ARG, "nero_stage2_predict_fwd: bad argument (pack the weights first)");
     Arena& A = h->A;
-    A = Arena();
-    A.base = static_cast<char*>(ws); A.cap = ws_bytes;
+    A = Arena(ws, ws_bytes);
     RC(do_predict_fwd(h, A, x, n, raw5, stream));
     h->predict_mark = h->shade_mark = A.mark();
     h->P = 0;

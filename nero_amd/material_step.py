@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .chain import Chain, Dense, Head, row_pad
+from .chain import Chain, Dense, Head, flatten_linears, pack_chains, row_pad, unflatten_linears
 from .fields import fibonacci_az_el
 from .shape_step import _p, predictor_entries
 
@@ -44,26 +44,13 @@ class MaterialKernels:
         self.tab_d, self.tab_s = table(dn), table(sn)
 
     def pack(self):
-        """(re)pack the operand images of all networks into ONE zero-filled flat buffer (kept while its size fits) with the pack jobs
-        of every chain batched (as ShapeKernels.pack)"""
-        from .chain import run_pack_jobs
-        parts = [c for c in [self.feats, self.outer_light, self.inner_light, self.human_light] + self.mat if c is not None]
-        sizes = [(c.pack_floats() + 63) // 64 * 64 for c in parts]
-        total = sum(sizes)
-        flat = getattr(self, '_flat', None)
-        if flat is None or flat.numel() != total:
-            flat = self._flat = torch.zeros(total, dtype=torch.float32, device=self.device)
-        else:
-            flat.zero_()
-        jobs, off = [], 0
-        for c, n in zip(parts, sizes):
-            jobs += c.pack(flat[off:off + n], run=False)
-            off += n
-        run_pack_jobs(jobs)
-        return self
+        """(re)pack the operand images of all networks (chain.pack_chains)"""
+        return pack_chains(self, [self.feats, self.outer_light, self.inner_light, self.human_light] + self.mat)
 
 
 MAT_NAMES = ('metallic', 'roughness', 'albedo')
+PREDICTORS = (('metallic', 'metallic_predictor'), ('roughness', 'roughness_predictor'), ('albedo', 'albedo_predictor'),
+              ('outer_light', 'outer_light'), ('inner_light', 'inner_light'), ('human', 'human_light'))
 
 
 def flatten_material_effective(shader):
@@ -73,33 +60,13 @@ def flatten_material_effective(shader):
 
 
 def _flatten_material_effective(shader):
-    names, ts = [], []
-
-    def add(prefix, wb):
-        names.extend([prefix + '.weight', prefix + '.bias'])
-        ts.extend(wb)
-    for i, wb in enumerate(shader.feats_network.effective()):
-        add(f'feats.{i}', wb)
-    preds = ['metallic_predictor', 'roughness_predictor', 'albedo_predictor', 'outer_light', 'inner_light']
-    if shader.cfg['human_lights']:
-        preds.append('human_light')
-    for pn in preds:
-        for i, wb in enumerate(getattr(shader, pn).effective()):
-            add(f'{pn}.{i}', wb)
-    return names, ts
+    preds = [pn for short, pn in PREDICTORS if short != 'human' or shader.cfg['human_lights']]
+    return flatten_linears([('feats', shader.feats_network.effective())] + [(pn, getattr(shader, pn).effective()) for pn in preds])
 
 
 def unflatten_material_effective(names, ts):
-    d = dict(zip(names, ts))
-
-    def wb(prefix):
-        return d[prefix + '.weight'], d[prefix + '.bias']
-    eff = {'feats': [wb(f'feats.{i}') for i in range(8)]}
-    for short, pn in (('metallic', 'metallic_predictor'), ('roughness', 'roughness_predictor'), ('albedo', 'albedo_predictor'),
-                      ('outer_light', 'outer_light'), ('inner_light', 'inner_light'), ('human', 'human_light')):
-        if f'{pn}.0.weight' in d:
-            eff[short] = [wb(f'{pn}.{i}') for i in range(4)]
-    return eff
+    wb, preds = unflatten_linears(names, ts, PREDICTORS)
+    return {'feats': [wb(f'feats.{i}') for i in range(8)], **preds}
 
 
 class PredictMaterials(torch.autograd.Function):

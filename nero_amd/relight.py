@@ -22,7 +22,6 @@ from .raytracing import RayTracer
 from .renderer import linear_to_srgb
 from .texture import _png_chunk
 
-HEADER_PATH = os.path.join(os.path.dirname(L.HEADER_PATH), 'nero_hip_relight.h')
 CONVENTIONS = {'nero': 0, 'nero_real': 1, 'blender': 2}          # nero_env_lookup's `convention`
 GEOMETRY_TYPES = {'schlick': 0, 'ggx_smith': 1}                  # as nero_amd.stage2
 MISS_DEPTH = 10.0
@@ -30,22 +29,6 @@ MAX_LANES = 2 ** 31 - 64                                         # (point, padde
 DEFAULT_CHUNK_LANES = 1 << 26
 
 
-def _bind():
-    """restype / argtypes of the third header's entry points on the library _lib loaded (the header is not part of _lib.HEADER_PATHS: this
-    module binds it).  -> {function: (restype, argtypes)}"""
-    with open(HEADER_PATH) as f:
-        sigs = L.parse_header(f.read())
-    for fn, (restype, argtypes) in sigs.items():
-        try:
-            f = getattr(L.lib, fn)
-        except AttributeError:
-            raise ImportError(f'{L.LIB_PATH} does not export {fn}, which nero_hip_relight.h declares: rebuild the library') from None
-        setattr(f, 'restype', restype)
-        setattr(f, 'argtypes', argtypes)
-    return sigs
-
-
-SIGNATURES = _bind()
 _lib = L.lib
 
 

@@ -8,6 +8,25 @@ import torch.nn as nn
 from .fields import build_shape_fields
 
 
+def _cached_kernels(owner, net, flatten, unflatten, kernels, cfg):
+    """(names, effective weights as autograd tensors, packed kernels(...)) of `net` for the current parameter values.  Under no_grad the
+    result is cached on `owner` and re-used until a parameter of `net` changes (storage pointer or torch's in-place version counter), the
+    GEMM modes do, or owner._param_epoch does -- bumped by optimisers that update the parameters with raw kernels, which torch's version
+    counters cannot see (nero_amd.train.FusedShapeOptimizer)."""
+    from .chain import GEMM_MODE
+    key = None
+    if not torch.is_grad_enabled():
+        key = (tuple((p.data_ptr(), p._version) for p in net.parameters()), tuple(sorted(GEMM_MODE.items())), getattr(owner, '_param_epoch', 0))
+        cached = getattr(owner, '_kern_cache', None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+    names, eff = flatten(net)
+    K = kernels(unflatten(names, [t.detach() for t in eff]), cfg, eff[0].device).pack()
+    if key is not None:
+        owner._kern_cache = (key, (names, eff, K))
+    return names, eff, K
+
+
 class NeROShapeRenderer(nn.Module):
     # same keys / defaults as the reference (network/renderer.py:64-111)
     default_cfg = {
@@ -375,21 +394,7 @@ class NeROShapeRenderer(nn.Module):
         render_image / nvs / test_step / extract_fields) the packed operand images are cached and re-used until a parameter changes
         (storage pointer or torch's in-place version counter), so a multi-chunk render packs the ten networks once."""
         from .shape_step import ShapeKernels, flatten_effective, unflatten_effective
-        from .chain import GEMM_MODE
-        key = None
-        if not torch.is_grad_enabled():
-            # (_param_epoch: bumped by optimisers that update the parameters with raw kernels, which torch's version counters
-            # cannot see -- nero_amd.train.FusedShapeOptimizer)
-            key = (tuple((p.data_ptr(), p._version) for p in self.parameters()), tuple(sorted(GEMM_MODE.items())),
-                   getattr(self, '_param_epoch', 0))
-            cached = getattr(self, '_kern_cache', None)
-            if cached is not None and cached[0] == key:
-                return cached[1]
-        names, eff = flatten_effective(self)
-        K = ShapeKernels(unflatten_effective(names, [t.detach() for t in eff]), self.color_network.cfg, eff[0].device).pack()
-        if key is not None:
-            self._kern_cache = (key, (names, eff, K))
-        return names, eff, K
+        return _cached_kernels(self, self, flatten_effective, unflatten_effective, ShapeKernels, self.color_network.cfg)
 
     def env_light(self, h, w, gamma=True, roughness=0.0, chunk=None):
         """the illumination AppShadingNetwork.outer_light has learned, as an h x w lat-long panorama: float32 [h, w, 3] on the device.  The
@@ -584,19 +589,8 @@ class NeROMaterialRenderer(nn.Module):
         shade() per 1024-ray chunk) the packed operand images are cached until a parameter changes, exactly like
         NeROShapeRenderer._kernels -- an 800 x 800 view used to re-flatten and re-pack all networks 625 times."""
         from .material_step import MaterialKernels, flatten_material_effective, unflatten_material_effective
-        from .chain import GEMM_MODE
-        key = None
-        if not torch.is_grad_enabled():
-            key = (tuple((p.data_ptr(), p._version) for p in self.shader_network.parameters()), tuple(sorted(GEMM_MODE.items())),
-                   getattr(self, '_param_epoch', 0))
-            cached = getattr(self, '_kern_cache', None)
-            if cached is not None and cached[0] == key:
-                return cached[1]
-        names, eff = flatten_material_effective(self.shader_network)
-        K = MaterialKernels(unflatten_material_effective(names, [t.detach() for t in eff]), self.shader_network.cfg, eff[0].device).pack()
-        if key is not None:
-            self._kern_cache = (key, (names, eff, K))
-        return names, eff, K
+        net = self.shader_network
+        return _cached_kernels(self, net, flatten_material_effective, unflatten_material_effective, MaterialKernels, net.cfg)
 
     def predict_materials(self, pts, _kern=None):
         """-> metallic [n,1], roughness [n,1] (affine to [0.04^2, 1]), albedo [n,3]   (network/field.py:915-922)"""

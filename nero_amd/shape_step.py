@@ -7,7 +7,7 @@ import os
 import torch
 
 from . import _lib as L
-from .chain import Chain, Dense, Head, row_pad
+from .chain import Chain, Dense, Head, flatten_linears, pack_chains, row_pad, unflatten_linears
 from .sdf import SDFField
 
 _p = L.ptr
@@ -66,25 +66,9 @@ class ShapeKernels:
         return Xi, Xo
 
     def pack(self):
-        """(re)pack the operand images of all ten networks: ONE zero-filled flat buffer (kept and re-used while its size fits) and
-        the pack jobs of every chain batched into a handful of launches (nero_pack_batch takes 64 jobs) -- ~10 launches per step
-        instead of ~35 plus as many allocations."""
-        from .chain import run_pack_jobs
-        parts = [self.sdf, self.nerf_trunk, self.nerf_head, self.outer_light, self.inner_light, self.inner_weight, self.human_light] + self.mat
-        parts = [c for c in parts if c is not None]
-        sizes = [(c.pack_floats() + 63) // 64 * 64 for c in parts]          # 256-byte aligned images
-        total = sum(sizes)
-        flat = getattr(self, '_flat', None)
-        if flat is None or flat.numel() != total:
-            flat = self._flat = torch.zeros(total, dtype=torch.float32, device=self.device)
-        else:
-            flat.zero_()
-        jobs, off = [], 0
-        for c, n in zip(parts, sizes):
-            jobs += c.pack(flat[off:off + n], run=False)
-            off += n
-        run_pack_jobs(jobs)
-        return self
+        """(re)pack the operand images of all ten networks (chain.pack_chains)"""
+        return pack_chains(self, [self.sdf, self.nerf_trunk, self.nerf_head, self.outer_light, self.inner_light, self.inner_weight,
+                                  self.human_light] + self.mat)
 
 
 def flatten_effective(net):
@@ -94,43 +78,24 @@ def flatten_effective(net):
     return batched_weight_norm(lambda: _flatten_effective(net), owner=net)
 
 
-def _flatten_effective(net):
-    names, ts = [], []
+PREDICTORS = (('metallic', 'metallic_predictor'), ('roughness', 'roughness_predictor'), ('albedo', 'albedo_predictor'),
+              ('outer_light', 'outer_light'), ('inner_light', 'inner_light'), ('inner_weight', 'inner_weight'),
+              ('human', 'human_light_predictor'))
 
-    def add(prefix, wb):
-        names.extend([prefix + '.weight', prefix + '.bias'])
-        ts.extend(wb)
-    for l, wb in enumerate(net.sdf_network.effective()):
-        add(f'sdf.{l}', wb)
-    nf = net.outer_nerf.effective()
-    for i, wb in enumerate(nf['pts']):
-        add(f'nerf.pts.{i}', wb)
-    for k in ('views', 'feature', 'alpha', 'rgb'):
-        add(f'nerf.{k}', nf[k])
-    cn = net.color_network
-    preds = ['metallic_predictor', 'roughness_predictor', 'albedo_predictor', 'outer_light', 'inner_light', 'inner_weight']
-    if cn.cfg['human_light']:
-        preds.append('human_light_predictor')
-    for pn in preds:
-        for i, wb in enumerate(getattr(cn, pn).effective()):
-            add(f'{pn}.{i}', wb)
-    return names, ts
+
+def _flatten_effective(net):
+    sdf, nf, cn = net.sdf_network.effective(), net.outer_nerf.effective(), net.color_network
+    preds = [pn for short, pn in PREDICTORS if short != 'human' or cn.cfg['human_light']]
+    return flatten_linears([('sdf', sdf), ('nerf.pts', nf['pts'])] + [(f'nerf.{k}', nf[k]) for k in ('views', 'feature', 'alpha', 'rgb')] +
+                           [(pn, getattr(cn, pn).effective()) for pn in preds])
 
 
 def unflatten_effective(names, ts):
-    d = dict(zip(names, ts))
-
-    def wb(prefix):
-        return d[prefix + '.weight'], d[prefix + '.bias']
-    eff = {'sdf': [wb(f'sdf.{l}') for l in range(sum(1 for k in d if k.startswith('sdf.') and k.endswith('.weight')))],
-           'nerf': {'pts': [wb(f'nerf.pts.{i}') for i in range(8)], 'views': wb('nerf.views'), 'feature': wb('nerf.feature'),
-                    'alpha': wb('nerf.alpha'), 'rgb': wb('nerf.rgb')}}
-    for short, pn in (('metallic', 'metallic_predictor'), ('roughness', 'roughness_predictor'), ('albedo', 'albedo_predictor'),
-                      ('outer_light', 'outer_light'), ('inner_light', 'inner_light'), ('inner_weight', 'inner_weight'),
-                      ('human', 'human_light_predictor')):
-        if f'{pn}.0.weight' in d:
-            eff[short] = [wb(f'{pn}.{i}') for i in range(4)]
-    return eff
+    wb, preds = unflatten_linears(names, ts, PREDICTORS)
+    n_sdf = sum(1 for k in names if k.startswith('sdf.') and k.endswith('.weight'))
+    return {'sdf': [wb(f'sdf.{l}') for l in range(n_sdf)],
+            'nerf': {'pts': [wb(f'nerf.pts.{i}') for i in range(8)], 'views': wb('nerf.views'), 'feature': wb('nerf.feature'),
+                     'alpha': wb('nerf.alpha'), 'rgb': wb('nerf.rgb')}, **preds}
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -11,26 +11,7 @@ import torch
 
 from . import _lib as L
 
-HEADER_PATH = os.path.join(os.path.dirname(L.HEADER_PATH), 'nero_hip_surface.h')
 MAX_SAMPLES = 2 ** 31 - 1
-
-
-def _bind():
-    """restype / argtypes of the fourth header's entry points on the library _lib loaded (the header is not part of _lib.HEADER_PATHS: this
-    module binds it).  -> {function: (restype, argtypes)}"""
-    with open(HEADER_PATH) as f:
-        sigs = L.parse_header(f.read())
-    for fn, (restype, argtypes) in sigs.items():
-        try:
-            f = getattr(L.lib, fn)
-        except AttributeError:
-            raise ImportError(f'{L.LIB_PATH} does not export {fn}, which nero_hip_surface.h declares: rebuild the library') from None
-        setattr(f, 'restype', restype)
-        setattr(f, 'argtypes', argtypes)
-    return sigs
-
-
-SIGNATURES = _bind()
 _lib = L.lib
 
 

@@ -1,4 +1,4 @@
-"""CPU tier of the relighter (include/nero_hip_relight.h, nero_amd/relight.py): the third header is bound by relight.py and by nobody else,
+"""CPU tier of the relighter (include/nero_hip_relight.h, nero_amd/relight.py): the third header is bound by _lib.py like the others,
 its entry points refuse bad arguments before any device call, the launch arithmetic holds at its limit under the sanitizer, the orbit
 equals the reference's, the stored roughness is squared once, the RGBA writer round-trips, and the restatement (tests/relight_ref.py) has
 its closed forms and stays inside the exemption cap on the committed direction sets."""
@@ -34,22 +34,23 @@ def _params(text):
             for name, params in re.findall(r'\b(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)}
 
 
-def test_the_third_header_is_bound_by_relight_py(RL):
+def test_the_third_header_is_bound_by_lib_py(RL):
     from nero_amd import _lib as L
     protos = _params(open(HEADER).read())
     assert protos == NAMES
-    assert RL.HEADER_PATH == HEADER and HEADER not in L.HEADER_PATHS and len(L.HEADER_PATHS) == 2
-    others = L.parse_headers()
-    assert len(others) == 175 and not set(protos) & set(others)
-    assert set(RL.SIGNATURES) == set(protos)
-    raw = C.CDLL(L.LIB_PATH)
-    for name, n_par in protos.items():
-        assert hasattr(raw, name), name
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-        assert fn.restype is (C.c_size_t if name == 'nero_relight_workspace_bytes' else C.c_int)
-    assert L.lib.nero_env_lookup.argtypes[6] is C.c_int64 and L.lib.nero_env_lookup.argtypes[7] is C.c_float
-    assert L.lib.nero_bvh_relight.argtypes[18] is C.c_size_t and L.lib.nero_bvh_relight.argtypes[13] is C.c_float
+    assert L.HEADER_PATHS[2] == HEADER and len(L.HEADER_PATHS) == 4
+    assert not hasattr(RL, 'SIGNATURES') and not hasattr(RL, 'HEADER_PATH') and not hasattr(RL, '_bind')
+    sigs = L.parse_headers()
+    assert {n for n, s in sigs.items() if s[2] == 'nero_hip_relight.h'} == set(protos)
+    assert len([n for n, s in sigs.items() if s[2] in ('nero_hip.h', 'nero_hip_visibility.h')]) == 175
+    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: what bind() alone gives, whatever was imported
+    for lib in (fresh, L.lib):
+        for name, n_par in protos.items():
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
+            assert fn.restype is (C.c_size_t if name == 'nero_relight_workspace_bytes' else C.c_int)
+        assert lib.nero_env_lookup.argtypes[6] is C.c_int64 and lib.nero_env_lookup.argtypes[7] is C.c_float
+        assert lib.nero_bvh_relight.argtypes[18] is C.c_size_t and lib.nero_bvh_relight.argtypes[13] is C.c_float
 
 
 def test_entry_points_refuse_bad_arguments_without_a_device(RL):

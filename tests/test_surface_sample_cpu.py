@@ -1,5 +1,5 @@
-"""CPU tier of the surface sampler (include/nero_hip_surface.h, nero_amd/surface.py): the fourth header is bound by surface.py and by nobody
-else, its entry points refuse bad arguments before any device call, the limit arithmetic holds at n = 2^31 - 1 and T = 2^31 - 2 under the
+"""CPU tier of the surface sampler (include/nero_hip_surface.h, nero_amd/surface.py): the fourth header is bound by _lib.py like the
+others, its entry points refuse bad arguments before any device call, the limit arithmetic holds at n = 2^31 - 1 and T = 2^31 - 2 under the
 sanitizer, and the restatement (tests/surface_ref.py) has the properties the contract promises: the stratified counts, the chi-square of
 independent draws, the moments of the barycentric weights, the silence of degenerate triangles, a closed form, and the command lines."""
 import ctypes as C
@@ -51,23 +51,23 @@ def _script(name):
     return mod
 
 
-def test_the_fourth_header_is_bound_by_surface_py(SF):
+def test_the_fourth_header_is_bound_by_lib_py(SF):
     from nero_amd import _lib as L
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', open(HEADER).read(), flags=re.S)
     protos = {name: params.count(',') + 1 for name, params in re.findall(r'\b(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)}
     assert protos == NAMES
-    assert SF.HEADER_PATH == HEADER and HEADER not in L.HEADER_PATHS and len(L.HEADER_PATHS) == 2
-    assert not set(protos) & set(L.parse_headers())
-    assert set(SF.SIGNATURES) == set(protos)
-    raw = C.CDLL(L.LIB_PATH)
-    for name, n_par in protos.items():
-        assert hasattr(raw, name), name
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-        assert fn.restype is (C.c_size_t if name == 'nero_surface_cdf_workspace_bytes' else C.c_int)
-    assert L.lib.nero_surface_cdf_workspace_bytes.argtypes == [C.c_int64]
-    a = L.lib.nero_surface_sample.argtypes
-    assert a[1] is C.c_int64 and a[3] is C.c_int64 and a[6:9] == [C.c_int64] * 3 and a[9] is C.c_uint and a[10] is C.c_int
+    assert L.HEADER_PATHS[3] == HEADER and len(L.HEADER_PATHS) == 4
+    assert not hasattr(SF, 'SIGNATURES') and not hasattr(SF, 'HEADER_PATH') and not hasattr(SF, '_bind')
+    assert {n for n, s in L.parse_headers().items() if s[2] == 'nero_hip_surface.h'} == set(protos)
+    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: what bind() alone gives, whatever was imported
+    for lib in (fresh, L.lib):
+        for name, n_par in protos.items():
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
+            assert fn.restype is (C.c_size_t if name == 'nero_surface_cdf_workspace_bytes' else C.c_int)
+        assert lib.nero_surface_cdf_workspace_bytes.argtypes == [C.c_int64]
+        a = lib.nero_surface_sample.argtypes
+        assert a[1] is C.c_int64 and a[3] is C.c_int64 and a[6:9] == [C.c_int64] * 3 and a[9] is C.c_uint and a[10] is C.c_int
     build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
     assert 'nero_hip_surface.h' in build                              # a change of the header rebuilds the library
     src = open(os.path.join(ROOT, 'nero_amd', 'surface.py')).read()

@@ -35,21 +35,27 @@ def test_the_second_header_is_bound_like_the_first(L):
     protos = _params(open(VIS_HEADER).read())
     assert sorted(protos) == ['nero_ao_rays', 'nero_bvh_ao', 'nero_bvh_occluded']
     assert [protos[k] for k in sorted(protos)] == [10, 11, 9]
-    raw = C.CDLL(L.LIB_PATH)
-    for name, n_par in protos.items():
-        assert hasattr(raw, name), name                               # exported
-        fn = getattr(L.lib, name)
-        assert fn.restype is C.c_int and fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-    assert L.lib.nero_ao_rays.argtypes[5] is C.c_uint and L.lib.nero_bvh_occluded.argtypes[5] is C.c_float
-    assert L.HEADER_PATHS[0] == L.HEADER_PATH and L.HEADER_PATHS[1] == VIS_HEADER and len(L.HEADER_PATHS) == 2
+    assert {n for n, s in L.parse_headers().items() if s[2] == 'nero_hip_visibility.h'} == set(protos)
+    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: exported, and what bind() alone gives
+    for lib in (fresh, L.lib):
+        for name, n_par in protos.items():
+            fn = getattr(lib, name)
+            assert fn.restype is C.c_int and fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
+        assert lib.nero_ao_rays.argtypes[5] is C.c_uint and lib.nero_bvh_occluded.argtypes[5] is C.c_float
+    assert L.HEADER_PATHS[0] == L.HEADER_PATH and L.HEADER_PATHS[1] == VIS_HEADER and len(L.HEADER_PATHS) == 4
+    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()     # the order build() lists them in; each one a build dependency
+    at = [build.index(f"'{os.path.basename(p)}'") for p in L.HEADER_PATHS]
+    assert at == sorted(at)
 
 
 def test_no_name_is_declared_twice(L, tmp_path):
     first = L.parse_header(open(L.HEADER_PATH).read())
     second = L.parse_header(open(VIS_HEADER).read())
     assert not set(first) & set(second)
-    assert len(first) == 172                                          # the first header is as it was: new entry points go into the second
-    assert set(L.parse_headers()) == set(first) | set(second)
+    assert len(first) == 172                                          # the first header is as it was: new entry points go into the others
+    assert set(L.parse_headers(L.HEADER_PATHS[:2])) == set(first) | set(second)
+    assert set(L.parse_headers()) == set().union(*(L.parse_header(open(p).read()) for p in L.HEADER_PATHS))
+    assert len(L.parse_headers()) == 172 + 3 + 6 + 3
     dup = tmp_path / 'dup.h'
     dup.write_text('int nero_fresh(int n);\nint nero_version(void);\n')
     with pytest.raises(ImportError, match='nero_version'):
