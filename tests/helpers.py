@@ -210,11 +210,13 @@ def assert_grads_small_batch(g_hip, g32, g64, where='', info=None, tol=1e-4, out
     assert not bad, f'{where}: per failing tensor: {bad}'
 
 
-def parity_report(test_id, **fields):
+def parity_report(test_id, file=None, **fields):
     """append one record to gpurun_out/parity_at_size.json (merged back from the GPU box by gpurun): what size a test REALLY ran at,
     how many razor-edge rays / escape clauses it needed -- `pytest -q` hides prints, this file does not"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(root, 'gpurun_out', 'parity_at_size.json')
+    if file is not None:                                 # another report in the same directory (tests/test_chain_kernels_gpu.py: chain_fp64.json)
+        path = os.path.join(os.path.dirname(path), file)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     try:
         with open(path) as f:
