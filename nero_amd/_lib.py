@@ -12,6 +12,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip.h')
 # every public header of the library, in the order the build lists them; an entry point is declared in exactly one of them
 HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h)
                      for h in ('nero_hip.h', 'nero_hip_visibility.h', 'nero_hip_relight.h', 'nero_hip_surface.h'))
+# headers added after the tests of the four above pinned their number and their prototype counts: bound by _load() like those, and held to
+# the same rule (a name is declared once across ALL headers); parse_headers() and bind() keep HEADER_PATHS as their default
+LATER_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_envsample.h',))
 
 MAX_LAYERS = 10
 HID = 256
@@ -132,10 +135,10 @@ def parse_headers(paths=None):
     return sigs
 
 
-def bind(lib):
-    """set restype and argtypes of EVERY entry point the headers (HEADER_PATHS) declare on `lib` (a CDLL of libnero_hip.so): a header is the one
-    place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call site hands over"""
-    for fn, (restype, argtypes, header) in parse_headers().items():
+def bind(lib, paths=None):
+    """set restype and argtypes of EVERY entry point the headers (`paths`, default HEADER_PATHS) declare on `lib` (a CDLL of libnero_hip.so): a
+    header is the one place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call site hands over"""
+    for fn, (restype, argtypes, header) in parse_headers(paths).items():
         try:
             f = getattr(lib, fn)
         except AttributeError:
@@ -148,7 +151,7 @@ def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    return bind(C.CDLL(LIB_PATH))
+    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
 
 
 lib = _load()

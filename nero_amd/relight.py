@@ -6,6 +6,10 @@ nero_bvh_relight evaluates the reference's shade_mixed estimator with "environme
 blocked" for the light -- one fused kernel that never stores a ray.  NOT modelled: inter-reflection (a blocked direction is black), texture
 maps as input, smooth normals unless the caller supplies per-vertex ones.  This is not Cycles.
 
+samples = (Dd, Ds) draws every direction from the BRDF; samples = (Dd, Ds, Dl) adds Dl directions drawn from the map itself (light_table,
+nero_env_cdf) and weighs all of them by one mixture density in nero_bvh_relight_mis (include/nero_hip_envsample.h): the
+same expectation, far less noise under a map with a sun or a lamp in it.
+
 ROUGHNESS: extract_materials.py stores -- and predict_materials_of_vertices returns -- the PERCEPTUAL roughness (the square root of what
 the network predicts); the estimator takes alpha = roughness^2.  Everything here carries the perceptual value, as a renderer's vertex
 attribute would, and estimator_materials() below squares it: the one place."""
@@ -134,8 +138,19 @@ def pixel_rotations(index, seed):
     return (h1 >> 8).float() * 2.0 ** -24, (h2 >> 8).float() * 2.0 ** -24
 
 
-def padded_samples(Dd, Ds):
-    return (Dd + Ds + 63) // 64 * 64
+def pixel_shifts(index, seed):
+    """the two shifts in [0,1) of a pixel's light samples: two more hashes chained after pixel_rotations' h2 by the same step, h3 =
+    lowbias32(h2 + 0x68E31DA4), h4 = lowbias32(h3 + 0x68E31DA4), s = (h >> 8) 2^-24 -> [n,2] float32.  index: int64 tensor"""
+    m = 0xffffffff
+    h1 = _lowbias32((index.long() * 0x9E3779B9 + (int(seed) & m)) & m)
+    h2 = _lowbias32((h1 + 0x68E31DA4) & m)
+    h3 = _lowbias32((h2 + 0x68E31DA4) & m)
+    h4 = _lowbias32((h3 + 0x68E31DA4) & m)
+    return torch.stack([(h3 >> 8).float() * 2.0 ** -24, (h4 >> 8).float() * 2.0 ** -24], -1)
+
+
+def padded_samples(Dd, Ds, Dl=0):
+    return (Dd + Ds + Dl + 63) // 64 * 64
 
 
 # ---- thin wrappers of the entry points ------------------------------------------------------------------------------------------------------
@@ -190,9 +205,59 @@ def relight_rays(pt, tab_d, tab_s, geometry_type=0):
     return ro, rd, dead
 
 
-def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=None, geometry_type=0, chunk=None):
+class LightTable:
+    """the sampling table of one map under one convention, rotation and cap (nero_env_cdf): cdf [gh gw] int64, info [5] int64 = (total,
+    zero-weight cells, e, B, fallback), both on the device; weights [gh gw] float32 when asked for"""
+
+    def __init__(self, cdf, info, gh, gw, weights=None):
+        self.cdf, self.info, self.gh, self.gw, self.weights = cdf, info, int(gh), int(gw), weights
+
+
+def light_table(env, convention=2, rot=None, clamp=None, weights=False):
+    """env [h,w,3] CUDA -> LightTable: luminance x cos(elevation) per cell of an h x w equirectangular grid in world directions, as integer
+    weights and their running sum (include/nero_hip_envsample.h)"""
+    env = env.float().contiguous()
+    gh, gw = int(env.shape[0]), int(env.shape[1])
+    dev = env.device
+    with torch.cuda.device(dev):
+        need = int(_lib.nero_env_cdf_workspace_bytes(gh, gw))
+        if need == 0:
+            raise L.NeroHipError(_lib.nero_last_error().decode())
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        cdf = torch.empty(gh * gw, dtype=torch.int64, device=dev)
+        info = torch.empty(5, dtype=torch.int64, device=dev)
+        wts = torch.empty(gh * gw, dtype=torch.float32, device=dev) if weights else None
+        L.check(_lib.nero_env_cdf(L.ptr(env), gh, gw, int(CONVENTIONS.get(convention, convention)), _rot_arg(rot), float(clamp or 0.0), L.ptr(ws),
+                                  L.ptr(cdf), L.ptr(info), L.ptr(wts), L.stream_ptr()))
+    return LightTable(cdf, info, gh, gw, wts)
+
+
+def relight_mis_rays(pt, tab_d, tab_s, tab_l, table, rand_l=None, geometry_type=0):
+    """the sample set of the three strategies (nero_relight_mis_rays) -> rays_o, rays_d [P D,3], dead [P D] uint8, cell [P D] int32,
+    pdf_l [P D]; D = Dd + Ds + Dl, cosine then GGX then light samples"""
+    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0]
+    n = P * (Dd + Ds + Dl)
+    ro = torch.empty(n, 3, dtype=torch.float32, device=pt.device)
+    rd = torch.empty_like(ro)
+    dead = torch.empty(n, dtype=torch.uint8, device=pt.device)
+    cell = torch.empty(n, dtype=torch.int32, device=pt.device)
+    pdf = torch.empty(n, dtype=torch.float32, device=pt.device)
+    rl = None if rand_l is None else rand_l.float().contiguous()
+    with torch.cuda.device(pt.device):
+        L.check(_lib.nero_relight_mis_rays(L.ptr(pt), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l), L.ptr(rl), P, Dd, Ds, Dl, int(geometry_type),
+                                           L.ptr(table.cdf), L.ptr(table.info), table.gh, table.gw, L.ptr(ro), L.ptr(rd), L.ptr(dead),
+                                           L.ptr(cell), L.ptr(pdf), L.stream_ptr()))
+    return ro, rd, dead, cell, pdf
+
+
+def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=None, geometry_type=0, chunk=None, tab_l=None, rand_l=None,
+                   table=None):
     """the fused kernel (nero_bvh_relight) over the point records pt [P,32], in chunks of `chunk` points (None: as many as fit
-    DEFAULT_CHUNK_LANES lanes; always within the per-call limit) -> rgb_lin, diffuse_lin, spec_lin [P,3].  Same bits for every chunk."""
+    DEFAULT_CHUNK_LANES lanes; always within the per-call limit) -> rgb_lin, diffuse_lin, spec_lin [P,3].  Same bits for every chunk.
+    With tab_l [Dl,2]: the MIS kernel (nero_bvh_relight_mis) with Dl light samples per point drawn from `table` (a LightTable of this map,
+    convention, rotation and cap; None: built here), shifted per point by rand_l [P,2] (None: no shift)."""
+    if tab_l is not None:
+        return _relight_points_mis(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk)
     P, Dd, Ds = pt.shape[0], tab_d.shape[0], tab_s.shape[0]
     pad = padded_samples(Dd, Ds)
     most = max(1, MAX_LANES // pad)
@@ -211,6 +276,33 @@ def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=
                                           L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0),
                                           L.ptr(out[0][i:i + n]), L.ptr(out[1][i:i + n]), L.ptr(out[2][i:i + n]), L.ptr(ws), ws.numel(),
                                           L.stream_ptr()))
+    return tuple(out)
+
+
+def _relight_points_mis(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk):
+    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0]
+    pad = padded_samples(Dd, Ds, Dl)
+    most = max(1, MAX_LANES // pad)
+    chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
+    chunk = max(1, min(chunk, most))
+    dev = pt.device
+    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(3)]
+    env = env.float().contiguous()
+    conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
+    if table is None:
+        table = light_table(env, conv, rot, clamp)
+    assert (table.gh, table.gw) == tuple(env.shape[:2]), 'the light table is not this map\'s'
+    rl = None if rand_l is None else rand_l.float().contiguous()
+    with torch.cuda.device(dev):
+        need = int(_lib.nero_relight_mis_workspace_bytes(min(chunk, max(P, 1)), Dd, Ds, Dl))
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+        for i in range(0, P, chunk):
+            n = min(chunk, P - i)
+            L.check(_lib.nero_bvh_relight_mis(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l),
+                                              None if rl is None else L.ptr(rl[i:i + n]), n, Dd, Ds, Dl, int(geometry_type), L.ptr(env),
+                                              env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), L.ptr(table.cdf), L.ptr(table.info),
+                                              L.ptr(out[0][i:i + n]), L.ptr(out[1][i:i + n]), L.ptr(out[2][i:i + n]), L.ptr(ws), ws.numel(),
+                                              L.stream_ptr()))
     return tuple(out)
 
 
@@ -258,6 +350,14 @@ class Relighter:
             env_rotation.detach().cpu().numpy() if torch.is_tensor(env_rotation) else env_rotation, np.float32).reshape(3, 3)
         self.tracer = tracer if tracer is not None else RayTracer(self.verts, self.tris.int(), build=build)
         self._tabs = {}
+        self._light = {}
+
+    def light_table(self, clamp=None):
+        """the map's sampling table under this relighter's convention and rotation, one per cap (the cap changes the weights)"""
+        key = float(clamp or 0.0)
+        if key not in self._light:
+            self._light[key] = light_table(self.env, self.convention, self.rot, clamp)
+        return self._light[key]
 
     def _table(self, n):
         if n not in self._tabs:
@@ -301,8 +401,10 @@ class Relighter:
     def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None):
         """one view -> dict of device tensors [h,w,C]: rgb_lin (linear), rgb (linear_to_srgb, clipped to [0,1]), alpha (coverage), albedo,
         metallic, roughness (perceptual), normal, depth (10 where nothing is hit), and rgba8 uint8 [h,w,4] (straight alpha).  samples = (Dd,
-        Ds) directions per pixel; ssaa = s renders s h x s w and box-filters with premultiplied alpha; chunk: hit pixels per kernel call (any
-        value gives the same bits); clamp: cap on the environment's radiance per channel (firefly control); background: linear rgb [3] or
+        Ds) directions per pixel, or (Dd, Ds, Dl) with Dl more drawn from the map itself and all three combined by multiple importance
+        sampling (same expectation, far less noise under a map with a sun or a lamp in it); ssaa = s renders s h x s w
+        and box-filters with premultiplied alpha; chunk: hit pixels per kernel call (any value gives the same bits); clamp: cap on the
+        environment's radiance per channel (firefly control; it darkens the picture, the third sample count does not); background: linear rgb [3] or
         [h,w,3] behind the uncovered part of a pixel (None: zeros there, rgb_lin is the straight colour)."""
         s = int(ssaa)
         assert s >= 1
@@ -312,13 +414,17 @@ class Relighter:
             rays_o, rays_d = self.camera_rays(pose, Ks, H, W)
             sf = self.surface(rays_o, rays_d)
             idx, m = sf['idx'], int(sf['idx'].numel())
+            if len(samples) not in (2, 3):
+                raise ValueError(f'samples {samples!r}: (Dd, Ds) or (Dd, Ds, Dl)')
             Dd, Ds = int(samples[0]), int(samples[1])
             rgb = torch.zeros(H * W, 3, device=self.device)
             if m > 0:
                 rand_d, rand_s = pixel_rotations(idx, seed)
                 pt = point_records(sf['pts'], -rays_d[idx], sf['normal'], estimator_materials(sf['mat5']), rand_d, rand_s)
+                mis = {} if len(samples) == 2 else dict(tab_l=self._table(int(samples[2])), rand_l=pixel_shifts(idx, seed),
+                                                        table=self.light_table(clamp))
                 rgb[idx] = relight_points(self.tracer, pt, self._table(Dd), self._table(Ds), self.env, self.convention, self.rot, clamp,
-                                          self.geometry_type, chunk)[0]
+                                          self.geometry_type, chunk, **mis)[0]
             alpha = sf['hit'].float().reshape(H * W, 1)
             full = lambda x: torch.zeros(H * W, x.shape[1], device=self.device).index_copy_(0, idx, x)
             planes = torch.cat([rgb, full(sf['mat5']), full(sf['normal']), (sf['depth'].reshape(-1, 1) * alpha), alpha], -1)    # premultiplied
