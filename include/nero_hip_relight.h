@@ -2,7 +2,8 @@
  *
  * Direct lighting with shadows: the reference's shade_mixed estimator (GGX distribution, Schlick-GGX or height-correlated Smith geometry
  * term, Schlick Fresnel, cosine-weighted + GGX importance sampling) in which the light a direction fetches is "the environment's radiance
- * if the shadow ray is free, zero if it is blocked".  No inter-reflection: a blocked direction contributes nothing.
+ * if the shadow ray is free, zero if it is blocked".  No inter-reflection here: a blocked direction contributes nothing (nero_hip_bounce.h
+ * has the siblings of nero_bvh_relight that give it one bounce).
  *
  * Conventions are those of nero_hip.h and nero_hip_visibility.h: device pointers to fp32 (int32 / bytes where stated), rays and points as
  * [n,3] rows, every call asynchronous on `stream` (a hipStream_t passed as void*), 0 on success or a negative NERO_ERR_* code with a message

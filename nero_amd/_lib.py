@@ -15,6 +15,8 @@ HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h)
 # headers added after the tests of the four above pinned their number and their prototype counts: bound by _load() like those, and held to
 # the same rule (a name is declared once across ALL headers); parse_headers() and bind() keep HEADER_PATHS as their default
 LATER_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_envsample.h',))
+# ... and those added after the tests of the fifth pinned that tuple too: the same rule once more
+BOUNCE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_bounce.h',))
 
 MAX_LAYERS = 10
 HID = 256
@@ -151,7 +153,7 @@ def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
+    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
 
 
 lib = _load()

@@ -28,21 +28,7 @@ using namespace nero_bvh;
 using namespace nero_relight;              // relight_plan.h (samples_ok, total_ok, waves_per_point, workspace_bytes, grid_blocks), relight_dev.h
 constexpr int PRIV_THREADS = 256;          // workgroup of the private-stack kernels (as trace_kernel)
 
-// ---- closest hit with the face ----------------------------------------------------------------------------------------------------------
-// (u, v) of tri_test on triangle `best`: the same operations in the same order
-__device__ __forceinline__ void hit_bary(const Tri* __restrict__ tris, int best, const float* o, const float* d, float& u, float& v) {
-#pragma clang fp contract(off)
-    const TriQ q = load_tri(tris, best);
-    const float v0[3] = {q.a.x, q.a.y, q.a.z}, e1[3] = {q.a.w, q.b.x, q.b.y}, e2[3] = {q.b.z, q.b.w, q.c.x};
-    const float px = cross_c(d[1], e2[2], d[2], e2[1]), py = cross_c(d[2], e2[0], d[0], e2[2]), pz = cross_c(d[0], e2[1], d[1], e2[0]);
-    const float det = dot3(e1[0], e1[1], e1[2], px, py, pz);
-    const float inv = 1.0f / det;
-    const float tx = o[0] - v0[0], ty = o[1] - v0[1], tz = o[2] - v0[2];
-    u = dot3(tx, ty, tz, px, py, pz) * inv;
-    const float qx = cross_c(ty, e1[2], tz, e1[1]), qy = cross_c(tz, e1[0], tx, e1[2]), qz = cross_c(tx, e1[1], ty, e1[0]);
-    v = dot3(d[0], d[1], d[2], qx, qy, qz) * inv;
-}
-
+// ---- closest hit with the face (hit_bary: relight_dev.h) --------------------------------------------------------------------------------
 // OVERLAP: PL_THREADS threads and the LDS stack (trees no deeper than PL_STACK), else PRIV_THREADS threads and the private stack
 template <bool OVERLAP>
 __global__ __launch_bounds__(OVERLAP ? PL_THREADS : PRIV_THREADS) void trace_faces_kernel(
@@ -102,7 +88,7 @@ __global__ __launch_bounds__(256) void relight_rays_kernel(const float* __restri
     if (dead) dead[row] = dd ? 1 : 0;
 }
 
-// ---- the estimator (brdf_weight, the any-hit walk: relight_dev.h) -----------------------------------------------------------------------
+// ---- the estimator (brdf_weight, two_strategy_terms, the any-hit walk: relight_dev.h) -----------------------------------------------------------------------
 // One lane per (point, sample): wavefront W of the grid is chunk W % wpp of point W / wpp, lane l its sample (W % wpp) 64 + l; samples at or
 // past D are padding.  partial [P wpp, 6]: the wavefront's sums of the diffuse and the specular terms, added by a shuffle butterfly (the same
 // order on every run).
@@ -126,17 +112,9 @@ __global__ __launch_bounds__(OVERLAP ? PL_THREADS : PRIV_THREADS) void relight_k
         const bool dead = relight_ray(q, tab_d, tab_s, j, Dd, geom, d, o);
         NERO_RELIGHT_ANY_HIT(blocked, MISS_DEPTH, dead ? NONE : root)
         if (!dead && !blocked) {
-            float L[3], W, fc;
+            float L[3];
             env_sample(E, d, L);
-            brdf_weight(q, d, j < Dd, (float)Dd / (float)D, (float)Ds / (float)D, geom, W, fc);
-            const float m = q[9];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float F0 = 0.04f * (1.f - m) + m * q[11 + c];
-                const float Fr = F0 + (1.f - F0) * fc;
-                spec[c] = Fr * L[c] * W;
-                if (j < Dd) diff[c] = q[11 + c] * (1.f - m) * L[c];
-            }
+            two_strategy_terms(q, d, j, Dd, Ds, geom, L, diff, spec);
         }
     }
 #pragma unroll

@@ -1,5 +1,6 @@
 // relight_dev.h -- the device functions and argument checks that relight.hip and envsample.hip share: the environment lookup (env_sample),
-// the sample set of the two BRDF strategies (relight_ray), the estimator's weight (brdf_weight) and the any-hit expansion of the BVH walks.
+// the sample set of the two BRDF strategies (relight_ray), the estimator's weight (brdf_weight) and per-sample terms (two_strategy_terms),
+// the hit's (u, v) (hit_bary) and the any-hit expansion of the BVH walks -- shared with relight_bounce.hip too.
 // One definition each, so that the two-strategy kernels and the MIS kernels form the same directions and read the same radiance bit for bit.
 // Include after bvh_walk.h, common.h, relight_plan.h and shade_math.h.
 #pragma once
@@ -140,6 +141,39 @@ __device__ __forceinline__ void brdf_weight(const float* q, const float* w, bool
     const float dg = a2 / (PI_F * t * t + 1e-4f);
     const float prob = diffuse ? nol / PI_F * wd : dg * noh / (4.f * hov + 1e-5f) * ws;
     W = dg * G / (4.f * nov * prob + 1e-5f);
+}
+
+// one sample's diffuse and specular terms for the radiance L it fetched: what relight_kernel adds up (a cosine sample alone carries a
+// diffuse term).  Not under a contraction pragma, as the kernel's body never was.
+__device__ __forceinline__ void two_strategy_terms(const float* q, const float* d, int j, int Dd, int Ds, int geom, const float* L, float* diff,
+                                                   float* spec) {
+    const int D = Dd + Ds;
+    float W, fc;
+    brdf_weight(q, d, j < Dd, (float)Dd / (float)D, (float)Ds / (float)D, geom, W, fc);
+    const float m = q[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float F0 = 0.04f * (1.f - m) + m * q[11 + c];
+        const float Fr = F0 + (1.f - F0) * fc;
+        spec[c] = Fr * L[c] * W;
+        if (j < Dd) diff[c] = q[11 + c] * (1.f - m) * L[c];
+    }
+}
+
+// ---- closest hit with the face ----------------------------------------------------------------------------------------------------------
+// (u, v) of tri_test on triangle `best`: the same operations in the same order
+__device__ __forceinline__ void hit_bary(const nero_bvh::Tri* __restrict__ tris, int best, const float* o, const float* d, float& u, float& v) {
+#pragma clang fp contract(off)
+    using nero_bvh::cross_c; using nero_bvh::dot3;
+    const nero_bvh::TriQ q = nero_bvh::load_tri(tris, best);
+    const float v0[3] = {q.a.x, q.a.y, q.a.z}, e1[3] = {q.a.w, q.b.x, q.b.y}, e2[3] = {q.b.z, q.b.w, q.c.x};
+    const float px = cross_c(d[1], e2[2], d[2], e2[1]), py = cross_c(d[2], e2[0], d[0], e2[2]), pz = cross_c(d[0], e2[1], d[1], e2[0]);
+    const float det = dot3(e1[0], e1[1], e1[2], px, py, pz);
+    const float inv = 1.0f / det;
+    const float tx = o[0] - v0[0], ty = o[1] - v0[1], tz = o[2] - v0[2];
+    u = dot3(tx, ty, tz, px, py, pz) * inv;
+    const float qx = cross_c(ty, e1[2], tz, e1[1]), qy = cross_c(tz, e1[0], tx, e1[2]), qz = cross_c(tx, e1[1], ty, e1[0]);
+    v = dot3(d[0], d[1], d[2], qx, qy, qz) * inv;
 }
 
 // bool HIT = does the ray (o, d) meet a triangle nearer than TMAX: the any-hit expansion of the walk that the kernel's OVERLAP selects (the

@@ -3,8 +3,10 @@ direct lighting with shadows on the mesh tracer's BVH (include/nero_hip_relight.
 
 Camera rays go through nero_bvh_trace_faces (depth, face, barycentrics), the per-vertex materials are interpolated at the hits, and
 nero_bvh_relight evaluates the reference's shade_mixed estimator with "environment radiance if the shadow ray is free, zero if it is
-blocked" for the light -- one fused kernel that never stores a ray.  NOT modelled: inter-reflection (a blocked direction is black), texture
-maps as input, smooth normals unless the caller supplies per-vertex ones.  This is not Cycles.
+blocked" for the light -- one fused kernel that never stores a ray.  With bounces=1 a blocked direction is not black: it fetches the light
+the surface it meets sends back under its own direct lighting (one bounce, one sample, a shadow ray of its own; include/nero_hip_bounce.h,
+DESIGN.md 9.12.2).  NOT modelled: more than one bounce, texture maps as input, smooth normals unless the caller supplies per-vertex ones.
+This is not Cycles.
 
 samples = (Dd, Ds) draws every direction from the BRDF; samples = (Dd, Ds, Dl) adds Dl directions drawn from the map itself (light_table,
 nero_env_cdf) and weighs all of them by one mixture density in nero_bvh_relight_mis (include/nero_hip_envsample.h): the
@@ -149,6 +151,17 @@ def pixel_shifts(index, seed):
     return torch.stack([(h3 >> 8).float() * 2.0 ** -24, (h4 >> 8).float() * 2.0 ** -24], -1)
 
 
+def pixel_keys(index, seed):
+    """the key of a pixel's bounces: one more hash chained after pixel_shifts' h4 by the same step, h5 = lowbias32(h4 + 0x68E31DA4) -> [n]
+    int64 in [0, 2^32) (relight_points sends it as uint32).  The variates of sample j's bounce are hashes of (key, j): a function of (pixel,
+    seed, j) alone, so the same for every chunking.  index: int64 tensor"""
+    m = 0xffffffff
+    h = _lowbias32((index.long() * 0x9E3779B9 + (int(seed) & m)) & m)
+    for _ in range(4):
+        h = _lowbias32((h + 0x68E31DA4) & m)
+    return h
+
+
 def padded_samples(Dd, Ds, Dl=0):
     return (Dd + Ds + Dl + 63) // 64 * 64
 
@@ -250,12 +263,104 @@ def relight_mis_rays(pt, tab_d, tab_s, tab_l, table, rand_l=None, geometry_type=
     return ro, rd, dead, cell, pdf
 
 
+def _mesh_args(mesh, dev):
+    """(verts, tris int32, mat5 PERCEPTUAL, normals | None) -> contiguous device tensors of the types the bounce entry points read"""
+    if mesh is None or len(mesh) != 4:
+        raise ValueError('bounces=1 needs mesh=(verts [V,3], tris [T,3] int32, mat5 [V,5] with the perceptual roughness, normals [V,3] or None)')
+    verts, tris, mat5, normals = mesh
+    verts, mat5 = verts.to(dev, torch.float32).contiguous(), mat5.to(dev, torch.float32).contiguous()
+    tris = tris.to(dev, torch.int32).contiguous()
+    normals = None if normals is None else normals.to(dev, torch.float32).contiguous()
+    assert verts.ndim == 2 and verts.shape[1] == 3 and tris.ndim == 2 and tris.shape[1] == 3 and tuple(mat5.shape) == (verts.shape[0], 5)
+    assert normals is None or normals.shape == verts.shape
+    return verts, tris, mat5, normals
+
+
+def _key_arg(key, P, dev):
+    """[P] integers in [0, 2^32) -> the same bits as int32 on the device (read as uint32), or None"""
+    if key is None:
+        return None
+    k = key.to(dev).long() & 0xffffffff
+    assert k.shape == (P,), k.shape
+    return torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32).contiguous()
+
+
+def relight_bounce_rays(tracer, pt, tab_d, tab_s, mesh, key=None, geometry_type=0, tab_l=None, rand_l=None, table=None):
+    """what every lane of the bounce kernels decides (nero_relight_bounce_rays) -> dict: state [P D] uint8 (0 free, 1 dead, 2 bounced, 3
+    bounced with a dead secondary sample, 4 bad face), face [P D] int32, bary [P D,2], sec_o, sec_d [P D,3], strategy [P D] int32, pdf_l
+    [P D], cell [P D] int32.  tab_l and table: the MIS variant"""
+    dev = pt.device
+    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], 0 if tab_l is None else tab_l.shape[0]
+    n = P * (Dd + Ds + Dl)
+    verts, tris, mat5, normals = _mesh_args(mesh, dev)
+    kk = _key_arg(key, P, dev)
+    out = {'state': torch.empty(n, dtype=torch.uint8, device=dev), 'face': torch.empty(n, dtype=torch.int32, device=dev),
+           'bary': torch.empty(n, 2, dtype=torch.float32, device=dev), 'sec_o': torch.empty(n, 3, dtype=torch.float32, device=dev),
+           'sec_d': torch.empty(n, 3, dtype=torch.float32, device=dev), 'strategy': torch.empty(n, dtype=torch.int32, device=dev),
+           'pdf_l': torch.empty(n, dtype=torch.float32, device=dev), 'cell': torch.empty(n, dtype=torch.int32, device=dev)}
+    rl = None if rand_l is None else rand_l.float().contiguous()
+    tl = (None, None, 1, 1) if tab_l is None else (L.ptr(table.cdf), L.ptr(table.info), table.gh, table.gw)
+    with torch.cuda.device(dev):
+        L.check(_lib.nero_relight_bounce_rays(tracer._handle(), L.ptr(pt), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l), L.ptr(rl), P, Dd, Ds, Dl,
+                                              int(geometry_type), *tl, L.ptr(verts), verts.shape[0], L.ptr(tris), tris.shape[0], L.ptr(mat5),
+                                              L.ptr(normals), L.ptr(kk), *[L.ptr(out[k]) for k in ('state', 'face', 'bary', 'sec_o', 'sec_d',
+                                                                                                   'strategy', 'pdf_l', 'cell')], L.stream_ptr()))
+    return out
+
+
+def _relight_points_bounce(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, mesh, key):
+    """-> rgb_lin, diffuse_lin, spec_lin, indirect_lin [P,3] (nero_bvh_relight_bounce / nero_bvh_relight_mis_bounce)"""
+    mis = tab_l is not None
+    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0] if mis else 0
+    pad = padded_samples(Dd, Ds, Dl)
+    most = max(1, MAX_LANES // pad)
+    chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
+    chunk = max(1, min(chunk, most))
+    dev = pt.device
+    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(4)]
+    env = env.float().contiguous()
+    conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
+    verts, tris, mat5, normals = _mesh_args(mesh, dev)
+    kk = _key_arg(key, P, dev)
+    if mis and table is None:
+        table = light_table(env, conv, rot, clamp)
+    if mis:
+        assert (table.gh, table.gw) == tuple(env.shape[:2]), 'the light table is not this map\'s'
+    rl = None if rand_l is None else rand_l.float().contiguous()
+    mesh_args = (L.ptr(verts), verts.shape[0], L.ptr(tris), tris.shape[0], L.ptr(mat5), L.ptr(normals))
+    with torch.cuda.device(dev):
+        n0 = min(chunk, max(P, 1))
+        need = int(_lib.nero_relight_mis_bounce_workspace_bytes(n0, Dd, Ds, Dl) if mis else _lib.nero_relight_bounce_workspace_bytes(n0, Dd, Ds))
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+        for i in range(0, P, chunk):
+            n = min(chunk, P - i)
+            outs = [L.ptr(o[i:i + n]) for o in out]
+            kp = None if kk is None else L.ptr(kk[i:i + n])
+            if mis:
+                L.check(_lib.nero_bvh_relight_mis_bounce(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l),
+                                                         None if rl is None else L.ptr(rl[i:i + n]), n, Dd, Ds, Dl, int(geometry_type), L.ptr(env),
+                                                         env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), L.ptr(table.cdf),
+                                                         L.ptr(table.info), *mesh_args, kp, *outs, L.ptr(ws), ws.numel(), L.stream_ptr()))
+            else:
+                L.check(_lib.nero_bvh_relight_bounce(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), n, Dd, Ds, int(geometry_type),
+                                                     L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), *mesh_args, kp,
+                                                     *outs, L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return tuple(out)
+
+
 def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=None, geometry_type=0, chunk=None, tab_l=None, rand_l=None,
-                   table=None):
+                   table=None, bounces=0, mesh=None, key=None):
     """the fused kernel (nero_bvh_relight) over the point records pt [P,32], in chunks of `chunk` points (None: as many as fit
     DEFAULT_CHUNK_LANES lanes; always within the per-call limit) -> rgb_lin, diffuse_lin, spec_lin [P,3].  Same bits for every chunk.
     With tab_l [Dl,2]: the MIS kernel (nero_bvh_relight_mis) with Dl light samples per point drawn from `table` (a LightTable of this map,
-    convention, rotation and cap; None: built here), shifted per point by rand_l [P,2] (None: no shift)."""
+    convention, rotation and cap; None: built here), shifted per point by rand_l [P,2] (None: no shift).
+    bounces=1: the bounce kernels (nero_bvh_relight_bounce / nero_bvh_relight_mis_bounce) over mesh = (verts [V,3], tris [T,3] int32, mat5
+    [V,5] with the PERCEPTUAL roughness, normals [V,3] or None) -- the arrays the tracer's tree was built from -- with key [P] (pixel_keys;
+    None: zeros) seeding each point's bounces -> rgb_lin, diffuse_lin, spec_lin (the direct terms: bounces=0's bits), indirect_lin."""
+    if bounces not in (0, 1):
+        raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
+    if bounces == 1:
+        return _relight_points_bounce(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, mesh, key)
     if tab_l is not None:
         return _relight_points_mis(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk)
     P, Dd, Ds = pt.shape[0], tab_d.shape[0], tab_s.shape[0]
@@ -324,10 +429,10 @@ class Relighter:
     predict_materials_of_vertices); env: linear radiance [h,w,3] (array, tensor) or the path of a Radiance .hdr; convention: 'blender'
     (the equirectangular mapping of an .hdr made for relight.py --hdr), 'nero' / 'nero_real' (this project's env_light grid, is_real = 0 /
     1); env_rotation: 3 x 3, applied to a direction before the lookup; tracer: a RayTracer over the same mesh to share, else one is built
-    (`build`); normals: per-vertex [V,3] for smooth shading, else flat face normals turned towards the camera."""
+    (`build`); normals: per-vertex [V,3] for smooth shading, else flat face normals turned towards the camera; bounces: render()'s default."""
 
     def __init__(self, verts, tris, materials, env, convention='blender', env_rotation=None, tracer=None, build='device',
-                 geometry_type='schlick', normals=None, device=None):
+                 geometry_type='schlick', normals=None, device=None, bounces=0):
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         as_t = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
         self.device = dev
@@ -351,6 +456,9 @@ class Relighter:
         self.tracer = tracer if tracer is not None else RayTracer(self.verts, self.tris.int(), build=build)
         self._tabs = {}
         self._light = {}
+        if bounces not in (0, 1):
+            raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
+        self.bounces = bounces                                          # what render() takes when it is not told
 
     def light_table(self, clamp=None):
         """the map's sampling table under this relighter's convention and rotation, one per cap (the cap changes the weights)"""
@@ -398,14 +506,19 @@ class Relighter:
         nrm = torch.nn.functional.normalize(nrm, dim=-1)
         return {'depth': depth, 'hit': hit, 'idx': idx, 'pts': pts, 'normal': nrm, 'mat5': mat5}
 
-    def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None):
+    def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None, bounces=None):
         """one view -> dict of device tensors [h,w,C]: rgb_lin (linear), rgb (linear_to_srgb, clipped to [0,1]), alpha (coverage), albedo,
         metallic, roughness (perceptual), normal, depth (10 where nothing is hit), and rgba8 uint8 [h,w,4] (straight alpha).  samples = (Dd,
         Ds) directions per pixel, or (Dd, Ds, Dl) with Dl more drawn from the map itself and all three combined by multiple importance
         sampling (same expectation, far less noise under a map with a sun or a lamp in it); ssaa = s renders s h x s w
         and box-filters with premultiplied alpha; chunk: hit pixels per kernel call (any value gives the same bits); clamp: cap on the
         environment's radiance per channel (firefly control; it darkens the picture, the third sample count does not); background: linear rgb [3] or
-        [h,w,3] behind the uncovered part of a pixel (None: zeros there, rgb_lin is the straight colour)."""
+        [h,w,3] behind the uncovered part of a pixel (None: zeros there, rgb_lin is the straight colour); bounces: 0 = direct lighting
+        (None: the relighter's default, 0 unless it was built otherwise), 1 = a blocked direction fetches the light of the surface it meets
+         -- rgb_lin then holds both, and indirect_lin [h,w,3] the bounced part alone, through the same filter."""
+        bounces = self.bounces if bounces is None else bounces
+        if bounces not in (0, 1):
+            raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
         s = int(ssaa)
         assert s >= 1
         H, W = s * h, s * w
@@ -418,13 +531,19 @@ class Relighter:
                 raise ValueError(f'samples {samples!r}: (Dd, Ds) or (Dd, Ds, Dl)')
             Dd, Ds = int(samples[0]), int(samples[1])
             rgb = torch.zeros(H * W, 3, device=self.device)
+            ind = torch.zeros(H * W, 3, device=self.device) if bounces else None
             if m > 0:
                 rand_d, rand_s = pixel_rotations(idx, seed)
                 pt = point_records(sf['pts'], -rays_d[idx], sf['normal'], estimator_materials(sf['mat5']), rand_d, rand_s)
                 mis = {} if len(samples) == 2 else dict(tab_l=self._table(int(samples[2])), rand_l=pixel_shifts(idx, seed),
                                                         table=self.light_table(clamp))
-                rgb[idx] = relight_points(self.tracer, pt, self._table(Dd), self._table(Ds), self.env, self.convention, self.rot, clamp,
-                                          self.geometry_type, chunk, **mis)[0]
+                if bounces:
+                    mis.update(bounces=1, mesh=(self.verts, self.tris.int(), self.mat5, self.normals), key=pixel_keys(idx, seed))
+                got = relight_points(self.tracer, pt, self._table(Dd), self._table(Ds), self.env, self.convention, self.rot, clamp,
+                                     self.geometry_type, chunk, **mis)
+                rgb[idx] = got[0]
+                if bounces:
+                    ind[idx] = got[3]
             alpha = sf['hit'].float().reshape(H * W, 1)
             full = lambda x: torch.zeros(H * W, x.shape[1], device=self.device).index_copy_(0, idx, x)
             planes = torch.cat([rgb, full(sf['mat5']), full(sf['normal']), (sf['depth'].reshape(-1, 1) * alpha), alpha], -1)    # premultiplied
@@ -440,7 +559,11 @@ class Relighter:
             rgba8 = torch.round(torch.cat([srgb, a], -1) * 255.0).to(torch.uint8)
             nrm = torch.nn.functional.normalize(straight[..., 8:11], dim=-1)
             depth = torch.where(a > 0, straight[..., 11:12], torch.full_like(a, MISS_DEPTH))
-        return {'rgb_lin': rgb_lin, 'rgb': srgb, 'alpha': a, 'albedo': straight[..., 5:8], 'metallic': straight[..., 3:4],
+            extra = {}
+            if bounces:                                                   # the same box filter and the same straightening as rgb_lin's
+                ip = ind.reshape(h, s, w, s, 3).mean((1, 3))
+                extra['indirect_lin'] = torch.where(a > 0, ip / torch.clamp(a, min=1e-12), torch.zeros_like(ip))
+        return {**extra, 'rgb_lin': rgb_lin, 'rgb': srgb, 'alpha': a, 'albedo': straight[..., 5:8], 'metallic': straight[..., 3:4],
                 'roughness': straight[..., 4:5], 'normal': nrm, 'depth': depth, 'rgba8': rgba8}
 
     def render_orbit(self, out_dir, num=360, azimuth=0.0, elevation=30.0, dist=3.0, h=800, w=800, K=None, **kw):

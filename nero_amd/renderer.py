@@ -814,15 +814,16 @@ class NeROMaterialRenderer(nn.Module):
         from .texture import bake_materials
         return bake_materials(self, **kw)
 
-    def relight(self, env, **kw):
+    def relight(self, env, bounces=0, **kw):
         """a nero_amd.relight.Relighter over self.ray_tracer's mesh (and its tree) with predict_materials_of_vertices as the materials:
         relight(env).render(pose, K, h, w) / .render_orbit(out_dir) is relight.py without Blender -- direct lighting with shadows under the
-        lat-long map `env` (array, tensor or .hdr path).  kw: convention, env_rotation, normals (Relighter)."""
+        lat-long map `env` (array, tensor or .hdr path); bounces=1: with one inter-reflection, as the default of every render().  kw:
+        convention, env_rotation, normals (Relighter)."""
         from .relight import Relighter
         dev = next(self.parameters()).device
         verts = torch.from_numpy(self.ray_tracer._v).to(dev)
         kw.setdefault('geometry_type', self.shader_network.cfg['geometry_type'])
-        return Relighter(verts, self.ray_tracer._f, self.predict_materials_of_vertices(verts), env, tracer=self.ray_tracer, device=dev, **kw)
+        return Relighter(verts, self.ray_tracer._f, self.predict_materials_of_vertices(verts), env, tracer=self.ray_tracer, device=dev, bounces=bounces, **kw)
 
     def env_light(self, h, w, gamma=True, chunk=None):
         """MCShadingNetwork.env_light (network/field.py:1020-1047): the estimated illumination as an h x w lat-long panorama, float32 [h, w, 3]

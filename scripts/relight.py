@@ -1,5 +1,5 @@
 """Relight a Stage-I mesh with its Stage-II materials under an HDR environment map, on the GPU: the reference's relight.py without Blender
-(nero_amd.relight; direct lighting with shadows, no inter-reflection -- DESIGN.md 9.12).
+(nero_amd.relight; direct lighting with shadows, and with --bounces 1 one inter-reflection -- DESIGN.md 9.12, 9.12.2).
 
     python scripts/relight.py --mesh M.ply --material DIR --hdr E.hdr --name N
     python scripts/relight.py --mesh M.ply --cfg configs/material/x.yaml --model model.pth --hdr E.hdr --name N
@@ -39,6 +39,8 @@ def main(argv=None):
     ap.add_argument('--clamp', type=float, default=None, help="cap on the environment's radiance per channel (firefly control)")
     ap.add_argument('--convention', default='blender', choices=['blender', 'nero', 'nero_real'],
                     help="how the map is laid out: Blender's equirectangular image, or this project's env_light grid (is_real 0 / 1)")
+    ap.add_argument('--bounces', type=int, default=0, choices=[0, 1],
+                    help='1: a direction that meets the mesh fetches the light that surface sends back (one inter-reflection) instead of black')
     ap.add_argument('--out', default='data/relight')
     a = ap.parse_args(argv)
 
@@ -71,8 +73,8 @@ def main(argv=None):
     rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention)
     out_dir = os.path.join(a.out, a.name)
     paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
-                            samples=samples, ssaa=a.ssaa, clamp=a.clamp)
-    print(f'{len(paths)} views of {a.width} x {a.height} at {"+".join(str(n) for n in samples)} samples -> {out_dir}')
+                            samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces)
+    print(f'{len(paths)} views of {a.width} x {a.height} at {"+".join(str(n) for n in samples)} samples, {a.bounces} bounces -> {out_dir}')
 
 
 if __name__ == '__main__':
