@@ -72,7 +72,10 @@ struct Builder {
 };
 
 // box_hit, tri_test, the leaf loaders and the text of the two walks are in bvh_walk.h (shared with the any-hit kernels of visibility.hip);
-// the kernels below expand the walks with ANY = false
+// the kernels below expand the walks with ANY = false.  The contract of a walk: what tri_test returns when it is run over every triangle.
+// box_hit therefore tests the box grown by BOX_PAD (2^-18) on every side -- rays through vertices and edges pass the corners of boxes within
+// rounding, and a ray with a zero direction component can run in the plane of a box face (bvh_walk.h has the derivation; the float32 model
+// of the walk in oracle/csrc/tracer_oracle.c is held to exhaustive search on such rays, and these kernels to the model bit for bit).
 __device__ __forceinline__ void write_hit(const Tri* __restrict__ tris, int r, const float* o, const float* d, float tbest, int best,
                                           float* __restrict__ pos, float* __restrict__ nrm, float* __restrict__ depth) {
 #pragma clang fp contract(off)

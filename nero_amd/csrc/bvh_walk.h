@@ -15,11 +15,30 @@
 
 namespace nero_bvh {
 
+// The slab test, over the box GROWN BY BOX_PAD on every side.  The contract of the walks is that they return what tri_test returns when it is run
+// over every triangle, so a box must not be culled while tri_test would accept a triangle inside it -- and the bare test (t0 <= t1 on the
+// rounded slab distances) culled two kinds of such boxes (tests/test_tracer_model_cpu.py):
+//   * a box whose corner or edge the ray passes within rounding: the entry distance on one axis and the exit distance on another are then equal
+//     up to their rounding, in either order (a ray aimed at a mesh vertex is aimed at the corner of the boxes of all triangles around it);
+//   * a box with a face in whose plane the ray runs (direction component 0, origin coordinate equal to the face's: marching-cubes vertices on
+//     grid lines, axis-aligned depth-map cameras): (mx - o) * 1e20 = 0 puts the exit at t = 0, while the box beyond the face is entered.
+// The pad is a length: slab a becomes [mn - PAD, mx + PAD], i.e. its two distances move apart by PAD |inv[a]| each -- one fused multiply-add
+// per distance, ((mn - o) - PAD) inv = fma(mn - o, inv, -PAD inv) whatever the sign of inv.  For a component below 1e-20 (inv = +-1e20) the slab
+// turns into "o within PAD of [mn, mx]", faces included.  Its size, from the rounding of what is compared: a slab distance carries three
+// roundings (the difference, the reciprocal, the product: 3 x 2^-24 relative), which moves the slab by at most 3 x 2^-24 |mn - o| <= 2^-19 for
+// |mn - o| <= 10.6 -- the miss distance bounds every distance that matters; the other 2^-19 is for tri_test, whose accepted point o + tt d may
+// lie that far outside the triangle's own box (its u, v and tt carry the roundings of two cross and three dot products of vectors of length
+// |o - v0|).  The scene is of unit scale with the miss distance 10, as everywhere in the tracer.  What the pad does NOT cover is tri_test
+// accepting a triangle far from where the ray is -- a ray almost in a triangle's plane, a sliver of aspect 1e4: the determinant gate of 1e-20
+// lets quotients of rounding noise through -- no box test can follow that.  Cost: the multiplies become fused multiply-adds.
+constexpr float BOX_PAD = 0x1p-18f;        // 3.8e-6: twice the 2^-19 above
 __device__ __forceinline__ bool box_hit(const float* mn, const float* mx, const float* o, const float* inv, float tbest, float& tn) {
+#pragma clang fp contract(off)
     float t0 = 0.f, t1 = tbest;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        float ta = (mn[a] - o[a]) * inv[a], tb = (mx[a] - o[a]) * inv[a];
+        const float p = BOX_PAD * inv[a];
+        float ta = fmaf(mn[a] - o[a], inv[a], -p), tb = fmaf(mx[a] - o[a], inv[a], p);
         const float lo = fminf(ta, tb), hi = fmaxf(ta, tb);
         t0 = fmaxf(t0, lo);
         t1 = fminf(t1, hi);
@@ -72,7 +91,9 @@ __device__ __forceinline__ void leaf_test(const Tri* __restrict__ tris, int ref,
     }
 }
 
-// the reciprocal direction the box test multiplies by (an axis-parallel ray gets +-1e20)
+// the reciprocal direction the box test multiplies by.  A component of at most 1e-20 (+0, -0, denormals) gets +-1e20: finite, so that a ray IN
+// the plane of a box face gives (mx - o) inv = 0 and not NaN, and large enough that box_hit's padded slab [-(PAD + d) 1e20, (PAD + d) 1e20] is
+// all or nothing against any tbest <= 10 (the kernels of bvh.hip write the same line out)
 __device__ __forceinline__ void ray_inverse(const float* d, float* inv) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) inv[a] = 1.0f / (fabsf(d[a]) > 1e-20f ? d[a] : (d[a] < 0.f ? -1e-20f : 1e-20f));
