@@ -116,6 +116,9 @@ class RayTracer:
         depth = torch.empty(n, dtype=torch.float32, device=rays_o.device)
         if inplace:                      # the kernel reads o/d before it writes: each thread owns its ray
             pass
+        if torch.is_tensor(_skip):       # both masked routes read n bytes at this pointer (an integer device pointer is taken as given)
+            assert _skip.dtype == torch.uint8 and _skip.is_cuda and _skip.device == rays_o.device and _skip.numel() == n \
+                and _skip.is_contiguous()
         if _chunks is not None:
             sp = None if _skip is None else (_skip.data_ptr() if torch.is_tensor(_skip) else int(_skip))
             arr = (C.c_int * len(_chunks))(*[int(c) for c in _chunks])
@@ -123,8 +126,6 @@ class RayTracer:
                                                  len(_chunks), positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         elif _skip is not None:
             sp = _skip.data_ptr() if torch.is_tensor(_skip) else int(_skip)
-            if torch.is_tensor(_skip):
-                assert _skip.dtype == torch.uint8 and _skip.is_cuda and _skip.numel() == n and _skip.is_contiguous()
             L.check(L.lib.nero_bvh_trace_masked(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n, sp,
                                                 positions.data_ptr(), face_normals.data_ptr(), depth.data_ptr(), L.stream_ptr()))
         elif _order is not None:

@@ -109,6 +109,7 @@ class NeROShapeRenderer(nn.Module):
         coords = torch.stack([xs + 0.5, ys + 0.5, torch.ones_like(xs, dtype=torch.float32)], -1).reshape(1, h * w, 3).float()
         dirs = coords @ torch.inverse(Ks.to(device)).permute(0, 2, 1)                      # imn, h*w, 3
         self.train_poses = poses.to(device).float()
+        self._cam_centres = None                                  # (recomputed from the new pool's poses at the next train_step)
         self._train_human_poses = self.get_human_coordinate_poses(self.train_poses)   # per IMAGE [imn,3,4]; never overwritten
         self.train_batch = {'dirs': dirs.reshape(-1, 3).contiguous(), 'rgbs': imgs.to(device).reshape(-1, 3).float().contiguous(),
                             'idxs': torch.arange(imn, device=device).repeat_interleave(h * w)}
@@ -123,19 +124,32 @@ class NeROShapeRenderer(nn.Module):
         perm = torch.randperm(self.tbn, device=self.train_batch['dirs'].device)
         self.train_batch = {k: v[perm] for k, v in self.train_batch.items()}
 
-    def _process_ray_batch(self, ray_batch, poses, human_poses_img=None):
-        """world-space rays of a pool slice (network/renderer.py:258-272).  `human_poses_img` [imn,3,4]: the per-image human
-        frames of `poses` when the caller has them cached; computed here otherwise, like the reference does on every call."""
+    @staticmethod
+    def _camera_centres(poses):
+        """-R^T t per IMAGE [imn,3] (network/renderer.py:262-263)"""
+        return (poses[:, :, :3].permute(0, 2, 1) @ -poses[:, :, 3:])[:, :, 0].contiguous()
+
+    def _train_cam_centres(self):
+        """the camera centres of self.train_poses, computed once per pool instead of on every step.  The cache HOLDS the tensor it was
+        computed from and is compared by identity and torch's in-place version counter: an address is no key -- the allocator hands a
+        released pose's address to the next one, with version 0 and the same shape."""
+        poses = self.train_poses
+        cached = getattr(self, '_cam_centres', None)
+        if cached is None or cached[0] is not poses or cached[1] != poses._version:
+            cached = self._cam_centres = (poses, poses._version, self._camera_centres(poses))
+        return cached[2]
+
+    def _process_ray_batch(self, ray_batch, poses, human_poses_img=None, cam_centres=None):
+        """world-space rays of a pool slice (network/renderer.py:258-272).  `human_poses_img` [imn,3,4] / `cam_centres` [imn,3]: the
+        per-image human frames / camera centres of `poses` when the caller holds them for exactly this tensor; computed here otherwise,
+        like the reference does on every call."""
         idxs = ray_batch['idxs']
         if idxs.dim() == 2:
             idxs = idxs[..., 0]                                   # the reference's pools carry idxs as [rn,1]
-        Rm, t = poses[:, :, :3], poses[:, :, 3:]
-        # camera centres per IMAGE: the same -R^T t the reference recomputes for all images on every call; cached while `poses` is unchanged
-        key = (poses.data_ptr(), poses._version, tuple(poses.shape))
-        cached = getattr(self, '_cam_centres', None)
-        if cached is None or cached[0] != key:
-            cached = self._cam_centres = (key, (Rm.permute(0, 2, 1) @ -t)[:, :, 0].contiguous())
-        rays_o = cached[1][idxs]
+        Rm = poses[:, :, :3]
+        if cam_centres is None:
+            cam_centres = self._camera_centres(poses)
+        rays_o = cam_centres[idxs]
         rays_d = (Rm[idxs].permute(0, 2, 1) @ ray_batch['dirs'].unsqueeze(-1))[..., 0]
         rays_d = torch.nn.functional.normalize(rays_d, dim=-1)
         near, far = self._near_far(rays_o, rays_d)
@@ -150,7 +164,7 @@ class NeROShapeRenderer(nn.Module):
         self.train_batch_i += rn
         if self.train_batch_i + rn >= self.tbn:
             self._shuffle_train_batch()
-        rays_o, rays_d, near, far, human_poses = self._process_ray_batch(batch, self.train_poses, self._train_human_poses)
+        rays_o, rays_d, near, far, human_poses = self._process_ray_batch(batch, self.train_poses, self._train_human_poses, self._train_cam_centres())
         kern, drv = self._train_driver(step)
         outputs = self.render(rays_o, rays_d, near, far, human_poses, -1, self.get_anneal_val(step), is_train=True, step=step, _kern=kern, _driver=drv)
         outputs['loss_rgb'] = self.compute_rgb_loss(outputs['ray_rgb'], batch['rgbs'])
@@ -191,6 +205,7 @@ class NeROShapeRenderer(nn.Module):
         coords = torch.stack([xs + 0.5, ys + 0.5, torch.ones_like(xs, dtype=torch.float32)], -1).reshape(h * w, 3).float()
         dirs = coords @ torch.inverse(K)[0].T
         hp_img = self.get_human_coordinate_poses(pose)
+        centre = self._camera_centres(pose)                      # once per view, and held by this call only
         outs = {}
         with torch.no_grad():
             kern = self._kernels()                                # packed ONCE per image (and cached across images), not per chunk
@@ -209,7 +224,7 @@ class NeROShapeRenderer(nn.Module):
                     drv = None
             for i in range(0, h * w, chunk):
                 batch = {'dirs': dirs[i:i + chunk], 'idxs': torch.zeros(min(chunk, h * w - i), dtype=torch.long, device=dev)}
-                ro, rd, near, far, hp = self._process_ray_batch(batch, pose, hp_img)
+                ro, rd, near, far, hp = self._process_ray_batch(batch, pose, hp_img, centre)
                 o = self.render(ro, rd, near, far, hp, 0, 0, is_train=not extras, step=step, _kern=kern, _driver=drv)
                 for k, v in o.items():
                     if not k.startswith('_') and torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == ro.shape[0]:

@@ -229,6 +229,51 @@ def parity_report(test_id, file=None, **fields):
     return path
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# cached state against a fresh run (tests/test_render_sequences_gpu.py, tests/test_driver_reuse_gpu.py, tests/test_host_logic.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def fresh_like(obj, build):
+    """a second object by the same recipe `build()` (which seeds for itself) carrying `obj`'s state_dict: what `obj` would be had it never
+    been called.  The caller runs ONLY the call under test on it and compares with assert_bit_equal."""
+    new = build()
+    dev = next(obj.parameters()).device
+    new.load_state_dict({k: v.detach().clone() for k, v in obj.state_dict().items()}, strict=True)
+    return new.to(dev)
+
+
+def assert_bit_equal(got, want, where=''):
+    """torch.equal over tensors, arrays, numbers and (nested) dicts / sequences of them: two runs of the same kernels on the same operands
+    (fixed-order reductions, no floating-point atomics: tests/test_determinism.py), so there is no tolerance to speak of.  Private entries
+    of a dict (leading underscore: state handles, views of a workspace) are not outputs and are left out."""
+    if isinstance(want, dict):
+        pub = lambda d: sorted(k for k in d if not str(k).startswith('_'))
+        assert pub(got) == pub(want), (where, pub(got), pub(want))
+        for k in pub(want):
+            assert_bit_equal(got[k], want[k], f'{where}[{k!r}]')
+    elif torch.is_tensor(want):
+        assert torch.is_tensor(got) and got.shape == want.shape and got.dtype == want.dtype, (where, getattr(got, 'shape', None), want.shape)
+        a, b = got.detach(), want.detach().to(got.device)
+        assert torch.equal(a, b), f'{where}: {int((a != b).sum())} of {a.numel()} entries differ, max |diff| ' \
+                                  f'{float((a.double() - b.double()).abs().nan_to_num().max()):.3e}'
+    elif isinstance(want, np.ndarray):
+        assert isinstance(got, np.ndarray) and got.shape == want.shape and np.array_equal(got, want), where
+    elif isinstance(want, (list, tuple)):
+        assert len(got) == len(want), where
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert_bit_equal(a, b, f'{where}[{i}]')
+    else:
+        assert got == want, (where, got, want)
+
+
+def centre_bound(pose):
+    """(-R^T t in float64 [3], its component-wise float32 bound [3]) of a world->camera pose [3,4]: each component is a three-term fp32 dot
+    product of exactly representable operands, |fl(c_i) - c_i| <= gamma_3 sum_j |R_ji| |t_j| with gamma_3 = 3u / (1 - 3u), u = 2^-24, rounded
+    up to 4 * 2^-24"""
+    p = np.asarray(pose.detach().cpu().numpy() if torch.is_tensor(pose) else pose, np.float64).reshape(3, 4)
+    Rm, t = p[:, :3], p[:, 3]
+    return -Rm.T @ t, 4.0 * 2.0 ** -24 * (np.abs(Rm).T @ np.abs(t))
+
+
 class CTracer:
     """RayTracer-shaped wrapper over the fp64 brute-force oracle (C restatement), remembering the ambiguity flags"""
 

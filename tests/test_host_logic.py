@@ -56,6 +56,113 @@ def test_process_ray_batch_vs_reference():
     assert torch.equal(hp, hp2)
 
 
+# ---- cached state: the camera centres must follow the pose tensor they are asked for, whatever was asked before -------------
+def _views(n):
+    from nero_amd.synthetic import look_at_pose
+    cams = ([3.0, 0.2, 0.5], [-0.4, 2.6, 1.1], [-1.9, -2.1, 1.6], [0.3, -3.2, -0.8], [2.2, 2.0, 0.4], [-2.8, 0.5, -0.6])
+    return [torch.from_numpy(look_at_pose(np.array(c, dtype=np.float64))) for c in cams[:n]]
+
+
+def _ray_batch(n_img, n=37, seed=4):
+    g = torch.Generator().manual_seed(seed)
+    return {'dirs': torch.randn(n, 3, generator=g), 'idxs': torch.randint(0, n_img, (n,), generator=g)}
+
+
+def _assert_rays_of(got, poses, batch, where):
+    """rays_o within the derived fp32 bound of the float64 centres of `poses` [imn,3,4]; all five outputs equal a fresh renderer's"""
+    from tests.helpers import centre_bound
+    idx = batch['idxs'].numpy()
+    cb = [centre_bound(p) for p in poses]
+    want, bound = np.stack([cb[i][0] for i in idx]), np.stack([cb[i][1] for i in idx])
+    err = np.abs(got[0].numpy().astype(np.float64) - want)
+    assert (err <= bound).all(), (where, float((err / bound).max()))
+    fresh = _shape_net()._process_ray_batch(batch, poses.clone())
+    for a, b, k in zip(got, fresh, ('rays_o', 'rays_d', 'near', 'far', 'human_poses')):
+        assert torch.equal(a, b), (where, k)
+
+
+def test_camera_centres_after_another_pose_at_the_same_address():
+    """A pose tensor whose address, version counter and shape equal those of the previous call's -- what the caching allocator hands out
+    when render_image's [1,3,4] pose is released and the next view allocates its own -- reproduced without the allocator: a DLPack alias
+    shares the memory and has a version counter of its own, so a pose written through it leaves (data_ptr, _version, shape) of the
+    original untouched.  rays_o must be the centre of the pose that is THERE: float64 -R^T t to 4 * 2^-24 * sum_j |R_ji| |t_j| (a
+    three-term fp32 dot product, gamma_3 rounded up; tests.helpers.centre_bound), and every output a fresh renderer's."""
+    from torch.utils.dlpack import from_dlpack, to_dlpack
+    net = _shape_net()
+    P1, P2, P3 = _views(3)
+    batch = _ray_batch(1)
+    A = P1.clone().reshape(1, 3, 4)
+    alias = from_dlpack(to_dlpack(A))
+    key = lambda t: (t.data_ptr(), t._version, tuple(t.shape))
+    k0 = key(A)
+    _assert_rays_of(net._process_ray_batch(batch, A), P1.reshape(1, 3, 4), batch, 'first pose')
+    alias.copy_(P2.reshape(1, 3, 4))
+    assert key(A) == k0 and torch.equal(A[0], P2)                    # same address, same version, same shape -- another camera
+    assert float((P2 - P1).abs().max()) > 0.5
+    _assert_rays_of(net._process_ray_batch(batch, A), P2.reshape(1, 3, 4), batch, 'second pose through the alias')
+    # ... and as the allocator does it: a NEW tensor object on that memory, version 0
+    alias.copy_(P3.reshape(1, 3, 4))
+    B = from_dlpack(to_dlpack(A))
+    assert B is not A and key(B) == k0
+    _assert_rays_of(net._process_ray_batch(batch, B), P3.reshape(1, 3, 4), batch, 'third pose, a new tensor on the same memory')
+
+
+@pytest.mark.parametrize('imn', [3, 1])
+def test_camera_centres_over_released_and_new_pose_tensors(imn):
+    """pose A, released, then pose B (whatever address the allocator gives it), for a pool of three images and for render_image's [1,3,4];
+    then a tensor of another shape at the address of the one before"""
+    net = _shape_net()
+    V = _views(6)
+    batch = _ray_batch(imn)
+    A = torch.stack(V[:imn]).clone()
+    _assert_rays_of(net._process_ray_batch(batch, A), torch.stack(V[:imn]), batch, 'A')
+    del A
+    B = torch.stack(V[3:3 + imn]).clone()
+    _assert_rays_of(net._process_ray_batch(batch, B), torch.stack(V[3:3 + imn]), batch, 'B after A was released')
+    # the same address with another shape: [3,3,4] whose first image is V[5], then its [1,3,4] head
+    C3 = torch.stack([V[5], V[0], V[1]]).clone()
+    b3, b1 = _ray_batch(3, seed=6), _ray_batch(1, seed=6)
+    _assert_rays_of(net._process_ray_batch(b3, C3), C3.clone(), b3, 'three images')
+    head = C3[:1]
+    assert head.data_ptr() == C3.data_ptr() and head.shape != C3.shape
+    _assert_rays_of(net._process_ray_batch(b1, head), C3[:1].clone(), b1, 'one image at the same address')
+
+
+def test_training_pool_centres_are_cached_on_the_pose_tensor_itself():
+    """train_step keeps its saving -- the centres of self.train_poses are computed once per pool, not per step -- and the cache is bound
+    to that tensor OBJECT and its version: a second set_ray_pool (the first pool's tensors released, as a caller would) or an in-place
+    update of train_poses gives the new centres.  render is replaced by a recorder: this is about the rays it is handed."""
+    from tests.helpers import centre_bound
+    net = _shape_net({'train_ray_num': 64})
+    V = _views(6)
+    imgs, Ks = torch.rand(3, 6, 5, 3), torch.tensor([[8.0, 0, 2.5], [0, 8.0, 3.0], [0, 0, 1]]).repeat(3, 1, 1)
+    seen = []
+    net.render = lambda rays_o, *a, **k: seen.append(rays_o.clone()) or {'ray_rgb': torch.zeros(rays_o.shape[0], 3)}
+
+    def step_and_check(poses, where):
+        i0 = net.train_batch_i
+        idxs = net.train_batch['idxs'][i0:i0 + 64].numpy()
+        net.train_step(25000)
+        cb = [centre_bound(p) for p in poses]
+        err = np.abs(seen[-1].numpy().astype(np.float64) - np.stack([cb[i][0] for i in idxs]))
+        assert (err <= np.stack([cb[i][1] for i in idxs])).all(), where
+
+    P1 = torch.stack(V[:3]).clone()
+    net.set_ray_pool(imgs, Ks, P1, device='cpu')
+    step_and_check(torch.stack(V[:3]), 'first pool')
+    held = net._train_cam_centres()
+    step_and_check(torch.stack(V[:3]), 'first pool, second step')
+    assert net._train_cam_centres() is held                              # not recomputed per step
+    del P1, held
+    P2 = torch.stack(V[3:]).clone()
+    net.set_ray_pool(imgs, Ks, P2, device='cpu')
+    step_and_check(torch.stack(V[3:]), 'second pool')
+    with torch.no_grad():
+        net.train_poses.copy_(torch.stack([V[1], V[4], V[2]]))           # in place: the version counter moves
+    step_and_check(torch.stack([V[1], V[4], V[2]]), 'poses updated in place')
+    assert net._cam_centres[0] is net.train_poses                        # the cache holds what it was computed from
+
+
 def test_stage1_pool_contents_vs_reference_construct_ray_batch():
     """set_ray_pool (device-side pool build) == NeROShapeRenderer._construct_ray_batch of the reference, before the shuffle"""
     z = _pools()

@@ -194,6 +194,12 @@ def test_material_trainer_entry_point_and_pretrace():
     assert all(torch.isfinite(p.grad).all() for p in net.parameters() if p.grad is not None)
     mats = net.predict_materials_of_vertices(torch.from_numpy(v).cuda())
     assert mats['albedo'].shape == (v.shape[0], 3) and np.isfinite(mats['roughness']).all()
+    # a validation render in between leaves them as they were (views in a row against fresh renderers: tests/test_render_sequences_gpu.py)
+    net.zero_grad()
+    ev = net({'eval': True, 'index': 0, 'step': 100})
+    assert ev['rgb_pr'].shape == (48, 48, 3)
+    again = net.predict_materials_of_vertices(torch.from_numpy(v).cuda())
+    assert all(np.array_equal(mats[k], again[k]) for k in mats)
 
 
 def test_stage2_pretrace_pool_vs_reference_construct_ray_batch():

@@ -344,12 +344,16 @@ def test_nvs_through_the_c_driver_equals_the_python_sequenced_render(monkeypatch
     net = net.cuda()
     K = np.array([[90., 0, 32], [0, 90., 32], [0, 0, 1]], np.float32)
     pose = look_at_pose(np.array([0.5, -2.8, 0.6], np.float32))
+    pose2 = look_at_pose(np.array([-2.1, 1.7, 1.1], np.float32))
     a = net.render_image(pose, K, 64, 64, chunk=1000)['ray_rgb']
+    a2 = net.render_image(pose2, K, 64, 64, chunk=1000)['ray_rgb']            # another view on the same object and driver
     assert getattr(net, '_infer_drv', None) is not None
     monkeypatch.setattr(NeROShapeRenderer, '_inference_driver', lambda self, kern: None)
+    b2 = net.render_image(pose2, K, 64, 64, chunk=1000)['ray_rgb']            # ... and in the other order on the Python-sequenced side
     b = net.render_image(pose, K, 64, 64, chunk=1000)['ray_rgb']
     assert a.shape == (4096, 3) and bool(torch.isfinite(a).all()) and float(a.std()) > 1e-3
     assert torch.equal(a, b), float((a - b).abs().max())
+    assert torch.equal(a2, b2) and float((a2 - a).abs().max()) > 1e-2
 
 
 def test_extract_fields_grid():

@@ -186,6 +186,14 @@ def test_c_driver_training_steps_and_small_workspace_error(monkeypatch):
         runs.append((float(info['loss']), ts.bucket.flat.clone()))
     assert runs[0][0] == runs[0][0] and runs[0][0] == runs[1][0] and torch.equal(runs[0][1], runs[1][1])
     assert float(runs[0][1].abs().max()) > 0
+    # ... and with a smaller batch on the same handle in between (the workspace keeps the 128-ray step's rows behind the 33-ray step's; the
+    # sizes in any order against fresh handles: tests/test_driver_reuse_gpu.py)
+    for R in (33, 128):
+        ts.R, ts.cursor = R, 0
+        torch.manual_seed(7)
+        info = ts.forward_backward(25010)
+        torch.cuda.synchronize()
+    assert float(info['loss']) == runs[0][0] and torch.equal(ts.bucket.flat, runs[0][1])
 
 
 @pytest.mark.gpu

@@ -114,6 +114,16 @@ def test_c_driven_material_training_steps(monkeypatch):
                            pool_points=512, device='cuda:0')
     losses = [float(ts.step(5000 + i)['loss']) for i in range(4)]
     assert all(l == l for l in losses) and ts.drv is not None
+    # the same batch before and after a smaller one on the same handle (the sizes in any order, empty partitions and repacks against
+    # fresh handles: tests/test_driver_reuse_gpu.py)
+    runs = []
+    for P in (128, 5, 128):
+        ts.P, ts.cursor = P, 0
+        torch.manual_seed(3)
+        info = ts.forward_backward(5010)
+        torch.cuda.synchronize()
+        runs.append((float(info['loss']), ts.bucket.flat.clone()))
+    assert runs[0][0] == runs[2][0] and torch.equal(runs[0][1], runs[2][1]) and float(runs[0][1].abs().max()) > 0
 
 
 @pytest.mark.gpu

@@ -217,3 +217,67 @@ def test_occ_l1_node_vs_tensor_expression(n_in, cap, kept):
     assert loss.shape == () and float((loss - ref).abs()) <= 2e-6 * max(1.0, float(ref.abs()))
     assert torch.equal(a.grad != 0, b.grad != 0)
     assert float((a.grad - b.grad).abs().max()) <= 1e-7 * max(1e-30, float(b.grad.abs().max())) + 1e-12
+
+
+@pytest.mark.parametrize('cap', [4096, 48], ids=['cap_above_the_candidates', 'cap_below_the_candidates'])
+def test_occ_loss_device_route_vs_tensor_route(cap, monkeypatch):
+    """The two occlusion-subset routes of nero_amd.shape_step.occ_loss -- nero_occ_select on the device (the default) and torch.nonzero +
+    argsort under NERO_OCC_DEVICE=0 -- on one 64-ray batch with the same per-candidate keys: both index the keys by the candidate's ORDINAL
+    (keys[:total]; test_occ_select_vs_nonzero_argsort_sort), the device route merely draws one per inner sample when none are given.  With
+    the cap above the candidate count both keep every candidate and no key matters; below it both keep argsort(keys, stable)[:cap],
+    sorted.  Identical kept sets (the points handed to the march, bit for bit), and loss_occ / d loss_occ / d occ_prob of either route
+    against the float64 mean of the same terms by the rule of test_occ_l1_node_vs_tensor_expression (2e-6 on the loss; the gradient's
+    support exactly, its values to 1e-7 -- one rounding of d / kept, the upstream factor 0.5 being exact)."""
+    from nero_amd import shape_step as SS
+    from nero_amd.renderer import NeROShapeRenderer
+    from nero_amd.synthetic import perturb_state, synthetic_rays
+    L, lib, p = _lib()
+    cfg = {'n_samples': 16, 'n_importance': 16, 'n_bg_samples': 8, 'apply_occ_loss': True, 'occ_loss_step': 20000, 'occ_loss_max_pn': cap}
+    torch.manual_seed(0)
+    net = NeROShapeRenderer(cfg, training=False)
+    perturb_state(net, 0.4)
+    net = net.cuda()
+    o, d, _, _ = (t.cuda() for t in synthetic_rays(64, seed=1, window=200))
+    near, far = net.near_far_from_sphere(o, d)
+    with torch.no_grad():            # a schedule step below occ_loss_step: the state of the render, no occlusion term yet
+        out = net.render(o, d, near, far, None, 0, 1.0, is_train=True, step=10000)
+    S, occ = out['_state'], out['_occ_prob'].detach().clone()
+    n_in = S['n_in']
+    var = net.deviation_network.kernel_variance().detach().contiguous()
+    flag = torch.empty(n_in, dtype=torch.uint8, device='cuda')
+    L.check(lib.nero_occ_candidates(p(S['x4']), p(S['sctx']['sdf4']), p(S['sctx']['normal']), p(S['inner_idx']), p(S['d']), S['T'],
+                                    net.cfg['occ_sdf_thresh'], n_in, p(flag), L.stream_ptr()))
+    every = torch.nonzero(flag)[:, 0]
+    total = every.numel()
+    assert 48 < total < 4096, total
+    k = torch.rand(total, generator=torch.Generator().manual_seed(3)).cuda()
+    want = every if total <= cap else every[torch.sort(torch.argsort(k, stable=True)[:cap])[0]]
+    kept = want.numel()
+    marched, real = [], SS.secondary_occlusion
+
+    def spy(K_, pts, dirs, *a):
+        gt = real(K_, pts, dirs, *a)
+        marched.append((pts.clone(), gt.clone()))
+        return gt
+    monkeypatch.setattr(SS, 'secondary_occlusion', spy)
+    res = {}
+    for route in ('1', '0'):
+        monkeypatch.setenv('NERO_OCC_DEVICE', route)
+        a = occ.clone().requires_grad_(True)
+        loss, count = SS.occ_loss(S, a, net.cfg, var, k)
+        (loss * 0.5).sum().backward()
+        pts, gt = marched.pop()
+        assert not marched and int(count) == kept, (route, int(count), kept)
+        assert pts.shape[0] == (cap if route == '1' else kept)
+        assert torch.equal(pts[:kept], S['x4'][want, :3]), f'route {route}: the kept candidates are not argsort(keys, stable)[:cap], sorted'
+        gt = gt.reshape(-1)[:kept]
+        diff = occ[want].double() - gt.double()
+        ref = float(diff.abs().mean())
+        ref_grad = torch.zeros(n_in, dtype=torch.float64, device='cuda')
+        ref_grad[want] = torch.sign(diff) * 0.5 / kept
+        print(f'route {route}: cap {cap}, candidates {total}, kept {kept}, loss {float(loss):.9g}, float64 {ref:.9g}')
+        assert abs(float(loss) - ref) <= 2e-6 * max(1.0, abs(ref)), (route, float(loss), ref)
+        assert torch.equal(a.grad != 0, ref_grad != 0), route
+        assert float((a.grad.double() - ref_grad).abs().max()) <= 1e-7 * max(1e-30, float(ref_grad.abs().max())) + 1e-12, route
+        res[route] = (gt.clone(), float(loss))
+    assert torch.equal(res['1'][0], res['0'][0])          # the same rows through the same march kernels, in launches of cap and of kept rows

@@ -161,6 +161,10 @@ def test_ordered_launch_is_bit_identical_to_the_natural_order(n_pts, k, order):
     both = rt.trace_masked(o, d, skip, chunk_order=order)
     for a, b in zip(masked, both):
         assert torch.equal(a, b)
+    for a, b in zip(masked, rt.trace_masked(o, d, skip.data_ptr(), chunk_order=order)):       # the mask as an integer device pointer
+        assert torch.equal(a, b)
+    with pytest.raises(AssertionError):                             # a mask tensor of another size is refused on this route too
+        rt.trace_masked(o, d, skip[:n - 64].contiguous(), chunk_order=order)
     for bad, m in (([0] * k, n), (order, n - 64)):                  # not a permutation / not whole groups: natural order, same result
         odd = rt.trace_masked(o[:m], d[:m], None, chunk_order=bad)
         for a, b in zip(plain, odd):
