@@ -17,6 +17,8 @@ HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h)
 LATER_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_envsample.h',))
 # ... and those added after the tests of the fifth pinned that tuple too: the same rule once more
 BOUNCE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_bounce.h',))
+# ... and the seventh header, after the tests of the sixth pinned that one: the same rule again
+NORMALS_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_normals.h',))
 
 MAX_LAYERS = 10
 HID = 256
@@ -153,7 +155,7 @@ def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
+    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
 
 
 lib = _load()

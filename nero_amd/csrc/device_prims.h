@@ -40,6 +40,15 @@ __device__ __forceinline__ unsigned wave_max(unsigned v) {
     }
     return v;
 }
+// (64 bits: the bit pattern of a non-negative double orders as the double does)
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
 // the float pair is fminf / fmaxf, not a comparison: a NaN lane does not spread
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll

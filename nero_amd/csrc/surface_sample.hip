@@ -46,15 +46,6 @@ __device__ __forceinline__ bool tri_cross(const float* __restrict__ verts, int V
     return true;
 }
 
-__device__ __forceinline__ u64 wave_max64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 // a2[t], and the largest of them in *mx_bits (zeroed by the caller): non-negative doubles order as their bit patterns do
 __global__ __launch_bounds__(THREADS) void surface_area_kernel(const float* __restrict__ verts, int V, const int* __restrict__ tris, int64_t T,
                                                                double* __restrict__ a2, u64* mx_bits) {
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(THREADS) void surface_area_kernel(const float* __re
         if (tri_cross(verts, V, tris, t, p, c, &len) && isfinite(len)) a = len;
         a2[t] = a;
     }
-    const u64 m = wave_max64((u64)__double_as_longlong(a));          // (lanes past T hold +0)
+    const u64 m = wave_max((u64)__double_as_longlong(a));          // (lanes past T hold +0)
     if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(mx_bits, m);
 }
 

@@ -14,6 +14,8 @@ reads it with trimesh (extract_mesh.py:34-37, network/renderer.py:704).  This mo
     (DESIGN.md, "Mesh simplification").
   * face_adjacency_device / face_charts_device: the neighbours of every face across its edges and the charts of the projection atlas
     (nero_mesh_face_adjacency / nero_mesh_chart_*), which nero_amd.texture.chart_atlas turns into UV coordinates.
+  * vertex_normals / winding_sign: smooth per-vertex normals, face normals weighted by angle or by area and summed as integers
+    (nero_vertex_normals), and the side a closed mesh's winding points to; write_ply / read_ply carry the normals.
 Conventions (include/nero_hip.h): a corner is inside when u < threshold; vertices are index-space, one per crossing grid edge, ordered by
 (linear grid index, axis x<y<z); triangles are ordered by (cell, table position) and wound so that their normals point into u < threshold --
 inward for an SDF, which NeROMaterialRenderer.trace flips to outward shading normals."""
@@ -448,22 +450,99 @@ def simplify_mesh(v, f, **kw):
     return info.positions64.cpu().numpy(), f2.cpu().numpy().astype(np.int64), info
 
 
+# ---- vertex normals ---------------------------------------------------------------------------------------------------------------------
+NORMAL_WEIGHTS = {'area': 0, 'angle': 1}
+
+
+def _as_mesh(verts, tris, device=None):
+    """host arrays or tensors on any device -> (verts float32 [V,3], tris int32 [T,3]) contiguous on `device` (None: where they are, host
+    arrays on the host)"""
+    v = verts.detach() if torch.is_tensor(verts) else torch.from_numpy(np.ascontiguousarray(np.asarray(verts), dtype=np.float32))
+    t = tris.detach() if torch.is_tensor(tris) else torch.from_numpy(np.ascontiguousarray(np.asarray(tris), dtype=np.int32))
+    if v.dim() != 2 or v.shape[1] != 3 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f'expected vertices [V, 3] and triangles [T, 3], got {tuple(v.shape)} and {tuple(t.shape)}')
+    dev = v.device if device is None else device
+    return v.to(device=dev, dtype=torch.float32).contiguous(), t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def winding_sign(verts, tris):
+    """+1 when the triangles of a closed mesh are wound so that their normals point outwards, -1 when inwards (the meshes of
+    extract_mesh.py), 0 when the mesh encloses no volume (an open sheet): the sign of the signed volume sum p0 . (p1 x p2) over the faces,
+    in float64 in torch after moving the centroid of the vertices to the origin, on the device the vertices are on.  Only the sign is used;
+    a sum within the rounding noise of its terms (2^-40 of the sum of |p0| |p1| |p2|) counts as zero.  Faces with an index out of range or a
+    non-finite corner are left out."""
+    v, t = _as_mesh(verts, tris)
+    t = t.to(v.device).long()
+    V = v.shape[0]
+    t = t[((t >= 0) & (t < V)).all(1)]
+    p = v.double()
+    finite = torch.isfinite(p).all(1)
+    if not bool(finite.any()) or t.shape[0] == 0:
+        return 0
+    p = p - p[finite].mean(0, keepdim=True)
+    c = p[t]                                                                               # [T,3,3]
+    term = (c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum(1)
+    size = c.norm(dim=2).prod(1)                                                           # |p0| |p1| |p2|: what a term's rounding scales with
+    ok = torch.isfinite(term) & torch.isfinite(size)
+    vol, noise = float(term[ok].sum()), float(size[ok].sum()) * 2.0 ** -40
+    return 0 if abs(vol) <= noise else (1 if vol > 0 else -1)
+
+
+def vertex_normals(verts, tris, weight='angle', orient='winding', return_info=False):
+    """smooth per-vertex normals (nero_vertex_normals): verts [V,3], tris [T,3], host arrays or tensors -> float32 [V,3] on
+    the device (that of the input tensors, else the current one).  weight: 'angle' (each face's unit normal weighted by its angle at the
+    vertex: independent of how a surface is cut into triangles) or 'area' (by its area).  orient: 'winding' leaves the normals on the
+    side the triangles' winding gives, 'outward' multiplies them by winding_sign (zeros for a mesh that encloses no volume).  The same
+    bits on every run and for every order of the triangles.  A vertex no face reaches, or whose faces cancel, gets (0, 0, 0); a face
+    with an index outside [0, V) or a non-finite corner contributes nothing.  return_info: also info int64 [4] on the device = (refused
+    faces, faces without area, vertices written as zero, the exponent of the area scale)."""
+    if weight not in NORMAL_WEIGHTS:
+        raise ValueError(f"vertex_normals: weight must be 'angle' or 'area', got {weight!r}")
+    if orient not in ('winding', 'outward'):
+        raise ValueError(f"vertex_normals: orient must be 'winding' or 'outward', got {orient!r}")
+    dev = next((x.device for x in (verts, tris) if torch.is_tensor(x) and x.is_cuda), None)
+    dev = torch.device('cuda', torch.cuda.current_device()) if dev is None else dev
+    v, t = _as_mesh(verts, tris, dev)
+    V, T = v.shape[0], t.shape[0]
+    need = int(L.lib.nero_vertex_normals_workspace_bytes(V, T))
+    if need == 0:
+        raise L.NeroHipError(f'vertex_normals: {V} vertices / {T} triangles: {L.lib.nero_last_error().decode()}')
+    L.check_workspace_fits(need + 12 * V, dev, what='vertex-normal workspace')
+    with torch.cuda.device(dev):
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        info = torch.empty(4, dtype=torch.int64, device=dev)
+        L.check(L.lib.nero_vertex_normals(L.ptr(v), V, L.ptr(t), T, NORMAL_WEIGHTS[weight], L.ptr(ws), L.ptr(out), L.ptr(info), L.stream_ptr()))
+        if orient == 'outward':
+            sign = winding_sign(v, t)
+            if sign <= 0:
+                out = out * float(sign) + 0.0                                              # (+ 0.0: a zero component stays +0, as the other winding's)
+    return (out, info) if return_info else out
+
+
 # ---- PLY --------------------------------------------------------------------------------------------------------------------------------
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
               'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
 
 
-def write_ply(path, v, f):
+def write_ply(path, v, f, normals=None):
     """binary little-endian PLY: `float x, y, z` per vertex, `list uchar int vertex_indices` per face (what trimesh writes for a mesh
-    without attributes, extract_mesh.py:37)"""
+    without attributes, extract_mesh.py:37).  normals [V,3]: `float nx, ny, nz` after z (vertex_normals); None: the same bytes as ever"""
     v = np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype='<f4').reshape(-1, 3)
     f = np.asarray(f.detach().cpu().numpy() if torch.is_tensor(f) else f).reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError('write_ply: a face index is out of range')
+    props = 'property float x\nproperty float y\nproperty float z\n'
+    if normals is not None:
+        n = np.ascontiguousarray(normals.detach().cpu().numpy() if torch.is_tensor(normals) else normals, dtype='<f4').reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f'write_ply: {len(n)} normals for {len(v)} vertices')
+        v = np.ascontiguousarray(np.concatenate([v, n], 1))
+        props += 'property float nx\nproperty float ny\nproperty float nz\n'
     faces = np.empty(len(f), dtype=[('n', 'u1'), ('idx', '<i4', (3,))])
     faces['n'] = 3
     faces['idx'] = f
-    head = (f'ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n'
+    head = (f'ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\n{props}'
             f'element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n')
     with open(path, 'wb') as fh:
         fh.write(head.encode('ascii'))
@@ -510,9 +589,10 @@ def _triangles(counts, where):
                          f'supported')
 
 
-def read_ply(path):
+def read_ply(path, with_normals=False):
     """-> (vertices float64 [V,3], faces int64 [T,3]).  binary_little_endian or ascii; float or double x, y, z, other vertex properties
-    (normals, colours, ...) skipped; faces must be triangles.  Big-endian files and polygon faces raise ValueError."""
+    (colours, ...) skipped; faces must be triangles.  Big-endian files and polygon faces raise ValueError.  with_normals: -> (vertices,
+    faces, normals float32 [V,3] from the vertex properties nx, ny, nz, or None when the file has none)."""
     with open(path, 'rb') as fh:
         fmt, elements = _read_header(fh)
         if fmt == 'binary_big_endian':
@@ -520,7 +600,7 @@ def read_ply(path):
         if fmt not in ('binary_little_endian', 'ascii'):
             raise ValueError(f'read_ply: unknown format {fmt!r}')
         body = fh.read()
-    verts = faces = None
+    verts = faces = normals = None
     if fmt == 'ascii':
         lines = body.decode('ascii').split('\n')
         at = 0
@@ -533,6 +613,8 @@ def read_ply(path):
                     raise ValueError('read_ply: list properties on vertices are not supported')
                 a = np.array(rows, dtype=np.float64).reshape(el['count'], len(cols))
                 verts = a[:, [cols.index(c) for c in 'xyz']]
+                if all(c in cols for c in ('nx', 'ny', 'nz')):
+                    normals = a[:, [cols.index(c) for c in ('nx', 'ny', 'nz')]].astype(np.float32)
             elif el['name'] == 'face':
                 if el['props'][0][1] != 'list':
                     raise ValueError('read_ply: the face element has no leading vertex-index list')
@@ -558,9 +640,11 @@ def read_ply(path):
                 rec = np.frombuffer(body, dtype=dt, count=el['count'], offset=at) if el['count'] else np.zeros(0, dt)
                 if el['name'] == 'vertex':
                     verts = np.stack([rec[c].astype(np.float64) for c in 'xyz'], -1).reshape(el['count'], 3)
+                    if all(c in rec.dtype.names for c in ('nx', 'ny', 'nz')):
+                        normals = np.stack([rec[c].astype(np.float32) for c in ('nx', 'ny', 'nz')], -1).reshape(el['count'], 3)
                 at += dt.itemsize * el['count']
     if verts is None or faces is None:
         raise ValueError(f'read_ply: {os.path.basename(path)} has no vertex or no face element')
     if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
         raise ValueError('read_ply: a face index is out of range')
-    return verts, faces
+    return (verts, faces, normals) if with_normals else (verts, faces)

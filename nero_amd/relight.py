@@ -5,7 +5,8 @@ Camera rays go through nero_bvh_trace_faces (depth, face, barycentrics), the per
 nero_bvh_relight evaluates the reference's shade_mixed estimator with "environment radiance if the shadow ray is free, zero if it is
 blocked" for the light -- one fused kernel that never stores a ray.  With bounces=1 a blocked direction is not black: it fetches the light
 the surface it meets sends back under its own direct lighting (one bounce, one sample, a shadow ray of its own; include/nero_hip_bounce.h,
-DESIGN.md 9.12.2).  NOT modelled: more than one bounce, texture maps as input, smooth normals unless the caller supplies per-vertex ones.
+DESIGN.md 9.12.2).  Smooth shading takes per-vertex normals, the caller's or computed here (normals='angle' / 'area').  NOT
+modelled: more than one bounce, texture maps as input.
 This is not Cycles.
 
 samples = (Dd, Ds) draws every direction from the BRDF; samples = (Dd, Ds, Dl) adds Dl directions drawn from the map itself (light_table,
@@ -30,6 +31,7 @@ from .texture import _png_chunk
 
 CONVENTIONS = {'nero': 0, 'nero_real': 1, 'blender': 2}          # nero_env_lookup's `convention`
 GEOMETRY_TYPES = {'schlick': 0, 'ggx_smith': 1}                  # as nero_amd.stage2
+NORMAL_MODES = ('angle', 'area')                                 # Relighter(normals=...): vertex normals computed from the mesh
 MISS_DEPTH = 10.0
 MAX_LANES = 2 ** 31 - 64                                         # (point, padded sample) lanes of one nero_bvh_relight call
 DEFAULT_CHUNK_LANES = 1 << 26
@@ -429,7 +431,9 @@ class Relighter:
     predict_materials_of_vertices); env: linear radiance [h,w,3] (array, tensor) or the path of a Radiance .hdr; convention: 'blender'
     (the equirectangular mapping of an .hdr made for relight.py --hdr), 'nero' / 'nero_real' (this project's env_light grid, is_real = 0 /
     1); env_rotation: 3 x 3, applied to a direction before the lookup; tracer: a RayTracer over the same mesh to share, else one is built
-    (`build`); normals: per-vertex [V,3] for smooth shading, else flat face normals turned towards the camera; bounces: render()'s default."""
+    (`build`); normals: per-vertex [V,3] for smooth shading, 'angle' or 'area' to compute them from the mesh (nero_amd.mesh.vertex_normals,
+    stored outward; the flat normal stands in wherever one has no direction), else flat face normals turned towards the camera; bounces:
+    render()'s default."""
 
     def __init__(self, verts, tris, materials, env, convention='blender', env_rotation=None, tracer=None, build='device',
                  geometry_type='schlick', normals=None, device=None, bounces=0):
@@ -440,7 +444,16 @@ class Relighter:
         V = self.verts.shape[0]
         self.mat5 = torch.cat([as_t(materials[k], torch.float32).reshape(V, -1) for k in ('metallic', 'roughness', 'albedo')], -1)   # perceptual
         assert self.mat5.shape[1] == 5, self.mat5.shape
-        self.normals = None if normals is None else as_t(normals, torch.float32).reshape(V, 3)
+        # 'angle' / 'area': smooth normals computed here, once, and stored OUTWARD whatever the winding (the bounce kernels read them at
+        # secondary hits without turning them); where they fail (zero, not finite) surface() falls back to the flat normal
+        self._computed_normals = isinstance(normals, str)
+        if self._computed_normals:
+            if normals not in NORMAL_MODES:
+                raise ValueError(f"normals {normals!r}: None (flat), {' or '.join(map(repr, NORMAL_MODES))} (computed), or a [V,3] array")
+            from .mesh import vertex_normals
+            self.normals = vertex_normals(self.verts, self.tris.int(), weight=normals, orient='outward')
+        else:
+            self.normals = None if normals is None else as_t(normals, torch.float32).reshape(V, 3)
         if isinstance(env, (str, os.PathLike)):
             from .envlight import read_hdr
             env = read_hdr(env)
@@ -496,13 +509,17 @@ class Relighter:
         corner = self.verts[f]                                                               # [m,3,3]
         pts = (wts * corner).sum(1)
         mat5 = (wts * self.mat5[f]).sum(1)
-        if self.normals is None:
+        if self.normals is None or self._computed_normals:
             # the flat normal on the side the ray came from: the meshes of extract_mesh.py are wound inwards (the reference's trace() negates the
             # tracer's normals), others outwards -- the side a camera ray meets of a closed mesh is its outside either way
             nrm = torch.linalg.cross(corner[:, 1] - corner[:, 0], corner[:, 2] - corner[:, 0])
             nrm = torch.where((nrm * rays_d[idx]).sum(-1, keepdim=True) > 0, -nrm, nrm)
-        else:
-            nrm = (wts * self.normals[f]).sum(1)
+        if self.normals is not None:
+            smooth = (wts * self.normals[f]).sum(1)
+            if self._computed_normals:                                                       # (a caller's own normals are taken as they are)
+                good = torch.isfinite(smooth).all(-1, keepdim=True) & (smooth != 0).any(-1, keepdim=True)
+                smooth = torch.where(good, smooth, nrm)
+            nrm = smooth
         nrm = torch.nn.functional.normalize(nrm, dim=-1)
         return {'depth': depth, 'hit': hit, 'idx': idx, 'pts': pts, 'normal': nrm, 'mat5': mat5}
 

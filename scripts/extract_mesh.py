@@ -20,6 +20,8 @@ Simplification: --simplify-cell C clusters the vertices on a grid of cells of si
 indices in extract mode, the PLY's units in clean-only mode); --target-faces N chooses the smallest cell of the ladder
 nero_amd.mesh.simplify_cells that leaves at most N faces.  One or the other.  The JSON line then holds `simplify`: the vertex and face
 counts before and after, the chosen cell, its step k, and the number of duplicate faces removed.
+Normals: --normals {angle,area} writes smooth per-vertex normals of the final mesh into the PLY (nero_amd.mesh.vertex_normals), turned
+outwards whatever the winding; in both modes, after the clean-up and the simplification.
 Prints one JSON line: the per-component table (vertices, faces, area, bounding box) before and after; --table-limit caps the rows listed
 per table (largest first), the counts are always complete."""
 import argparse
@@ -51,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument('--min-face-ratio', type=float, default=0.0, metavar='R')
     ap.add_argument('--simplify-cell', type=float, default=None, metavar='C')
     ap.add_argument('--target-faces', type=int, default=None, metavar='N')
+    ap.add_argument('--normals', choices=['angle', 'area'], default=None,
+                    help='write smooth vertex normals (nx, ny, nz) into the PLY, pointing outwards: face normals weighted by angle or by area')
     ap.add_argument('--table-limit', type=int, default=32)
     args = ap.parse_args(argv)
     if args.inp and (args.cfg or args.model):
@@ -132,7 +136,12 @@ def main(argv=None):
         out['resolution'] = args.resolution
         out['table_space'] = 'grid index'
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    M.write_ply(args.out, to_world(v2), f2)
+    vw = to_world(v2)
+    normals = None
+    if args.normals:                                                      # of the vertices the file holds, as float32, turned outwards
+        normals, ninfo = M.vertex_normals(np.ascontiguousarray(vw, dtype=np.float32), f2, weight=args.normals, orient='outward', return_info=True)
+        out['normals'] = dict(zip(('weight', 'refused_faces', 'faces_without_area', 'zero_normals'), [args.normals] + ninfo[:3].tolist()))
+    M.write_ply(args.out, vw, f2, normals=normals)
     print(json.dumps(out))
     return out
 

@@ -5,7 +5,8 @@
     python scripts/relight.py --mesh M.ply --cfg configs/material/x.yaml --model model.pth --hdr E.hdr --name N
 
 --material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
-materials are predicted from the trained Stage-II network instead.  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
+materials are predicted from the trained Stage-II network instead.  --normals angle (or area) shades with smooth vertex normals computed
+from the mesh instead of flat face normals.  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
 import argparse
 import os
 import sys
@@ -41,6 +42,8 @@ def main(argv=None):
                     help="how the map is laid out: Blender's equirectangular image, or this project's env_light grid (is_real 0 / 1)")
     ap.add_argument('--bounces', type=int, default=0, choices=[0, 1],
                     help='1: a direction that meets the mesh fetches the light that surface sends back (one inter-reflection) instead of black')
+    ap.add_argument('--normals', default='flat', choices=['flat', 'angle', 'area'],
+                    help='flat: face normals; angle / area: smooth vertex normals computed from the mesh, face normals weighted by angle or by area')
     ap.add_argument('--out', default='data/relight')
     a = ap.parse_args(argv)
 
@@ -70,7 +73,7 @@ def main(argv=None):
     if len(a.samples) > 3 or min(a.samples) < 1:
         ap.error('--samples takes one to three positive integers')
     samples = tuple(a.samples) if len(a.samples) == 3 else tuple((a.samples * 2)[:2])
-    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention)
+    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if a.normals == 'flat' else a.normals)
     out_dir = os.path.join(a.out, a.name)
     paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
                             samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces)
