@@ -1,8 +1,9 @@
-// envsample_dev.h -- the device functions that envsample.hip and relight_bounce.hip share: the grid's directions, the light draw (env_draw),
-// the density (env_pdf, env_lookup_cell), the sample set of the three strategies (mis_ray) and the MIS per-sample terms (mis_weight,
-// mis_terms) and the host checks of the MIS sample counts and the table's size.  One definition each, moved here as text from envsample.hip, so that the MIS kernel and the bounce kernels draw the same
-// directions and weigh them by the same mixture bit for bit.  Every function switches floating-point contraction off for its own body
-// (envsample.hip does so for the whole file): every operation is the one include/nero_hip_envsample.h writes.
+// envsample_dev.h -- the device functions that envsample.hip (the light table), relight.hip (the ray export) and relight_estimator.hip (the
+// estimator) share: the grid's directions, the light draw (env_draw), the density (env_pdf, env_lookup_cell), the sample set of the three
+// strategies (mis_ray) and the MIS per-sample terms (mis_weight, mis_terms), and the host checks of the MIS sample counts and the table's
+// size.  One definition each, so that the export, the primary estimator and a bounce's one sample draw the same directions and weigh them
+// by the same mixture bit for bit.  Every function switches floating-point contraction off for its own body: every operation is the one
+// include/nero_hip_envsample.h writes.
 // Include after relight_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -174,7 +175,7 @@ __device__ __forceinline__ void mis_weight(const float* q, const float* w, float
     W = S * dg * G / (4.f * nov * pmix + 1e-5f);
 }
 
-// one sample's diffuse and specular terms under the mixture, for the radiance L it fetched: what relight_mis_kernel adds up
+// one sample's diffuse and specular terms under the mixture, for the radiance L it fetched: what relight_kernel<MIS> adds up
 __device__ __forceinline__ void mis_terms(const float* q, const float* w, float pl, int Dd, int Ds, int Dl, int geom, const float* L, float* diff,
                                           float* spec) {
 #pragma clang fp contract(off)
@@ -204,9 +205,9 @@ inline int check_table_size(const char* who, int eh, int ew) {
 inline int check_mis_samples(const char* who, int P, int Dd, int Ds, int Dl, int geometry_type) {
     char msg[160];
     if (P < 0) { snprintf(msg, sizeof(msg), "%s: P must be >= 0", who); return nero_fail(NERO_ERR_ARG, msg); }
-    if (!samples_ok(Dd, Ds, Dl)) { snprintf(msg, sizeof(msg), "%s: Dd, Ds and Dl must lie in [1, 4096]", who); return nero_fail(NERO_ERR_ARG, msg); }
+    if (!nero_relight::mis_samples_ok(Dd, Ds, Dl)) { snprintf(msg, sizeof(msg), "%s: Dd, Ds and Dl must lie in [1, 4096]", who); return nero_fail(NERO_ERR_ARG, msg); }
     if (geometry_type < 0 || geometry_type > 1) { snprintf(msg, sizeof(msg), "%s: geometry_type must be 0 or 1", who); return nero_fail(NERO_ERR_ARG, msg); }
-    if (!total_ok(P, Dd, Ds, Dl)) {
+    if (!nero_relight::total_ok(P, Dd, Ds, Dl)) {
         snprintf(msg, sizeof(msg), "%s: P * (Dd + Ds + Dl padded to 64) must be at most 2^31 - 64: call in chunks", who);
         return nero_fail(NERO_ERR_ARG, msg);
     }

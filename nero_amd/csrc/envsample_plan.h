@@ -1,16 +1,14 @@
-// envsample_plan.h -- the limits, weight-width, workspace and launch arithmetic of envsample.hip, free of HIP calls:
+// envsample_plan.h -- the limits, weight-width and workspace arithmetic of the light table (envsample.hip), free of HIP calls:
 // tests/envsample_plan_main.cpp is a stand-alone program over it that the CPU tests build with the undefined-behaviour sanitizer.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include "relight_plan.h"
 #include "ws_plan.h"
 
 namespace nero_envsample {
 
 constexpr int MAX_SIDE = 16384;                               // eh and ew, as nero_env_lookup
 constexpr int64_t MAX_CELLS = (int64_t)1 << 26;               // eh * ew: the table is 8 bytes per cell (512 MB here)
-constexpr int MIN_LIGHT = 1, MAX_LIGHT = 4096;                // Dl
 constexpr int MAX_WEIGHT_BITS = 40, TOTAL_BITS = 62;          // w < 2^B (<= 2^B in the fallback) with B <= 40; the sum stays <= 2^62
 constexpr int INFO_WORDS = 5;                                 // total, zero-weight cells, e, B, fallback taken
 constexpr int THREADS = 256;                                  // (what nero_ws::blocks_of divides by)
@@ -30,16 +28,5 @@ constexpr size_t HEAD_BYTES = 256;
 inline size_t float_bytes(int64_t N) { return nero_ws::align256((size_t)N * 4); }
 inline size_t weight_bytes(int64_t N) { return nero_ws::align256((size_t)N * 8); }
 inline size_t fixed_bytes(int64_t N) { return HEAD_BYTES + float_bytes(N) + weight_bytes(N); }
-
-// ---- the MIS kernel: D = Dd + Ds + Dl samples per point, padded to whole wavefronts (the layout of relight_plan.h) -----------------------
-inline bool samples_ok(int Dd, int Ds, int Dl) { return nero_relight::samples_ok(Dd, Ds) && Dl >= MIN_LIGHT && Dl <= MAX_LIGHT; }
-inline int waves_per_point(int Dd, int Ds, int Dl) { return (Dd + Ds + Dl + 63) / 64; }
-inline int padded_samples(int Dd, int Ds, int Dl) { return waves_per_point(Dd, Ds, Dl) * 64; }
-inline long long total_lanes(int P, int Dd, int Ds, int Dl) { return (long long)P * (long long)padded_samples(Dd, Ds, Dl); }
-inline bool total_ok(int P, int Dd, int Ds, int Dl) { return P >= 0 && total_lanes(P, Dd, Ds, Dl) <= nero_relight::MAX_LANES; }
-inline size_t workspace_bytes(int P, int Dd, int Ds, int Dl) {
-    return (size_t)P * (size_t)waves_per_point(Dd, Ds, Dl) * (size_t)nero_relight::PARTIAL_FLOATS * sizeof(float);
-}
-using nero_relight::grid_blocks;
 
 }  // namespace nero_envsample

@@ -1,32 +1,32 @@
 // relight.hip -- relighting the Stage-II mesh under a lat-long environment map (include/nero_hip_relight.h).  Replaces what the reference
-// hands to Blender Cycles in relight.py with direct lighting and shadows on the mesh tracer's BVH:
+// hands to Blender Cycles in relight.py with direct lighting and shadows on the mesh tracer's BVH.  Here, what surrounds the estimator:
 //   * nero_bvh_export_faces / nero_bvh_trace_faces: the closest-hit walks of bvh_walk.h expanded once more (ANY = false), reporting WHICH
 //     triangle was hit (through the builders' leaf-order table, Bvh::d_face) and where on it (the u, v of tri_test's own arithmetic);
 //   * nero_env_lookup: bilinear radiance of a lat-long map, in this project's own grid (the inverse of nero_env_encode's directions) or in
 //     the equirectangular mapping an .hdr made for the reference's relight.py --hdr assumes;
-//   * nero_relight_rays: the sample set -- relight_ray() of relight_dev.h IS the definition: the directions of sample_diffuse_directions /
-//     sample_specular_directions (field.py:768-810) as mc_shade.hip forms them, restated here with every product and sum rounded on its own
-//     so that the two kernels that expand it agree bit for bit;
-//   * nero_bvh_relight: the same rays from the same function, walked as shadow rays (any hit within the miss distance) without ever being
-//     stored, the environment looked up for the free ones, weighed by the estimator of shade_mixed (field.py:950-998) and reduced per point
-//     in a fixed order: shuffle butterfly inside the wavefront, one partial per wavefront, a finishing pass in index order.  No float atomics.
+//   * nero_relight_rays / nero_relight_mis_rays (include/nero_hip_envsample.h): the sample set -- relight_ray() of relight_dev.h IS the
+//     definition: the directions of sample_diffuse_directions / sample_specular_directions (field.py:768-810) as mc_shade.hip forms them,
+//     with every product and sum rounded on its own; mis_ray() of envsample_dev.h is relight_ray() for the first Dd + Ds samples and the
+//     light draws behind them.  The estimator (relight_estimator.hip) forms its rays by the same two functions and never stores them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/nero_hip.h"
 #include "../../include/nero_hip_relight.h"
+#include "../../include/nero_hip_envsample.h"
 #include "bvh_types.h"
 #include "bvh_walk.h"
 #include "common.h"
 #include "relight_plan.h"
-#include "relight_dev.h"                     // env_sample, relight_ray, brdf_weight, the any-hit walk and the argument checks: shared with
-                                             // envsample.hip, which expands the same sample set and reads the same radiance
+#include "relight_dev.h"                     // env_sample, relight_ray, hit_bary, the choice of the walk and the argument checks
+#include "envsample_dev.h"                   // mis_ray and the checks of the MIS sample counts
 
 namespace {
 
 using namespace nero_bvh;
-using namespace nero_relight;              // relight_plan.h (samples_ok, total_ok, waves_per_point, workspace_bytes, grid_blocks), relight_dev.h
-constexpr int PRIV_THREADS = 256;          // workgroup of the private-stack kernels (as trace_kernel)
+using namespace nero_relight;              // relight_plan.h (grid_blocks), relight_dev.h
+using nero_envsample::LightTab; using nero_envsample::u64; using nero_envsample::mis_ray; using nero_envsample::check_mis_samples;
+using nero_envsample::map_ok;
 
 // ---- closest hit with the face (hit_bary: relight_dev.h) --------------------------------------------------------------------------------
 // OVERLAP: PL_THREADS threads and the LDS stack (trees no deeper than PL_STACK), else PRIV_THREADS threads and the private stack
@@ -71,89 +71,38 @@ __global__ __launch_bounds__(256) void env_lookup_kernel(EnvMap E, const float* 
     for (int k = 0; k < 3; ++k) rgb[i * 3 + k] = L[k];
 }
 
-// ---- the sample set (relight_ray: relight_dev.h) ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void relight_rays_kernel(const float* __restrict__ pt, const float* __restrict__ tab_d,
-                                                           const float* __restrict__ tab_s, int total, int Dd, int Ds, int geom,
-                                                           float* __restrict__ ro, float* __restrict__ rd, unsigned char* __restrict__ dead) {
+// ---- the sample set (relight_ray: relight_dev.h; mis_ray: envsample_dev.h) ---------------------------------------------------------------
+// MIS: the three strategies' D = Dd + Ds + Dl samples with their cell and density, else the two BRDF strategies' (Dl = 0; tab_l .. gw, cell
+// and pdf_l unread)
+template <bool MIS>
+__global__ __launch_bounds__(256) void rays_kernel(const float* __restrict__ pt, const float* __restrict__ tab_d, const float* __restrict__ tab_s,
+                                                   const float* __restrict__ tab_l, const float* __restrict__ rand_l, int total, int Dd, int Ds,
+                                                   int Dl, int geom, const int64_t* __restrict__ cdf, const int64_t* __restrict__ info, int gh,
+                                                   int gw, float* __restrict__ ro, float* __restrict__ rd, unsigned char* __restrict__ dead,
+                                                   int* __restrict__ cell, float* __restrict__ pdf_l) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;             // ray p D + j
     if (row >= total) return;
-    const int D = Dd + Ds;
+    const int D = Dd + Ds + Dl;
     const int p = row / D, j = row - p * D;
     const float* q = pt + (size_t)p * 32;
-    float w[3], o[3];
-    const bool dd = relight_ray(q, tab_d, tab_s, j, Dd, geom, w, o);
+    float w[3], o[3], pdf = 0.f;
+    int k = -1;
+    bool dd;
+    if constexpr (MIS) {
+        const LightTab T = {cdf, gh, gw, (u64)info[0]};
+        dd = mis_ray(q, tab_d, tab_s, tab_l, rand_l ? rand_l + (size_t)p * 2 : nullptr, j, Dd, Ds, geom, T, w, o, k, pdf);
+    } else {
+        dd = relight_ray(q, tab_d, tab_s, j, Dd, geom, w, o);
+    }
     const size_t at = (size_t)row * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) { ro[at + c] = o[c]; rd[at + c] = w[c]; }
     if (dead) dead[row] = dd ? 1 : 0;
-}
-
-// ---- the estimator (brdf_weight, two_strategy_terms, the any-hit walk: relight_dev.h) -----------------------------------------------------------------------
-// One lane per (point, sample): wavefront W of the grid is chunk W % wpp of point W / wpp, lane l its sample (W % wpp) 64 + l; samples at or
-// past D are padding.  partial [P wpp, 6]: the wavefront's sums of the diffuse and the specular terms, added by a shuffle butterfly (the same
-// order on every run).
-template <bool OVERLAP>
-__global__ __launch_bounds__(OVERLAP ? PL_THREADS : PRIV_THREADS) void relight_kernel(
-    const Node* __restrict__ nodes, const Tri* __restrict__ tris, int root, const float* __restrict__ pt, const float* __restrict__ tab_d,
-    const float* __restrict__ tab_s, int P_, int Dd, int Ds, int wpp, int geom, EnvMap E, float* __restrict__ partial) {
-    __shared__ int lds_stack[OVERLAP ? PL_STACK * PL_THREADS : 1];
-    int* const st = lds_stack + (OVERLAP ? threadIdx.x : 0);
-    (void)st;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;               // below 2^31 (relight_plan.h)
-    const int wave = g >> 6, lane = threadIdx.x & 63;
-    const int p = wave / wpp;
-    if (p >= P_) return;                                               // a whole wavefront of the last workgroup
-    const int D = Dd + Ds;
-    const int j = (wave - p * wpp) * 64 + lane;
-    const float* q = pt + (size_t)p * 32;
-    float diff[3] = {0.f, 0.f, 0.f}, spec[3] = {0.f, 0.f, 0.f};
-    if (j < D) {
-        float d[3], o[3];
-        const bool dead = relight_ray(q, tab_d, tab_s, j, Dd, geom, d, o);
-        NERO_RELIGHT_ANY_HIT(blocked, MISS_DEPTH, dead ? NONE : root)
-        if (!dead && !blocked) {
-            float L[3];
-            env_sample(E, d, L);
-            two_strategy_terms(q, d, j, Dd, Ds, geom, L, diff, spec);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            diff[c] += __shfl_xor(diff[c], off);
-            spec[c] += __shfl_xor(spec[c], off);
-        }
-    }
-    if (lane == 0) {
-        float* out = partial + (size_t)wave * PARTIAL_FLOATS;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { out[c] = diff[c]; out[3 + c] = spec[c]; }
+    if constexpr (MIS) {
+        if (cell) cell[row] = k;
+        if (pdf_l) pdf_l[row] = pdf;
     }
 }
-
-// a point's partials added in index order
-__global__ __launch_bounds__(256) void relight_finish_kernel(const float* __restrict__ partial, int P_, int wpp, int Dd, int Ds,
-                                                             float* __restrict__ rgb_lin, float* __restrict__ diffuse_lin,
-                                                             float* __restrict__ spec_lin) {
-#pragma clang fp contract(off)
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P_) return;
-    float s[PARTIAL_FLOATS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < wpp; ++k) {
-        const float* in = partial + ((size_t)p * wpp + k) * PARTIAL_FLOATS;
-#pragma unroll
-        for (int c = 0; c < PARTIAL_FLOATS; ++c) s[c] += in[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float df = s[c] / (float)Dd, sp = s[3 + c] / (float)(Dd + Ds);
-        rgb_lin[(size_t)p * 3 + c] = df + sp;
-        if (diffuse_lin) diffuse_lin[(size_t)p * 3 + c] = df;
-        if (spec_lin) spec_lin[(size_t)p * 3 + c] = sp;
-    }
-}
-
 
 }  // namespace
 
@@ -174,12 +123,10 @@ int nero_bvh_trace_faces(void* handle, const float* rays_o, const float* rays_d,
     if ((long long)n > 2147483647ll / 3) return nero_fail(NERO_ERR_ARG, "nero_bvh_trace_faces: more than (2^31 - 1) / 3 rays: call in chunks");
     if (n == 0) return NERO_OK;
     Handle* h = (Handle*)handle;
-    if (h->mode == 0)
-        hipLaunchKernelGGL(trace_faces_kernel<false>, dim3(grid_blocks(n, PRIV_THREADS)), dim3(PRIV_THREADS), 0, (hipStream_t)stream,
+    with_walk(h, [&](auto overlap, int threads) {
+        hipLaunchKernelGGL(trace_faces_kernel<decltype(overlap)::value>, dim3(grid_blocks(n, threads)), dim3(threads), 0, (hipStream_t)stream,
                            h->b.d_nodes, h->b.d_tris, h->b.d_face, h->root, rays_o, rays_d, n, depth, face, bary);
-    else
-        hipLaunchKernelGGL(trace_faces_kernel<true>, dim3(grid_blocks(n, PL_THREADS)), dim3(PL_THREADS), 0, (hipStream_t)stream,
-                           h->b.d_nodes, h->b.d_tris, h->b.d_face, h->root, rays_o, rays_d, n, depth, face, bary);
+    });
     return nero_check_launch("nero_bvh_trace_faces");
 }
 
@@ -200,40 +147,22 @@ int nero_relight_rays(const float* pt, const float* tab_d, const float* tab_s, i
     if (check_samples("nero_relight_rays", P, Dd, Ds, geometry_type) != NERO_OK) return NERO_ERR_ARG;
     if (P == 0) return NERO_OK;
     const int total = P * (Dd + Ds);                                   // at most P * padded(D)
-    hipLaunchKernelGGL(relight_rays_kernel, dim3(grid_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, pt, tab_d, tab_s, total, Dd, Ds,
-                       geometry_type, rays_o, rays_d, dead);
+    hipLaunchKernelGGL(rays_kernel<false>, dim3(grid_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, pt, tab_d, tab_s, nullptr, nullptr,
+                       total, Dd, Ds, 0, geometry_type, nullptr, nullptr, 1, 1, rays_o, rays_d, dead, nullptr, nullptr);
     return nero_check_launch("nero_relight_rays");
 }
 
-size_t nero_relight_workspace_bytes(int P, int Dd, int Ds) {
-    if (!samples_ok(Dd, Ds) || !total_ok(P, Dd, Ds)) return 0;
-    return workspace_bytes(P, Dd, Ds);
-}
-
-int nero_bvh_relight(void* handle, const float* pt, const float* tab_d, const float* tab_s, int P, int Dd, int Ds, int geometry_type,
-                     const float* env, int eh, int ew, int convention, const float* rot, float clamp_max, float* rgb_lin, float* diffuse_lin,
-                     float* spec_lin, void* ws, size_t ws_bytes, void* stream) {
-    if (!handle || !pt || !tab_d || !tab_s || !rgb_lin) return nero_fail(NERO_ERR_ARG, "nero_bvh_relight: null handle or pointer");
-    if (check_samples("nero_bvh_relight", P, Dd, Ds, geometry_type) != NERO_OK) return NERO_ERR_ARG;
-    EnvMap E;
-    if (check_env("nero_bvh_relight", env, eh, ew, convention, rot, clamp_max, &E) != NERO_OK) return NERO_ERR_ARG;
+int nero_relight_mis_rays(const float* pt, const float* tab_d, const float* tab_s, const float* tab_l, const float* rand_l, int P, int Dd, int Ds,
+                          int Dl, int geometry_type, const int64_t* cdf, const int64_t* info, int gh, int gw, float* rays_o, float* rays_d,
+                          unsigned char* dead, int* cell, float* pdf_l, void* stream) {
+    if (!pt || !tab_d || !tab_s || !tab_l || !cdf || !info || !rays_o || !rays_d) return nero_fail(NERO_ERR_ARG, "nero_relight_mis_rays: null pointer");
+    if (check_mis_samples("nero_relight_mis_rays", P, Dd, Ds, Dl, geometry_type) != NERO_OK) return NERO_ERR_ARG;
+    if (!map_ok(gh, gw)) return nero_fail(NERO_ERR_ARG, "nero_relight_mis_rays: gh and gw must be in [1, 16384] and gh * gw at most 2^26");
     if (P == 0) return NERO_OK;
-    if (!ws || ((uintptr_t)ws & 3u) != 0 || ws_bytes < workspace_bytes(P, Dd, Ds))
-        return nero_fail(NERO_ERR_ARG, "nero_bvh_relight: workspace missing, misaligned or smaller than nero_relight_workspace_bytes");
-    Handle* h = (Handle*)handle;
-    const int wpp = waves_per_point(Dd, Ds);
-    const long long total = total_lanes(P, Dd, Ds);
-    float* partial = (float*)ws;
-    if (h->mode == 0)
-        hipLaunchKernelGGL(relight_kernel<false>, dim3(grid_blocks(total, PRIV_THREADS)), dim3(PRIV_THREADS), 0, (hipStream_t)stream,
-                           h->b.d_nodes, h->b.d_tris, h->root, pt, tab_d, tab_s, P, Dd, Ds, wpp, geometry_type, E, partial);
-    else
-        hipLaunchKernelGGL(relight_kernel<true>, dim3(grid_blocks(total, PL_THREADS)), dim3(PL_THREADS), 0, (hipStream_t)stream,
-                           h->b.d_nodes, h->b.d_tris, h->root, pt, tab_d, tab_s, P, Dd, Ds, wpp, geometry_type, E, partial);
-    if (nero_check_launch("nero_bvh_relight") != NERO_OK) return NERO_ERR_LAUNCH;
-    hipLaunchKernelGGL(relight_finish_kernel, dim3(grid_blocks(P, 256)), dim3(256), 0, (hipStream_t)stream, partial, P, wpp, Dd, Ds, rgb_lin,
-                       diffuse_lin, spec_lin);
-    return nero_check_launch("nero_bvh_relight (finish)");
+    const int total = P * (Dd + Ds + Dl);                              // at most P * padded(D)
+    hipLaunchKernelGGL(rays_kernel<true>, dim3(grid_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, pt, tab_d, tab_s, tab_l, rand_l, total,
+                       Dd, Ds, Dl, geometry_type, cdf, info, gh, gw, rays_o, rays_d, dead, cell, pdf_l);
+    return nero_check_launch("nero_relight_mis_rays");
 }
 
 }  // extern "C"

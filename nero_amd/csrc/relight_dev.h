@@ -1,12 +1,13 @@
-// relight_dev.h -- the device functions and argument checks that relight.hip and envsample.hip share: the environment lookup (env_sample),
-// the sample set of the two BRDF strategies (relight_ray), the estimator's weight (brdf_weight) and per-sample terms (two_strategy_terms),
-// the hit's (u, v) (hit_bary) and the any-hit expansion of the BVH walks -- shared with relight_bounce.hip too.
-// One definition each, so that the two-strategy kernels and the MIS kernels form the same directions and read the same radiance bit for bit.
+// relight_dev.h -- the device functions and argument checks that relight.hip, relight_estimator.hip and envsample.hip share: the environment
+// lookup (env_sample), the sample set of the two BRDF strategies (relight_ray), the estimator's weight (brdf_weight) and per-sample terms
+// (two_strategy_terms), the hit's (u, v) (hit_bary), the any-hit expansion of the BVH walks and the host's choice between the walks.
+// One definition each, so that the ray exports and every estimator form the same directions and read the same radiance bit for bit.
 // Include after bvh_walk.h, common.h, relight_plan.h and shade_math.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/nero_hip.h"
 #include "bvh_types.h"
 #include "bvh_walk.h"
@@ -192,6 +193,16 @@ __device__ __forceinline__ void hit_bary(const nero_bvh::Tri* __restrict__ tris,
         }                                                                    \
     }
 
+// ---- the walk of a tree -----------------------------------------------------------------------------------------------------------------
+constexpr int PRIV_THREADS = 256;          // workgroup of the private-stack kernels (as trace_kernel)
+// launch(OVERLAP as a std::bool_constant, threads per workgroup): PL_THREADS threads and the LDS stack where the tree is no deeper than
+// PL_STACK (mode != 0), else PRIV_THREADS threads and the private stack
+template <class Launch>
+inline void with_walk(const nero_bvh::Handle* h, Launch&& launch) {
+    if (h->mode == 0) launch(std::false_type{}, PRIV_THREADS);
+    else launch(std::true_type{}, nero_bvh::PL_THREADS);
+}
+
 // ---- argument checks --------------------------------------------------------------------------------------------------------------------
 inline int check_env(const char* who, const float* env, int h, int w, int convention, const float* rot, float clamp_max, EnvMap* E) {
     char msg[160];
@@ -212,9 +223,9 @@ inline int check_env(const char* who, const float* env, int h, int w, int conven
 inline int check_samples(const char* who, int P, int Dd, int Ds, int geometry_type) {
     char msg[160];
     if (P < 0) { snprintf(msg, sizeof(msg), "%s: P must be >= 0", who); return nero_fail(NERO_ERR_ARG, msg); }
-    if (!samples_ok(Dd, Ds)) { snprintf(msg, sizeof(msg), "%s: Dd and Ds must lie in [1, 4096]", who); return nero_fail(NERO_ERR_ARG, msg); }
+    if (!samples_ok(Dd, Ds, 0)) { snprintf(msg, sizeof(msg), "%s: Dd and Ds must lie in [1, 4096]", who); return nero_fail(NERO_ERR_ARG, msg); }
     if (geometry_type < 0 || geometry_type > 1) { snprintf(msg, sizeof(msg), "%s: geometry_type must be 0 or 1", who); return nero_fail(NERO_ERR_ARG, msg); }
-    if (!total_ok(P, Dd, Ds)) {
+    if (!total_ok(P, Dd, Ds, 0)) {
         snprintf(msg, sizeof(msg), "%s: P * (Dd + Ds padded to 64) must be at most 2^31 - 64: call in chunks", who);
         return nero_fail(NERO_ERR_ARG, msg);
     }

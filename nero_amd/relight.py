@@ -310,46 +310,6 @@ def relight_bounce_rays(tracer, pt, tab_d, tab_s, mesh, key=None, geometry_type=
     return out
 
 
-def _relight_points_bounce(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, mesh, key):
-    """-> rgb_lin, diffuse_lin, spec_lin, indirect_lin [P,3] (nero_bvh_relight_bounce / nero_bvh_relight_mis_bounce)"""
-    mis = tab_l is not None
-    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0] if mis else 0
-    pad = padded_samples(Dd, Ds, Dl)
-    most = max(1, MAX_LANES // pad)
-    chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
-    chunk = max(1, min(chunk, most))
-    dev = pt.device
-    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(4)]
-    env = env.float().contiguous()
-    conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
-    verts, tris, mat5, normals = _mesh_args(mesh, dev)
-    kk = _key_arg(key, P, dev)
-    if mis and table is None:
-        table = light_table(env, conv, rot, clamp)
-    if mis:
-        assert (table.gh, table.gw) == tuple(env.shape[:2]), 'the light table is not this map\'s'
-    rl = None if rand_l is None else rand_l.float().contiguous()
-    mesh_args = (L.ptr(verts), verts.shape[0], L.ptr(tris), tris.shape[0], L.ptr(mat5), L.ptr(normals))
-    with torch.cuda.device(dev):
-        n0 = min(chunk, max(P, 1))
-        need = int(_lib.nero_relight_mis_bounce_workspace_bytes(n0, Dd, Ds, Dl) if mis else _lib.nero_relight_bounce_workspace_bytes(n0, Dd, Ds))
-        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
-        for i in range(0, P, chunk):
-            n = min(chunk, P - i)
-            outs = [L.ptr(o[i:i + n]) for o in out]
-            kp = None if kk is None else L.ptr(kk[i:i + n])
-            if mis:
-                L.check(_lib.nero_bvh_relight_mis_bounce(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l),
-                                                         None if rl is None else L.ptr(rl[i:i + n]), n, Dd, Ds, Dl, int(geometry_type), L.ptr(env),
-                                                         env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), L.ptr(table.cdf),
-                                                         L.ptr(table.info), *mesh_args, kp, *outs, L.ptr(ws), ws.numel(), L.stream_ptr()))
-            else:
-                L.check(_lib.nero_bvh_relight_bounce(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), n, Dd, Ds, int(geometry_type),
-                                                     L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), *mesh_args, kp,
-                                                     *outs, L.ptr(ws), ws.numel(), L.stream_ptr()))
-    return tuple(out)
-
-
 def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=None, geometry_type=0, chunk=None, tab_l=None, rand_l=None,
                    table=None, bounces=0, mesh=None, key=None):
     """the fused kernel (nero_bvh_relight) over the point records pt [P,32], in chunks of `chunk` points (None: as many as fit
@@ -361,55 +321,50 @@ def relight_points(tracer, pt, tab_d, tab_s, env, convention=2, rot=None, clamp=
     None: zeros) seeding each point's bounces -> rgb_lin, diffuse_lin, spec_lin (the direct terms: bounces=0's bits), indirect_lin."""
     if bounces not in (0, 1):
         raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
-    if bounces == 1:
-        return _relight_points_bounce(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, mesh, key)
-    if tab_l is not None:
-        return _relight_points_mis(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk)
-    P, Dd, Ds = pt.shape[0], tab_d.shape[0], tab_s.shape[0]
-    pad = padded_samples(Dd, Ds)
-    most = max(1, MAX_LANES // pad)
-    chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
-    chunk = max(1, min(chunk, most))
-    dev = pt.device
-    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(3)]
-    env = env.float().contiguous()
-    conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
-    with torch.cuda.device(dev):
-        need = int(_lib.nero_relight_workspace_bytes(min(chunk, max(P, 1)), Dd, Ds))
-        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
-        for i in range(0, P, chunk):
-            n = min(chunk, P - i)
-            L.check(_lib.nero_bvh_relight(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), n, Dd, Ds, int(geometry_type),
-                                          L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0),
-                                          L.ptr(out[0][i:i + n]), L.ptr(out[1][i:i + n]), L.ptr(out[2][i:i + n]), L.ptr(ws), ws.numel(),
-                                          L.stream_ptr()))
-    return tuple(out)
+    return _relight_chunks(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, bounces, mesh, key)
 
 
-def _relight_points_mis(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk):
-    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0]
+# (MIS, bounces) -> the fused entry point and the one that sizes its workspace
+_FUSED = {(False, 0): (_lib.nero_bvh_relight, _lib.nero_relight_workspace_bytes),
+          (True, 0): (_lib.nero_bvh_relight_mis, _lib.nero_relight_mis_workspace_bytes),
+          (False, 1): (_lib.nero_bvh_relight_bounce, _lib.nero_relight_bounce_workspace_bytes),
+          (True, 1): (_lib.nero_bvh_relight_mis_bounce, _lib.nero_relight_mis_bounce_workspace_bytes)}
+
+
+def _relight_chunks(tracer, pt, tab_d, tab_s, tab_l, rand_l, table, env, convention, rot, clamp, geometry_type, chunk, bounces, mesh, key):
+    """relight_points' work: slices of `chunk` points through one fused entry point -- tab_l picks the MIS ones, bounces the bounce ones --
+    into one workspace -> rgb_lin, diffuse_lin, spec_lin [P,3], and indirect_lin with bounces"""
+    mis = tab_l is not None
+    fused, sizer = _FUSED[mis, bounces]
+    P, Dd, Ds, Dl = pt.shape[0], tab_d.shape[0], tab_s.shape[0], tab_l.shape[0] if mis else 0
+    counts = (Dd, Ds, Dl) if mis else (Dd, Ds)
     pad = padded_samples(Dd, Ds, Dl)
     most = max(1, MAX_LANES // pad)
     chunk = max(1, DEFAULT_CHUNK_LANES // pad) if chunk is None else int(chunk)
     chunk = max(1, min(chunk, most))
     dev = pt.device
-    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(3)]
+    out = [torch.zeros(P, 3, dtype=torch.float32, device=dev) for _ in range(4 if bounces else 3)]
     env = env.float().contiguous()
     conv, rot_arg = int(CONVENTIONS.get(convention, convention)), _rot_arg(rot)
-    if table is None:
+    if bounces:
+        verts, tris, mat5, normals = _mesh_args(mesh, dev)
+        mesh_args = (L.ptr(verts), verts.shape[0], L.ptr(tris), tris.shape[0], L.ptr(mat5), L.ptr(normals))
+        kk = _key_arg(key, P, dev)
+    if mis and table is None:
         table = light_table(env, conv, rot, clamp)
-    assert (table.gh, table.gw) == tuple(env.shape[:2]), 'the light table is not this map\'s'
+    if mis:
+        assert (table.gh, table.gw) == tuple(env.shape[:2]), 'the light table is not this map\'s'
     rl = None if rand_l is None else rand_l.float().contiguous()
+    env_args = (L.ptr(env), env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0)) + ((L.ptr(table.cdf), L.ptr(table.info)) if mis else ())
     with torch.cuda.device(dev):
-        need = int(_lib.nero_relight_mis_workspace_bytes(min(chunk, max(P, 1)), Dd, Ds, Dl))
+        need = int(sizer(min(chunk, max(P, 1)), *counts))
         ws = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
         for i in range(0, P, chunk):
-            n = min(chunk, P - i)
-            L.check(_lib.nero_bvh_relight_mis(tracer._handle(), L.ptr(pt[i:i + n]), L.ptr(tab_d), L.ptr(tab_s), L.ptr(tab_l),
-                                              None if rl is None else L.ptr(rl[i:i + n]), n, Dd, Ds, Dl, int(geometry_type), L.ptr(env),
-                                              env.shape[0], env.shape[1], conv, rot_arg, float(clamp or 0.0), L.ptr(table.cdf), L.ptr(table.info),
-                                              L.ptr(out[0][i:i + n]), L.ptr(out[1][i:i + n]), L.ptr(out[2][i:i + n]), L.ptr(ws), ws.numel(),
-                                              L.stream_ptr()))
+            at = slice(i, i + min(chunk, P - i))
+            light = (L.ptr(tab_l), None if rl is None else L.ptr(rl[at])) if mis else ()
+            scene = (*mesh_args, None if kk is None else L.ptr(kk[at])) if bounces else ()
+            L.check(fused(tracer._handle(), L.ptr(pt[at]), L.ptr(tab_d), L.ptr(tab_s), *light, at.stop - i, *counts, int(geometry_type), *env_args,
+                          *scene, *[L.ptr(o[at]) for o in out], L.ptr(ws), ws.numel(), L.stream_ptr()))
     return tuple(out)
 
 

@@ -1,4 +1,4 @@
-"""Plain torch / numpy restatement of the relighter's one bounce (nero_amd/csrc/relight_bounce.hip, include/nero_hip_bounce.h), dtype-generic:
+"""Plain torch / numpy restatement of the relighter's one bounce (nero_amd/csrc/relight_estimator.hip, include/nero_hip_bounce.h), dtype-generic:
 one source serves float64 and float32.  It stands on tests/relight_ref.py (closest_hit, occluded, interpolate, env_lookup), tests/
 envsample_ref.py (draw, pdf_light, lookup_cell, brdf_terms, mis_estimator) and tests/mc_shade_ref.py (point_setup, estimator); what it adds
 is the counter hash, the choice of the strategy, the surface record at the hit, the per-lane secondary direction and L_o.

@@ -1,4 +1,4 @@
-"""CPU tier of the relighter's one bounce (include/nero_hip_bounce.h, nero_amd/csrc/relight_bounce.hip): the sixth header is bound through
+"""CPU tier of the relighter's one bounce (include/nero_hip_bounce.h, nero_amd/csrc/relight_estimator.hip): the sixth header is bound through
 _lib.py beside the pinned five, the entry points refuse bad arguments before any device call, the workspace arithmetic holds at its limits
 under the sanitizers, and the restatement (tests/bounce_ref.py) is checked against closed forms and quadrature: a point under a disk, the
 one-sample secondary estimator's expectation, a convex mesh.  The committed cases of the GPU tier are checked here, with the restatement
@@ -135,7 +135,7 @@ def test_entry_points_refuse_bad_arguments_without_a_device(RL):
 
 # ---- 3. the workspace arithmetic ------------------------------------------------------------------------------------------------------------
 def test_workspace_arithmetic_at_the_limits_under_the_sanitizers(tmp_path):
-    """nero_amd/csrc/relight_bounce_plan.h as a stand-alone program built with -fsanitize=address,undefined"""
+    """nero_amd/csrc/relight_plan.h with the bounce's partial, as a stand-alone program built with -fsanitize=address,undefined"""
     cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
     exe = str(tmp_path / 'relight_bounce_plan')
     subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',

@@ -382,3 +382,55 @@ def test_the_script_takes_bounces(RL, tmp_path):
         assert np.array_equal(img[..., 3], direct[..., 3]) and not np.array_equal(img, direct)
     bad = subprocess.run(cmd[:-1] + ['2'], capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and 'bounces' in bad.stderr
+
+
+# ---- the width of a wavefront's partial -------------------------------------------------------------------------------------------------------
+GUARD = 256
+
+
+@pytest.mark.parametrize('mode', [0, 1])
+@pytest.mark.parametrize('bounces', [0, 1])
+@pytest.mark.parametrize('Dd,Ds,Dl', [(3, 2, 0), (33, 32, 0), (16, 16, 32), (33, 32, 7)])
+def test_a_fused_call_writes_all_of_its_workspace_and_nothing_beyond(RL, L, tracers, Dd, Ds, Dl, bounces, mode):
+    """each of the four fused entry points through the C ABI, on both walks, with a workspace of exactly the bytes its sizer states, cut
+    from the middle of a buffer of 0xFF bytes (an unwritten partial reads as NaN): the 256 bytes on either side stay 0xFF, every output is
+    finite, and every output has the bits of the same call with four times the workspace.  One padded wavefront per point, two with the
+    second nearly empty, exactly one full, and two under the MIS estimator -- six floats per wavefront, twelve with the bounce."""
+    P_, lib = 3, L.lib
+    tr = tracers['corner']
+    s = _device_case(RL, tr, 7, P_, Dd, Ds, Dl, 'corner')
+    mis = Dl > 0
+    counts = (Dd, Ds, Dl) if mis else (Dd, Ds)
+    fused, sizer = {(False, 0): (lib.nero_bvh_relight, lib.nero_relight_workspace_bytes),
+                    (True, 0): (lib.nero_bvh_relight_mis, lib.nero_relight_mis_workspace_bytes),
+                    (False, 1): (lib.nero_bvh_relight_bounce, lib.nero_relight_bounce_workspace_bytes),
+                    (True, 1): (lib.nero_bvh_relight_mis_bounce, lib.nero_relight_mis_bounce_workspace_bytes)}[mis, bounces]
+    need = int(sizer(P_, *counts))
+    assert need == P_ * ((Dd + Ds + Dl + 63) // 64) * (12 if bounces else 6) * 4
+    tab_d, tab_s, env = s['tab_d'].cuda(), s['tab_s'].cuda(), s['env'].cuda().float().contiguous()
+    light = (L.ptr(s['mis']['tab_l']), L.ptr(s['mis']['rand_l'].float().contiguous())) if mis else ()
+    env_args = (L.ptr(env), env.shape[0], env.shape[1], int(RL.CONVENTIONS.get(s['conv'], s['conv'])), RL._rot_arg(s['rot']), float(s['clamp'] or 0.0))
+    if mis:
+        env_args += (L.ptr(s['table'].cdf), L.ptr(s['table'].info))
+    V, Fc, vm, nrm = s['mesh_dev']
+    key = RL._key_arg(s['key_dev'], P_, V.device)
+    scene = (L.ptr(V), V.shape[0], L.ptr(Fc), Fc.shape[0], L.ptr(vm), L.ptr(nrm), L.ptr(key)) if bounces else ()
+
+    def call(ws):
+        out = [torch.full((P_, 3), float('nan'), device='cuda') for _ in range(4 if bounces else 3)]
+        L.check(fused(tr._handle(), L.ptr(s['pt']), L.ptr(tab_d), L.ptr(tab_s), *light, P_, *counts, 0, *env_args, *scene, *[L.ptr(o) for o in out],
+                      L.ptr(ws), ws.numel(), L.stream_ptr()))
+        torch.cuda.synchronize()
+        return out
+
+    L.check(lib.nero_bvh_set_traversal(tr._handle(), mode))
+    try:
+        buf = torch.full((GUARD + need + GUARD,), 0xFF, dtype=torch.uint8, device='cuda')
+        got = call(buf[GUARD:GUARD + need])
+        roomy = call(torch.full((4 * need,), 0xFF, dtype=torch.uint8, device='cuda'))
+    finally:
+        L.check(lib.nero_bvh_set_traversal(tr._handle(), 1))
+    assert bool((buf[:GUARD] == 0xFF).all()) and bool((buf[GUARD + need:] == 0xFF).all())
+    for k, (a, b) in enumerate(zip(got, roomy)):
+        assert bool(torch.isfinite(a).all()), k
+        assert torch.equal(_bits(a), _bits(b)), k
