@@ -509,6 +509,8 @@ int nero_mat_loss_bwd(const nero_mat_loss_cfg* cfg, int P, int has_reg, const fl
  * nero_occ_select: flag [n] (nero_occ_candidates) -> counts = (kept = min(total, cap), total); cand [cap] = the sample indices of the
  *   kept candidates in ascending order, -1 in unused slots.  Above the cap the kept ones are the `cap` smallest keys[ordinal]
  *   (ordinal = rank of the candidate among the candidates; ties to the lower ordinal): argsort(keys[:total], stable)[:cap], sorted.
+ *   A candidate whose key is +inf ranks behind every finite key, by ordinal, and ahead of every sample that is no candidate.  A key
+ *   that is a positive NaN ranks behind +inf and still ahead of the non-candidates, as in torch.argsort; -0.0 ties with +0.0.
  *   Nothing is read back: every launch covers the worst case n.  ws: nero_occ_select_workspace(n) bytes.
  * nero_occ_gather: pts / dirs [cap,3] = x4[cand, 0:3] / geo[cand, 4:7] (the reflected direction); unused slots: origin, +z.
  * nero_occ_l1: loss[0] = sum over the used slots k of |occ_prob[cand[k]] - gt[k]| / max(counts[0], 1) -- F.l1_loss(occ_prob[cand], gt) of

@@ -3,7 +3,7 @@
 // glue cost 0.75 ms at every batch size -- 14 % of the reference's own 512-ray step, scripts/r04/glue_floor.py):
 //   nero_near_far_sphere   near / far of the unit sphere along every ray                  (network/renderer.py:224-230)
 //   nero_occ_select        the occlusion-loss candidate subset, on the device: one stable radix sort (hipCUB) of (key of the candidate's
-//                          ordinal | +inf, sample index) over ALL inner samples, then the first min(#candidates, cap) indices in
+//                          ordinal as an ordered unsigned | 0xFFFFFFFF, sample index) over ALL inner samples, then the first min(#candidates, cap) indices in
 //                          ascending order -- what torch.nonzero + argsort(keys, stable)[:cap] + sort did with a host read-back of
 //                          the candidate count (network/renderer.py:535-541).  Launch sizes depend on n only.
 //   nero_occ_gather        surface points / reflected directions of the kept candidates into a FIXED-capacity batch (unused slots
@@ -20,7 +20,7 @@
 #include <stdint.h>
 #include "../../include/nero_hip.h"
 #include "common.h"
-#include "device_prims.h"                            // block_tree_sum
+#include "device_prims.h"                            // block_tree_sum, f2o
 #include "shade_math.h"                              // sgn
 
 namespace {
@@ -86,11 +86,20 @@ __global__ __launch_bounds__(LB) void occ_scan_kernel(int* __restrict__ blk, int
     }
     if (threadIdx.x == 0) { counts[0] = run < cap ? run : cap; counts[1] = run; }
 }
-// sort records of the subset selection: every sample i gets (key, i) with key = keys[ordinal of i among the candidates] for a candidate
-// and +inf otherwise -- a STABLE sort by key then lists the candidates by (key, ordinal), i.e. argsort(keys[:Pn], stable), with the
-// non-candidates behind them
+// sort records of the subset selection: every sample i gets (key, i) with key = the ordered unsigned image (nero_prims::f2o) of
+// keys[ordinal of i among the candidates] for a candidate and 0xFFFFFFFF otherwise -- a STABLE sort by key then lists the candidates by
+// (key, ordinal), i.e. argsort(keys[:Pn], stable), with the non-candidates behind them.  A float key of +inf for the non-candidates would
+// tie with a candidate whose own key is +inf (both callers pad injected keys with it) and hand its place to every non-candidate of a
+// lower index; as unsigned, +inf (0xFF800000) and the positive NaNs behind it stay below 0xFFFFFFFF.  -0.0 counts as +0.0, as in a float
+// sort; a candidate's image is kept below the non-candidates' whatever its bits.
+constexpr unsigned KEY_NOT_A_CANDIDATE = 0xFFFFFFFFu;
+__device__ __forceinline__ unsigned candidate_key(float k) {
+    const unsigned u = nero_prims::f2o(k);
+    if (u == 0x7FFFFFFFu) return 0x80000000u;            // -0.0 -> +0.0
+    return u < KEY_NOT_A_CANDIDATE ? u : KEY_NOT_A_CANDIDATE - 1u;
+}
 __global__ __launch_bounds__(LB) void occ_records_kernel(const unsigned char* __restrict__ flag, int n, const int* __restrict__ blk,
-                                                         const float* __restrict__ keys, float* __restrict__ skey, int* __restrict__ sval) {
+                                                         const float* __restrict__ keys, unsigned* __restrict__ skey, int* __restrict__ sval) {
     __shared__ int lds[LB];
     const int base = blockIdx.x * SB + 4 * threadIdx.x;
     int f[4], c = 0;
@@ -101,7 +110,7 @@ __global__ __launch_bounds__(LB) void occ_records_kernel(const unsigned char* __
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (base + j < n) {
-            skey[base + j] = f[j] ? keys[p] : INFINITY;
+            skey[base + j] = f[j] ? candidate_key(keys[p]) : KEY_NOT_A_CANDIDATE;
             sval[base + j] = base + j;
             p += f[j];
         }
@@ -277,7 +286,7 @@ int nero_near_far_sphere(const float* o, const float* d, int R, float* near, flo
 static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 static size_t occ_sort_temp_bytes(int n) {
     size_t bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const float*)nullptr, (float*)nullptr, (const int*)nullptr, (int*)nullptr, n);
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const int*)nullptr, (int*)nullptr, n);
     return bytes;
 }
 size_t nero_occ_select_workspace(int n) {
@@ -296,8 +305,8 @@ int nero_occ_select(const unsigned char* flag, int n, const float* keys, int cap
     const int nb = (n + SB - 1) / SB;
     char* p = (char*)ws;
     int* blk = (int*)p;                 p += align256((size_t)(nb + 1) * 4);
-    float* skey = (float*)p;            p += align256((size_t)n * 4);
-    float* skey2 = (float*)p;           p += align256((size_t)n * 4);
+    unsigned* skey = (unsigned*)p;      p += align256((size_t)n * 4);
+    unsigned* skey2 = (unsigned*)p;     p += align256((size_t)n * 4);
     int* sval = (int*)p;                p += align256((size_t)n * 4);
     int* sval2 = (int*)p;               p += align256((size_t)n * 4);
     size_t temp_bytes = occ_sort_temp_bytes(n);
