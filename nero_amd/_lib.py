@@ -19,6 +19,8 @@ LATER_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h i
 BOUNCE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_bounce.h',))
 # ... and the seventh header, after the tests of the sixth pinned that one: the same rule again
 NORMALS_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_normals.h',))
+# ... and the eighth, after the tests of the seventh pinned that one too
+DENOISE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_denoise.h',))
 
 MAX_LAYERS = 10
 HID = 256
@@ -155,7 +157,8 @@ def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS)       # one parse_headers over all of them: a name twice is an ImportError
+    # one parse_headers over all of them: a name twice is an ImportError
+    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS + DENOISE_HEADER_PATHS)
 
 
 lib = _load()

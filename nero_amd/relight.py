@@ -5,7 +5,8 @@ Camera rays go through nero_bvh_trace_faces (depth, face, barycentrics), the per
 nero_bvh_relight evaluates the reference's shade_mixed estimator with "environment radiance if the shadow ray is free, zero if it is
 blocked" for the light -- one fused kernel that never stores a ray.  With bounces=1 a blocked direction is not black: it fetches the light
 the surface it meets sends back under its own direct lighting (one bounce, one sample, a shadow ray of its own; include/nero_hip_bounce.h,
-DESIGN.md 9.12.2).  Smooth shading takes per-vertex normals, the caller's or computed here (normals='angle' / 'area').  NOT
+DESIGN.md 9.12.2).  Smooth shading takes per-vertex normals, the caller's or computed here (normals='angle' / 'area').  render(denoise=True)
+filters the noise a sample count leaves with a single-frame edge-aware filter (nero_amd/denoise.py).  NOT
 modelled: more than one bounce, texture maps as input.
 This is not Cycles.
 
@@ -478,7 +479,7 @@ class Relighter:
         nrm = torch.nn.functional.normalize(nrm, dim=-1)
         return {'depth': depth, 'hit': hit, 'idx': idx, 'pts': pts, 'normal': nrm, 'mat5': mat5}
 
-    def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None, bounces=None):
+    def render(self, pose, K, h, w, samples=(128, 128), ssaa=1, seed=0, chunk=None, clamp=None, background=None, bounces=None, denoise=None):
         """one view -> dict of device tensors [h,w,C]: rgb_lin (linear), rgb (linear_to_srgb, clipped to [0,1]), alpha (coverage), albedo,
         metallic, roughness (perceptual), normal, depth (10 where nothing is hit), and rgba8 uint8 [h,w,4] (straight alpha).  samples = (Dd,
         Ds) directions per pixel, or (Dd, Ds, Dl) with Dl more drawn from the map itself and all three combined by multiple importance
@@ -487,8 +488,19 @@ class Relighter:
         environment's radiance per channel (firefly control; it darkens the picture, the third sample count does not); background: linear rgb [3] or
         [h,w,3] behind the uncovered part of a pixel (None: zeros there, rgb_lin is the straight colour); bounces: 0 = direct lighting
         (None: the relighter's default, 0 unless it was built otherwise), 1 = a blocked direction fetches the light of the surface it meets
-         -- rgb_lin then holds both, and indirect_lin [h,w,3] the bounced part alone, through the same filter."""
+         -- rgb_lin then holds both, and indirect_lin [h,w,3] the bounced part alone, through the same filter.
+        denoise: None or False = off, the bits of a call without the argument; True, or a dict of nero_amd.denoise.denoise's parameters (iterations, sigma_l,
+        normal_pow2, sigma_p, sigma_g), filters three signals at the traced resolution (ssaa h x ssaa w), before the box filter (DESIGN.md
+        9.12.3): the diffuse term divided by max(albedo (1 - metallic), 1e-4), filtered and multiplied back, so that the filter sees the
+        light and not the surface's colour; the specular term; with bounces the indirect term -- the last two with (roughness, metallic,
+        luminance of the albedo, 0) as extra guide channels.  rgb_lin is then the sum of the filtered signals, indirect_lin the filtered
+        one, and rgb_lin_raw the unfiltered sum through the same box filter and background.  sigma_p defaults to 0.015 x the diagonal of
+        the mesh's bounding box: a constant carried over from the analytic scene the filter was prototyped on, NOT tuned on a real render."""
         bounces = self.bounces if bounces is None else bounces
+        dn = None
+        if denoise is not None and denoise is not False:
+            from . import denoise as DN
+            dn = DN.options(denoise, 0.015 * float((self.verts.max(0).values - self.verts.min(0).values).norm()))
         if bounces not in (0, 1):
             raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
         s = int(ssaa)
@@ -504,6 +516,7 @@ class Relighter:
             Dd, Ds = int(samples[0]), int(samples[1])
             rgb = torch.zeros(H * W, 3, device=self.device)
             ind = torch.zeros(H * W, 3, device=self.device) if bounces else None
+            raw = rgb                                                     # (the unfiltered sum, where a filter replaces rgb below)
             if m > 0:
                 rand_d, rand_s = pixel_rotations(idx, seed)
                 pt = point_records(sf['pts'], -rays_d[idx], sf['normal'], estimator_materials(sf['mat5']), rand_d, rand_s)
@@ -516,6 +529,9 @@ class Relighter:
                 rgb[idx] = got[0]
                 if bounces:
                     ind[idx] = got[3]
+                if dn is not None:
+                    raw = rgb
+                    rgb, ind = self._denoise(dn, H, W, sf, got, bounces)
             alpha = sf['hit'].float().reshape(H * W, 1)
             full = lambda x: torch.zeros(H * W, x.shape[1], device=self.device).index_copy_(0, idx, x)
             planes = torch.cat([rgb, full(sf['mat5']), full(sf['normal']), (sf['depth'].reshape(-1, 1) * alpha), alpha], -1)    # premultiplied
@@ -535,8 +551,34 @@ class Relighter:
             if bounces:                                                   # the same box filter and the same straightening as rgb_lin's
                 ip = ind.reshape(h, s, w, s, 3).mean((1, 3))
                 extra['indirect_lin'] = torch.where(a > 0, ip / torch.clamp(a, min=1e-12), torch.zeros_like(ip))
+            if dn is not None:                                            # ... and the same background
+                rp = raw.reshape(h, s, w, s, 3).mean((1, 3))
+                extra['rgb_lin_raw'] = (torch.where(a > 0, rp / torch.clamp(a, min=1e-12), torch.zeros_like(rp)) if background is None
+                                        else rp + (1.0 - a) * bg.expand(h, w, 3))
         return {**extra, 'rgb_lin': rgb_lin, 'rgb': srgb, 'alpha': a, 'albedo': straight[..., 5:8], 'metallic': straight[..., 3:4],
                 'roughness': straight[..., 4:5], 'normal': nrm, 'depth': depth, 'rgba8': rgba8}
+
+    def _denoise(self, dn, H, W, sf, got, bounces):
+        """render(denoise=...)'s filter at the traced resolution: got = relight_points' (rgb, diffuse, specular[, indirect]) over the hit
+        pixels sf['idx'] -> (rgb, indirect | None) [H W,3], the filtered signals and their sum"""
+        from . import denoise as DN
+        idx = sf['idx']
+        full = lambda x: torch.zeros(H * W, x.shape[1], device=self.device).index_copy_(0, idx, x)
+        pos, nrm, valid = full(sf['pts']), full(sf['normal']), sf['hit'].reshape(-1)
+        metallic, rough, albedo = sf['mat5'][:, 0:1], sf['mat5'][:, 1:2], sf['mat5'][:, 2:5]
+        demod = full(torch.clamp(albedo * (1.0 - metallic), min=1e-4))
+        lum = (0.2126 * albedo[:, 0:1] + 0.7152 * albedo[:, 1:2]) + 0.0722 * albedo[:, 2:3]
+        guide_mat = DN.pack_guides(pos, nrm, valid, full(torch.cat([rough, metallic, lum, torch.zeros_like(lum)], -1)))
+        guide = guide_mat[:, :8].contiguous()
+        run = lambda g, x: DN.denoise_records(g, DN.pack_signal(x), H, W, dn['iterations'], dn['sigma_l'], dn['normal_pow2'], dn['sigma_p'],
+                                              dn['sigma_g'])[:, :3]
+        diffuse = run(guide, full(got[1]) / torch.where(valid[:, None], demod, torch.ones_like(demod))) * demod
+        rgb = diffuse + run(guide_mat, full(got[2]))
+        ind = None
+        if bounces:
+            ind = run(guide_mat, full(got[3]))
+            rgb = rgb + ind
+        return rgb, ind
 
     def render_orbit(self, out_dir, num=360, azimuth=0.0, elevation=30.0, dist=3.0, h=800, w=800, K=None, **kw):
         """the reference's relighting orbit: view k of relighting_poses(num, azimuth, elevation, dist), as Blender sees it over the mesh's own

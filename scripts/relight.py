@@ -6,7 +6,8 @@
 
 --material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
 materials are predicted from the trained Stage-II network instead.  --normals angle (or area) shades with smooth vertex normals computed
-from the mesh instead of flat face normals.  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
+from the mesh instead of flat face normals.  --denoise filters the picture's signals with the edge-aware denoiser
+(DESIGN.md 9.12.3).  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
 import argparse
 import os
 import sys
@@ -44,8 +45,19 @@ def main(argv=None):
                     help='1: a direction that meets the mesh fetches the light that surface sends back (one inter-reflection) instead of black')
     ap.add_argument('--normals', default='flat', choices=['flat', 'angle', 'area'],
                     help='flat: face normals; angle / area: smooth vertex normals computed from the mesh, face normals weighted by angle or by area')
+    ap.add_argument('--denoise', action='store_true',
+                    help='filter the diffuse, specular and indirect signals with the edge-aware denoiser before they are summed (DESIGN.md 9.12.3): '
+                         'fewer --samples for the same noise')
+    ap.add_argument('--denoise-iterations', type=int, default=None, metavar='N', help='a-trous passes of --denoise (default 5), the stride doubling from 1')
+    ap.add_argument('--denoise-sigma', type=float, default=None, metavar='L',
+                    help='--denoise: how many standard deviations of luminance a tap may differ by (default 4)')
     ap.add_argument('--out', default='data/relight')
     a = ap.parse_args(argv)
+    denoise = None
+    if a.denoise:
+        denoise = {k: v for k, v in (('iterations', a.denoise_iterations), ('sigma_l', a.denoise_sigma)) if v is not None} or True
+    elif a.denoise_iterations is not None or a.denoise_sigma is not None:
+        ap.error('--denoise-iterations and --denoise-sigma need --denoise')
 
     import torch
     from nero_amd.mesh import read_ply
@@ -76,7 +88,7 @@ def main(argv=None):
     rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if a.normals == 'flat' else a.normals)
     out_dir = os.path.join(a.out, a.name)
     paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
-                            samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces)
+                            samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces, denoise=denoise)
     print(f'{len(paths)} views of {a.width} x {a.height} at {"+".join(str(n) for n in samples)} samples, {a.bounces} bounces -> {out_dir}')
 
 
