@@ -21,6 +21,8 @@ BOUNCE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h 
 NORMALS_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_normals.h',))
 # ... and the eighth, after the tests of the seventh pinned that one too
 DENOISE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_denoise.h',))
+# ... and the ninth, after the tests of the eighth pinned that one as well
+TEXFETCH_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_texfetch.h',))
 
 MAX_LAYERS = 10
 HID = 256
@@ -158,7 +160,8 @@ def _load():
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
     # one parse_headers over all of them: a name twice is an ImportError
-    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS + DENOISE_HEADER_PATHS)
+    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS + DENOISE_HEADER_PATHS
+                + TEXFETCH_HEADER_PATHS)
 
 
 lib = _load()

@@ -6,8 +6,9 @@ nero_bvh_relight evaluates the reference's shade_mixed estimator with "environme
 blocked" for the light -- one fused kernel that never stores a ray.  With bounces=1 a blocked direction is not black: it fetches the light
 the surface it meets sends back under its own direct lighting (one bounce, one sample, a shadow ray of its own; include/nero_hip_bounce.h,
 DESIGN.md 9.12.2).  Smooth shading takes per-vertex normals, the caller's or computed here (normals='angle' / 'area').  render(denoise=True)
-filters the noise a sample count leaves with a single-frame edge-aware filter (nero_amd/denoise.py).  NOT
-modelled: more than one bounce, texture maps as input.
+filters the noise a sample count leaves with a single-frame edge-aware filter (nero_amd/denoise.py).
+Relighter(textures=...) reads the materials from the UV maps bake_materials writes instead of per vertex, through a mip pyramid with a
+trilinear fetch (nero_amd/texfetch.py).  NOT modelled: more than one bounce, textures at secondary hits.
 This is not Cycles.
 
 samples = (Dd, Ds) draws every direction from the BRDF; samples = (Dd, Ds, Dl) adds Dl directions drawn from the map itself (light_table,
@@ -389,16 +390,32 @@ class Relighter:
     1); env_rotation: 3 x 3, applied to a direction before the lookup; tracer: a RayTracer over the same mesh to share, else one is built
     (`build`); normals: per-vertex [V,3] for smooth shading, 'angle' or 'area' to compute them from the mesh (nero_amd.mesh.vertex_normals,
     stored outward; the flat normal stands in wherever one has no direction), else flat face normals turned towards the camera; bounces:
-    render()'s default."""
+    render()'s default.
+    textures: None, or the dict read_textured_obj or bake_materials returns -- 'albedo' uint8 [h,w,3], 'metallic', 'roughness' uint8 [h,w]
+    (every channel sRGB-encoded, the roughness channel holding alpha), 'vt' [Vt,2], 'ft' [T,3] -- and `materials` may then be None: the
+    camera's hits take their materials from the maps, filtered to the pixel's footprint (nero_amd/texfetch.py; DESIGN.md 9.12.4);
+    lod_bias shifts the level of detail (+1: one level blurrier).  self.mat5 is then texfetch.vertex_materials: one level-0 fetch per
+    vertex, which is what the bounce kernels shade the surface at a SECONDARY hit from -- an approximation: a bounce sees the maps at
+    the vertex spacing.  Without textures nothing changes."""
 
     def __init__(self, verts, tris, materials, env, convention='blender', env_rotation=None, tracer=None, build='device',
-                 geometry_type='schlick', normals=None, device=None, bounces=0):
+                 geometry_type='schlick', normals=None, device=None, bounces=0, textures=None, lod_bias=0.0):
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         as_t = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
         self.device = dev
         self.verts, self.tris = as_t(verts, torch.float32).reshape(-1, 3), as_t(tris, torch.int64).reshape(-1, 3)
         V = self.verts.shape[0]
-        self.mat5 = torch.cat([as_t(materials[k], torch.float32).reshape(V, -1) for k in ('metallic', 'roughness', 'albedo')], -1)   # perceptual
+        self.textures, self.lod_bias = None, float(lod_bias)
+        if textures is not None:
+            from . import texfetch
+            self.textures = texfetch.TextureSet(textures['albedo'], textures['metallic'], textures['roughness'], device=dev)
+            self.vt, self.ft = as_t(textures['vt'], torch.float32).reshape(-1, 2), as_t(textures['ft'], torch.int32).reshape(-1, 3)
+            if self.ft.shape != self.tris.shape:
+                raise ValueError(f'textures: ft has {self.ft.shape[0]} faces, the mesh {self.tris.shape[0]}')
+            self.face_scale = texfetch.face_scale(self.verts, self.tris.int(), self.vt, self.ft, self.textures.h, self.textures.w)
+            self.mat5 = texfetch.vertex_materials(self.textures, self.vt, self.tris.int(), self.ft, V)       # the bounce kernels' stand-in
+        else:
+            self.mat5 = torch.cat([as_t(materials[k], torch.float32).reshape(V, -1) for k in ('metallic', 'roughness', 'albedo')], -1)   # perceptual
         assert self.mat5.shape[1] == 5, self.mat5.shape
         # 'angle' / 'area': smooth normals computed here, once, and stored OUTWARD whatever the winding (the bounce kernels read them at
         # secondary hits without turning them); where they fail (zero, not finite) surface() falls back to the flat normal
@@ -429,6 +446,17 @@ class Relighter:
             raise ValueError(f'bounces {bounces!r}: 0 (direct lighting) or 1 (one inter-reflection)')
         self.bounces = bounces                                          # what render() takes when it is not told
 
+    @classmethod
+    def from_asset(cls, obj_path, env, **kw):
+        """the textured asset write_textured_obj stored -- <name>.obj with its MTL and the three maps beside it -- under `env`; **kw: the
+        other arguments of Relighter"""
+        from .texture import read_textured_obj
+        asset = read_textured_obj(obj_path)
+        missing = [k for k in ('albedo', 'metallic', 'roughness') if k not in asset]
+        if missing:
+            raise ValueError(f'{obj_path}: no {", ".join(missing)} map beside it (the MTL names {asset["map_Kd"]!r})')
+        return cls(asset['v'], asset['f'], None, env, textures=asset, **kw)
+
     def light_table(self, clamp=None):
         """the map's sampling table under this relighter's convention and rotation, one per cap (the cap changes the weights)"""
         key = float(clamp or 0.0)
@@ -453,9 +481,10 @@ class Relighter:
         rays_o = (-Rm.permute(0, 2, 1) @ t).permute(0, 2, 1).repeat(1, h * w, 1)
         return rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
 
-    def surface(self, rays_o, rays_d):
+    def surface(self, rays_o, rays_d, spread=None):
         """trace and interpolate -> dict: depth [n], hit [n] bool, idx [m] (the hit rays), and for those pts, normal, mat5 (PERCEPTUAL
-        roughness) [m,.]"""
+        roughness) [m,.].  With textures mat5 is fetched from the maps at the hits' UVs: spread is the width of a ray's footprint at unit
+        distance, which sets the level of detail (None: level 0); without textures it is not read"""
         depth, face, bary = trace_faces(self.tracer, rays_o, rays_d)
         hit = face >= 0
         idx = torch.nonzero(hit)[:, 0]
@@ -464,7 +493,11 @@ class Relighter:
         wts = torch.stack([1.0 - u - v, u, v], 1)                                            # [m,3,1]
         corner = self.verts[f]                                                               # [m,3,3]
         pts = (wts * corner).sum(1)
-        mat5 = (wts * self.mat5[f]).sum(1)
+        if self.textures is not None:
+            from . import texfetch
+            mat5 = texfetch.fetch_materials(self.textures, self.vt, self.ft, self.face_scale, face[idx], bary[idx], depth[idx], spread, self.lod_bias)
+        else:
+            mat5 = (wts * self.mat5[f]).sum(1)
         if self.normals is None or self._computed_normals:
             # the flat normal on the side the ray came from: the meshes of extract_mesh.py are wound inwards (the reference's trace() negates the
             # tracer's normals), others outwards -- the side a camera ray meets of a closed mesh is its outside either way
@@ -509,7 +542,8 @@ class Relighter:
         Ks = np.diag([float(s), float(s), 1.0]).astype(np.float32) @ np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float32).reshape(3, 3)
         with torch.no_grad():
             rays_o, rays_d = self.camera_rays(pose, Ks, H, W)
-            sf = self.surface(rays_o, rays_d)
+            # (textured: a pixel's width at unit distance at the traced resolution sets the level of detail)
+            sf = self.surface(rays_o, rays_d) if self.textures is None else self.surface(rays_o, rays_d, spread=1.0 / float(Ks[0, 0]))
             idx, m = sf['idx'], int(sf['idx'].numel())
             if len(samples) not in (2, 3):
                 raise ValueError(f'samples {samples!r}: (Dd, Ds) or (Dd, Ds, Dl)')

@@ -3,8 +3,11 @@
 
     python scripts/relight.py --mesh M.ply --material DIR --hdr E.hdr --name N
     python scripts/relight.py --mesh M.ply --cfg configs/material/x.yaml --model model.pth --hdr E.hdr --name N
+    python scripts/relight.py --mesh mesh_0.obj --textured --hdr E.hdr --name N
 
---material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
+--textured: --mesh is the textured OBJ extract_texture_maps.py wrote, with its MTL and the albedo / metallic / roughness maps beside it; the
+materials are read from the maps at every hit, filtered to the pixel's footprint; --lod-bias B shifts the level of detail
+(+1: one level blurrier).  --material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
 materials are predicted from the trained Stage-II network instead.  --normals angle (or area) shades with smooth vertex normals computed
 from the mesh instead of flat face normals.  --denoise filters the picture's signals with the edge-aware denoiser
 (DESIGN.md 9.12.3).  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
@@ -51,8 +54,15 @@ def main(argv=None):
     ap.add_argument('--denoise-iterations', type=int, default=None, metavar='N', help='a-trous passes of --denoise (default 5), the stride doubling from 1')
     ap.add_argument('--denoise-sigma', type=float, default=None, metavar='L',
                     help='--denoise: how many standard deviations of luminance a tap may differ by (default 4)')
+    ap.add_argument('--textured', action='store_true',
+                    help='--mesh is a textured OBJ (write_textured_obj): read the materials from its maps instead of --material / --cfg and --model')
+    ap.add_argument('--lod-bias', type=float, default=None, metavar='B', help='--textured: levels added to the level of detail (default 0)')
     ap.add_argument('--out', default='data/relight')
     a = ap.parse_args(argv)
+    if a.lod_bias is not None and not a.textured:
+        ap.error('--lod-bias needs --textured')
+    if a.textured and (a.material or a.cfg or a.model):
+        ap.error('--textured reads the materials from the maps: give no --material, --cfg or --model')
     denoise = None
     if a.denoise:
         denoise = {k: v for k, v in (('iterations', a.denoise_iterations), ('sigma_l', a.denoise_sigma)) if v is not None} or True
@@ -62,9 +72,19 @@ def main(argv=None):
     import torch
     from nero_amd.mesh import read_ply
     from nero_amd.relight import Relighter, load_materials
-    verts, tris = read_ply(a.mesh)
+    textures, materials = None, None
+    if a.textured:
+        from nero_amd.texture import read_textured_obj
+        textures = read_textured_obj(a.mesh)
+        if not all(k in textures for k in ('albedo', 'metallic', 'roughness')):
+            raise SystemExit(f'{a.mesh}: the albedo, metallic and roughness maps its MTL names are not beside it')
+        verts, tris = textures['v'], textures['f']
+    else:
+        verts, tris = read_ply(a.mesh)
     verts = np.asarray(verts, np.float32)
-    if a.material:
+    if a.textured:
+        materials = None                                                  # (Relighter fetches them from the maps)
+    elif a.material:
         materials = load_materials(a.material)
     elif a.cfg and a.model:
         import yaml
@@ -78,14 +98,15 @@ def main(argv=None):
         materials = net.predict_materials_of_vertices(torch.from_numpy(verts).cuda())
     else:
         ap.error('give --material DIR, or --cfg and --model')
-    if materials['albedo'].shape[0] != verts.shape[0]:
+    if materials is not None and materials['albedo'].shape[0] != verts.shape[0]:
         raise SystemExit(f"{materials['albedo'].shape[0]} material rows for {verts.shape[0]} vertices: --material does not belong to --mesh")
     if a.trans:                                                           # (x, y, z) -> (x, -z, y)
         verts = verts @ np.asarray([[1, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32).T
     if len(a.samples) > 3 or min(a.samples) < 1:
         ap.error('--samples takes one to three positive integers')
     samples = tuple(a.samples) if len(a.samples) == 3 else tuple((a.samples * 2)[:2])
-    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if a.normals == 'flat' else a.normals)
+    tex_kw = dict(textures=textures, lod_bias=a.lod_bias or 0.0) if a.textured else {}
+    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if a.normals == 'flat' else a.normals, **tex_kw)
     out_dir = os.path.join(a.out, a.name)
     paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
                             samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces, denoise=denoise)
