@@ -9,20 +9,11 @@ import torch  # noqa: F401  -- must come first: libnero_hip.so has to bind to th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERO_HIP_LIB') or os.path.join(_HERE, 'libnero_hip.so')     # (override: kernel-variant experiments)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'nero_hip.h')
-# every public header of the library, in the order the build lists them; an entry point is declared in exactly one of them
+# every public header of the library, in the order they were added: the ONE list.  An entry point is declared in exactly one of them, and
+# parse_headers() and bind() read all of them unless told otherwise.  A new header goes into include/ and into this tuple
 HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h)
-                     for h in ('nero_hip.h', 'nero_hip_visibility.h', 'nero_hip_relight.h', 'nero_hip_surface.h'))
-# headers added after the tests of the four above pinned their number and their prototype counts: bound by _load() like those, and held to
-# the same rule (a name is declared once across ALL headers); parse_headers() and bind() keep HEADER_PATHS as their default
-LATER_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_envsample.h',))
-# ... and those added after the tests of the fifth pinned that tuple too: the same rule once more
-BOUNCE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_bounce.h',))
-# ... and the seventh header, after the tests of the sixth pinned that one: the same rule again
-NORMALS_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_normals.h',))
-# ... and the eighth, after the tests of the seventh pinned that one too
-DENOISE_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_denoise.h',))
-# ... and the ninth, after the tests of the eighth pinned that one as well
-TEXFETCH_HEADER_PATHS = tuple(os.path.join(os.path.dirname(HEADER_PATH), h) for h in ('nero_hip_texfetch.h',))
+                     for h in ('nero_hip.h', 'nero_hip_visibility.h', 'nero_hip_relight.h', 'nero_hip_surface.h', 'nero_hip_envsample.h',
+                               'nero_hip_bounce.h', 'nero_hip_normals.h', 'nero_hip_denoise.h', 'nero_hip_texfetch.h'))
 
 MAX_LAYERS = 10
 HID = 256
@@ -112,12 +103,13 @@ def _ctype(decl, fn, ret=False):
     if ret and ctype == 'void':
         return None
     if ctype not in _SCALARS:
-        raise ImportError(f'nero_hip.h: {fn}: no ctypes type for {ctype!r} (in {decl!r})')
+        raise ImportError(f'{fn}: no ctypes type for {ctype!r} (in {decl!r})')
     return _SCALARS[ctype]
 
 
 def parse_header(text):
-    """{function: (restype, argtypes)} for every prototype in `text`, the contents of include/nero_hip.h"""
+    """{function: (restype, argtypes)} for every prototype in `text`, the contents of one public header; parse_headers puts the file's
+    name in front of what this refuses"""
     text = re.sub(r'/\*.*?\*/|//[^\n]*|^\s*#[^\n]*', ' ', text, flags=re.S | re.M)       # comments, preprocessor lines
     sigs = {}
     for ret, fn, params in re.findall(r'([\w\s*]+?)\b(nero_\w+)\s*\(([^()]*)\)\s*;', text):
@@ -125,27 +117,32 @@ def parse_header(text):
         sigs[fn] = (_ctype(ret.strip(), fn, ret=True), [_ctype(p, fn) for p in params])
     names = set(re.findall(r'\b(nero_\w+)\s*\(', text))
     if set(sigs) != names:
-        raise ImportError(f'nero_hip.h: {len(sigs)} prototypes parsed, {len(names)} functions named: {sorted(names ^ set(sigs))}')
+        raise ImportError(f'{len(sigs)} prototypes parsed, {len(names)} functions named: {sorted(names ^ set(sigs))}')
     return sigs
 
 
 def parse_headers(paths=None):
-    """{function: (restype, argtypes, header file name)} over all of `paths` (default HEADER_PATHS), each read by parse_header; a name that
-    two headers declare is an ImportError"""
+    """{function: (restype, argtypes, header file name)} over all of `paths` (default HEADER_PATHS: every public header), each read by
+    parse_header; a name that two headers declare is an ImportError"""
     sigs = {}
     for path in HEADER_PATHS if paths is None else paths:
         name = os.path.basename(path)
         with open(path) as f:
-            for fn, (restype, argtypes) in parse_header(f.read()).items():
-                if fn in sigs:
-                    raise ImportError(f'{name} declares {fn}, which {sigs[fn][2]} declares already')
-                sigs[fn] = (restype, argtypes, name)
+            try:
+                parsed = parse_header(f.read())
+            except ImportError as e:
+                raise ImportError(f'{name}: {e}') from None
+        for fn, (restype, argtypes) in parsed.items():
+            if fn in sigs:
+                raise ImportError(f'{name} declares {fn}, which {sigs[fn][2]} declares already')
+            sigs[fn] = (restype, argtypes, name)
     return sigs
 
 
 def bind(lib, paths=None):
-    """set restype and argtypes of EVERY entry point the headers (`paths`, default HEADER_PATHS) declare on `lib` (a CDLL of libnero_hip.so): a
-    header is the one place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call site hands over"""
+    """set restype and argtypes of EVERY entry point the headers (`paths`, default HEADER_PATHS: all of them) declare on `lib` (a CDLL of
+    libnero_hip.so): a header is the one place a signature is written, so a size_t, an int64_t or a pointer reaches C whole whatever the call
+    site hands over"""
     for fn, (restype, argtypes, header) in parse_headers(paths).items():
         try:
             f = getattr(lib, fn)
@@ -159,9 +156,7 @@ def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                           f'(hipcc --offload-arch=gfx950).  nero_amd has no non-HIP fallback.')
-    # one parse_headers over all of them: a name twice is an ImportError
-    return bind(C.CDLL(LIB_PATH), HEADER_PATHS + LATER_HEADER_PATHS + BOUNCE_HEADER_PATHS + NORMALS_HEADER_PATHS + DENOISE_HEADER_PATHS
-                + TEXFETCH_HEADER_PATHS)
+    return bind(C.CDLL(LIB_PATH))
 
 
 lib = _load()
@@ -203,5 +198,4 @@ def ptr(t):
 
 
 def stream_ptr():
-    import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -1,6 +1,8 @@
 """Shared test helpers: rebuild the golden cases' weights / inputs (tests/golden/*.npz, made by oracle/gen_golden.py)."""
 import json
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import torch
@@ -8,6 +10,20 @@ import torch
 from nero_amd.synthetic import perturb_state
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+
+def run_host_program(tmp_path, main_cpp, sanitize='address,undefined', extra=(), args=()):
+    """stdout of tests/<main_cpp> -- a stand-alone host program with its own main -- built under the sanitizers with the host compiler and run
+    as a child process with `args`, nothing added to its environment: it must exit with 0 and a silent stderr, i.e. no sanitizer report.
+    Built once per tmp_path, so a test may run its program several times."""
+    exe = str(tmp_path / os.path.splitext(main_cpp)[0])
+    if not os.path.exists(exe):
+        cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
+        subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', f'-fsanitize={sanitize}', '-fno-sanitize-recover=all', *extra,
+                               os.path.join(os.path.dirname(os.path.abspath(__file__)), main_cpp), '-o', exe])
+    run = subprocess.run([exe, *args], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
+    return run.stdout
 
 
 def load_golden(name):

@@ -4,13 +4,12 @@ address and undefined-behaviour sanitizers."""
 import ctypes
 import math
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import bvh_build_ref as R
+from tests.helpers import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ('nero_bvh_build_workspace_bytes', 'nero_bvh_build_lds_capacity', 'nero_bvh_create_device', 'nero_bvh_info', 'nero_bvh_export')
@@ -108,15 +107,9 @@ def test_workspace_bytes_needs_no_device():
 def test_planning_header_under_sanitizers(tmp_path):
     """bvh_build_plan.h as a stand-alone program, built with -fsanitize=address,undefined and run as a child process: its level tables, node
     counts, per-level walks and hand-off levels equal the restatement's for every nT in 1 .. 5000"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'bvh_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'bvh_plan_main.cpp'), '-o', exe])
     cap = _lib().nero_bvh_build_lds_capacity()
     for c in (cap, 16):                                           # the library's S, and a small one (more hand-off levels in range)
-        run = subprocess.run([exe, '1', '5000', str(c)], capture_output=True, text=True)
-        assert run.returncode == 0 and run.stderr == '', run.stderr[-2000:]
-        lines = run.stdout.splitlines()
+        lines = run_host_program(tmp_path, 'bvh_plan_main.cpp', args=('1', '5000', str(c))).splitlines()
         assert len(lines) == 5000
         for nT, line in zip(range(1, 5001), lines):
             assert line == R.plan_line(nT, c), nT

@@ -1,4 +1,5 @@
-"""CPU tier: the C-ABI library loads and exports every symbol include/nero_hip.h declares (no compute calls)."""
+"""CPU tier: the C-ABI library loads and exports every symbol include/nero_hip.h declares (no compute calls); that every entry point of
+every header is bound: tests/test_binding_cpu.py."""
 import ctypes
 import os
 import re
@@ -87,36 +88,6 @@ def test_f16_paired_selector_round_trip():
     finally:
         CH.f16_paired(prev)
     assert CH.f16_paired() == prev
-
-
-def _prototypes():
-    """{name: (return type, parameter count)} read off the header by this test's own rule: comments out, then `type name(params);`"""
-    hdr = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', open(os.path.join(ROOT, 'include', 'nero_hip.h')).read(), flags=re.S)
-    protos = {}
-    for ret, name, params in re.findall(r'([\w ]+?[\s*]+)(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', hdr):
-        params = params.strip()
-        protos[name] = (' '.join(ret.replace('*', ' * ').split()), 0 if params in ('', 'void') else params.count(',') + 1)
-    return protos
-
-
-def test_every_declared_symbol_is_bound():
-    """nero_amd._lib.bind gives every entry point of the header its signature: as many argtypes as the prototype has parameters, c_size_t
-    results for the 24 size queries, no result for the two void functions"""
-    from nero_amd import _lib as L
-    hdr = open(os.path.join(ROOT, 'include', 'nero_hip.h')).read()
-    names = sorted(set(re.findall(r'\b(nero_[a-z0-9_]+)\s*\(', hdr)))         # the rule of test_library_exports_every_declared_symbol
-    protos = _prototypes()
-    assert sorted(protos) == names and len(names) == 172
-    for n in names:
-        fn = getattr(L.lib, n)
-        assert fn.argtypes is not None and len(fn.argtypes) == protos[n][1], (n, fn.argtypes, protos[n])
-    sized = [n for n in names if protos[n][0] == 'size_t']
-    void = [n for n in names if protos[n][0] == 'void']
-    assert len(sized) == 24 and len(void) == 2, (sized, void)
-    assert [n for n in names if getattr(L.lib, n).restype is ctypes.c_size_t] == sized
-    assert [n for n in names if getattr(L.lib, n).restype is None] == void
-    assert L.lib.nero_last_error.restype is ctypes.c_char_p
-    assert L.lib.nero_check_device_memory.argtypes == [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p]
 
 
 def test_signatures_are_live():

@@ -3,10 +3,10 @@ tests/chain_host_main.cpp is built with the host compiler under ASan + UBSan -- 
 its pack sizes, pack jobs and chain offsets must be the Python twin's, its arena peaks the ones the header gave before the planner was
 split from its kernels (tests/golden/chain_host_peaks.txt)."""
 import os
-import shutil
-import subprocess
 
 import torch
+
+from tests.helpers import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = (1, 63, 64, 65, 4097)                       # each side of a 64-row tile edge, and many tiles
@@ -15,15 +15,9 @@ NAMES = ('predictor', 'predictor_no_aux', 'feats')
 
 def _program(tmp_path):
     """stdout of the program, as {first word: [the other words of each such line]}"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'chain_host')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           '-I' + os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include'),
-                           os.path.join(ROOT, 'tests', 'chain_host_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
+    stdout = run_host_program(tmp_path, 'chain_host_main.cpp', extra=('-I' + os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include'),))
     out = {}
-    for ln in run.stdout.splitlines():
+    for ln in stdout.splitlines():
         out.setdefault(ln.split()[0], []).append(ln.split()[1:])
     return out
 

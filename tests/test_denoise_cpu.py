@@ -1,21 +1,14 @@
 """CPU tier of the denoiser (include/nero_hip_denoise.h, nero_amd/csrc/denoise.hip, nero_amd/denoise.py): the restatement
-(tests/denoise_ref.py) on an analytic scene -- it lowers the noise, barely moves a clean picture, leaves uncovered pixels alone --, the eighth
-header bound through _lib.py beside the pinned seven, the entry points' refusals before any device call, and the tile and grid arithmetic as
-a stand-alone program under the sanitizers."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
+(tests/denoise_ref.py) on an analytic scene -- it lowers the noise, barely moves a clean picture, leaves uncovered pixels alone --, the
+entry points' refusals before any device call, and the tile and grid arithmetic as a stand-alone program under the sanitizers.  The
+header's binding: tests/test_binding_cpu.py."""
 import numpy as np
 import pytest
 
 from tests import denoise_ref as DR
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_denoise.h')
 ERR_ARG = -1
-NAMES = {'nero_denoise_max_pixels': 0, 'nero_denoise_variance': 10, 'nero_denoise_atrous': 12}
 PARAMS = dict(iterations=5, sigma_l=4.0, normal_pow2=6, sigma_p=0.05)
 
 
@@ -93,39 +86,7 @@ def test_a_constant_signal_and_perpendicular_halves_are_exact_in_the_restatement
     assert np.array_equal(out, rgb) and not var.any()
 
 
-# ---- 2. the surface: binding and refusals ---------------------------------------------------------------------------------------------------
-def test_the_eighth_header_is_bound_beside_the_pinned_seven(L):
-    inc = lambda h: os.path.join(ROOT, 'include', h)
-    assert len(L.HEADER_PATHS) == 4 and L.LATER_HEADER_PATHS == (inc('nero_hip_envsample.h'),)                 # the pinned tuples: as they were
-    assert L.BOUNCE_HEADER_PATHS == (inc('nero_hip_bounce.h'),) and L.NORMALS_HEADER_PATHS == (inc('nero_hip_normals.h'),)
-    assert L.DENOISE_HEADER_PATHS == (HEADER,)
-    new = L.parse_headers(L.DENOISE_HEADER_PATHS)
-    assert {k: len(v[1]) for k, v in new.items()} == NAMES
-    seven = L.HEADER_PATHS + L.LATER_HEADER_PATHS + L.BOUNCE_HEADER_PATHS + L.NORMALS_HEADER_PATHS
-    every = seven + L.DENOISE_HEADER_PATHS
-    assert len(L.parse_headers(every)) == len(L.parse_headers(seven)) + len(NAMES)              # a name declared once across ALL headers
-    assert not set(new) & set(L.parse_headers(seven))
-    exported = C.CDLL(L.LIB_PATH)
-    for name, n_par in NAMES.items():
-        assert hasattr(exported, name)
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par
-        assert fn.restype is (C.c_int64 if name.endswith('max_pixels') else C.c_int)
-    p, i, i64, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-    assert L.lib.nero_denoise_variance.argtypes == [p, i, p, i64, i64, i, f, f, p, p]
-    assert L.lib.nero_denoise_atrous.argtypes == [p, i, p, i64, i64, i, i, f, f, f, p, p]
-    assert L.lib.nero_denoise_max_pixels() == 2 ** 31 - 1
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                              # bind()'s default: the four, nothing of the later ones
-    assert fresh.nero_denoise_atrous.argtypes is None and fresh.nero_surface_cdf.argtypes is not None
-    with pytest.raises(ImportError, match='nero_denoise'):                          # a name twice across ANY two headers
-        L.parse_headers(every + (HEADER,))
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert build.index("'nero_hip_normals.h'") < build.index("'nero_hip_denoise.h'")
-    for mod in ('denoise.py', 'relight.py'):
-        assert '.argtypes' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()   # nothing is bound outside _lib.py
-        assert '.restype' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()
-
-
+# ---- 2. the surface: refusals (the binding: tests/test_binding_cpu.py) ----------------------------------------------------------------------
 def test_entry_points_refuse_bad_arguments_without_a_device(L):
     lib = L.lib
     p, q = 4096, 8192                                                 # non-null pointers that are never followed: every call is refused first
@@ -183,21 +144,16 @@ def test_host_layer_refuses_bad_shapes_and_options():
 
 # ---- 3. tiles and grids ---------------------------------------------------------------------------------------------------------------------
 def test_tile_and_grid_arithmetic_under_the_sanitizers(tmp_path):
-    """nero_amd/csrc/denoise_plan.h as a stand-alone program built with -fsanitize=address,undefined, run as a child: the tiles cover every
+    """nero_amd/csrc/denoise_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): the tiles cover every
     shape of the GPU tier, 800 x 800, 1600 x 1600 and the limits; the grid stays within 2^20 workgroups; the argument checks hold at their
     edges"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'denoise_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'denoise_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
-    assert run.stdout.splitlines()[-1] == 'bad 0'
-    rows = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('S ')]
+    lines = run_host_program(tmp_path, 'denoise_plan_main.cpp').splitlines()
+    assert lines[-1] == 'bad 0'
+    rows = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('S ')]
     assert len(rows) == 15
     for h, w, tx, ty, t, grid in rows:
         assert tx == -(-w // 32) and ty == -(-h // 8) and t == tx * ty and grid == min(t, 2 ** 20)
-    lds = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('L ')]
+    lds = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('L ')]
     assert lds == [(1, 36 * 12, 36 * 12 * 48, 36 * 12 * 64), (2, 40 * 16, 40 * 16 * 48, 40 * 16 * 64), (0, 38 * 14, 38 * 14 * 48, 38 * 14 * 64)]
     assert max(r[-1] for r in lds) <= 65536
     got = {r[:2]: r[2:] for r in rows}

@@ -1,13 +1,10 @@
-"""CPU tier of the relighter's one bounce (include/nero_hip_bounce.h, nero_amd/csrc/relight_estimator.hip): the sixth header is bound through
-_lib.py beside the pinned five, the entry points refuse bad arguments before any device call, the workspace arithmetic holds at its limits
+"""CPU tier of the relighter's one bounce (include/nero_hip_bounce.h, nero_amd/csrc/relight_estimator.hip; its binding:
+tests/test_binding_cpu.py): the entry points refuse bad arguments before any device call, the workspace arithmetic holds at its limits
 under the sanitizers, and the restatement (tests/bounce_ref.py) is checked against closed forms and quadrature: a point under a disk, the
 one-sample secondary estimator's expectation, a convex mesh.  The committed cases of the GPU tier are checked here, with the restatement
 alone, for the share of lanes that bounce and for the share of points a decision margin exempts."""
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,13 +14,10 @@ from tests import bounce_ref as B
 from tests import envsample_ref as ER
 from tests import mc_shade_ref as R
 from tests import relight_ref as RR
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_bounce.h')
 ERR_ARG = -1
 F32, F64 = torch.float32, torch.float64
-NAMES = {'nero_relight_bounce_workspace_bytes': 3, 'nero_relight_mis_bounce_workspace_bytes': 4, 'nero_bvh_relight_bounce': 28,
-         'nero_bvh_relight_mis_bounce': 33, 'nero_relight_bounce_rays': 31}
 
 
 @pytest.fixture(scope='module')
@@ -34,32 +28,7 @@ def RL():
     return relight
 
 
-# ---- 1. binding -----------------------------------------------------------------------------------------------------------------------------
-def test_the_sixth_header_is_bound_beside_the_pinned_five(RL):
-    from nero_amd import _lib as L
-    envsample = os.path.join(ROOT, 'include', 'nero_hip_envsample.h')
-    assert len(L.HEADER_PATHS) == 4 and L.LATER_HEADER_PATHS == (envsample,) and L.BOUNCE_HEADER_PATHS == (HEADER,)     # the pinned tuples: as they were
-    assert len(L.parse_headers()) == 184 and len(L.parse_headers(L.LATER_HEADER_PATHS)) == 5                           # the defaults too
-    new = L.parse_headers(L.BOUNCE_HEADER_PATHS)
-    assert {k: len(v[1]) for k, v in new.items()} == NAMES
-    assert len(L.parse_headers(L.HEADER_PATHS + L.LATER_HEADER_PATHS + L.BOUNCE_HEADER_PATHS)) == 184 + 5 + len(NAMES)
-    for name, n_par in NAMES.items():
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par
-        assert fn.restype is (C.c_size_t if name.endswith('workspace_bytes') else C.c_int)
-    assert L.lib.nero_bvh_relight_bounce.argtypes[13] is C.c_float and L.lib.nero_bvh_relight_bounce.argtypes[26] is C.c_size_t
-    assert L.lib.nero_bvh_relight_mis_bounce.argtypes[31] is C.c_size_t and L.lib.nero_relight_bounce_rays.argtypes[16] is C.c_int
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                              # bind()'s default: the four, nothing of the later ones
-    assert fresh.nero_bvh_relight_bounce.argtypes is None and fresh.nero_bvh_relight.argtypes is not None
-    with pytest.raises(ImportError, match='nero_relight_bounce_workspace_bytes'):   # a name twice across ANY two headers
-        L.parse_headers(L.HEADER_PATHS + L.LATER_HEADER_PATHS + L.BOUNCE_HEADER_PATHS + (HEADER,))
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert build.index("'nero_hip_envsample.h'") < build.index("'nero_hip_bounce.h'")
-    import nero_amd.relight as rl_src
-    assert '.argtypes' not in open(rl_src.__file__).read()                          # relight.py binds nothing itself
-
-
-# ---- 2. arguments ---------------------------------------------------------------------------------------------------------------------------
+# ---- 1. binding: tests/test_binding_cpu.py.  2. arguments -----------------------------------------------------------------------------------
 class _Bvh(C.Structure):
     _fields_ = [('d_nodes', C.c_void_p), ('d_tris', C.c_void_p), ('d_face', C.c_void_p), ('n_nodes', C.c_int), ('n_tris', C.c_int)]
 
@@ -135,14 +104,9 @@ def test_entry_points_refuse_bad_arguments_without_a_device(RL):
 
 # ---- 3. the workspace arithmetic ------------------------------------------------------------------------------------------------------------
 def test_workspace_arithmetic_at_the_limits_under_the_sanitizers(tmp_path):
-    """nero_amd/csrc/relight_plan.h with the bounce's partial, as a stand-alone program built with -fsanitize=address,undefined"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'relight_bounce_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'relight_bounce_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stderr[-2000:])
-    rows = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('bounce')]
+    """nero_amd/csrc/relight_plan.h with the bounce's partial, as a stand-alone program under the sanitizers (tests.helpers.run_host_program)"""
+    stdout = run_host_program(tmp_path, 'relight_bounce_plan_main.cpp')
+    rows = [tuple(int(x) for x in ln.split()[1:]) for ln in stdout.splitlines() if ln.startswith('bounce')]
     assert len(rows) == 22
     for Dd, Ds, Dl, P_, total, nbytes, threads, blocks in rows:
         pad = -(-(Dd + Ds + Dl) // 64) * 64

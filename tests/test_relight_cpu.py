@@ -1,23 +1,19 @@
-"""CPU tier of the relighter (include/nero_hip_relight.h, nero_amd/relight.py): the third header is bound by _lib.py like the others,
-its entry points refuse bad arguments before any device call, the launch arithmetic holds at its limit under the sanitizer, the orbit
-equals the reference's, the stored roughness is squared once, the RGBA writer round-trips, and the restatement (tests/relight_ref.py) has
-its closed forms and stays inside the exemption cap on the committed direction sets."""
-import ctypes as C
+"""CPU tier of the relighter (include/nero_hip_relight.h, nero_amd/relight.py; its binding: tests/test_binding_cpu.py): the entry points
+refuse bad arguments before any device call, the launch arithmetic holds at its limit under the sanitizers, the orbit equals the
+reference's, the stored roughness is squared once, the RGBA writer round-trips, and the restatement (tests/relight_ref.py) has its closed
+forms and stays inside the exemption cap on the committed direction sets."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import relight_ref as RR
+from tests.helpers import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_relight.h')
 ERR_ARG = -1
-NAMES = {'nero_bvh_export_faces': 2, 'nero_bvh_trace_faces': 8, 'nero_env_lookup': 10, 'nero_relight_rays': 11,
-         'nero_relight_workspace_bytes': 3, 'nero_bvh_relight': 20}
 
 
 @pytest.fixture(scope='module')
@@ -26,31 +22,6 @@ def RL():
     ge.build()
     from nero_amd import relight
     return relight
-
-
-def _params(text):
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
-    return {name: 0 if params.strip() in ('', 'void') else params.count(',') + 1
-            for name, params in re.findall(r'\b(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)}
-
-
-def test_the_third_header_is_bound_by_lib_py(RL):
-    from nero_amd import _lib as L
-    protos = _params(open(HEADER).read())
-    assert protos == NAMES
-    assert L.HEADER_PATHS[2] == HEADER and len(L.HEADER_PATHS) == 4
-    assert not hasattr(RL, 'SIGNATURES') and not hasattr(RL, 'HEADER_PATH') and not hasattr(RL, '_bind')
-    sigs = L.parse_headers()
-    assert {n for n, s in sigs.items() if s[2] == 'nero_hip_relight.h'} == set(protos)
-    assert len([n for n, s in sigs.items() if s[2] in ('nero_hip.h', 'nero_hip_visibility.h')]) == 175
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: what bind() alone gives, whatever was imported
-    for lib in (fresh, L.lib):
-        for name, n_par in protos.items():
-            fn = getattr(lib, name)
-            assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-            assert fn.restype is (C.c_size_t if name == 'nero_relight_workspace_bytes' else C.c_int)
-        assert lib.nero_env_lookup.argtypes[6] is C.c_int64 and lib.nero_env_lookup.argtypes[7] is C.c_float
-        assert lib.nero_bvh_relight.argtypes[18] is C.c_size_t and lib.nero_bvh_relight.argtypes[13] is C.c_float
 
 
 def test_entry_points_refuse_bad_arguments_without_a_device(RL):
@@ -108,17 +79,10 @@ def test_entry_points_refuse_bad_arguments_without_a_device(RL):
 
 
 def test_grid_arithmetic_at_the_limit_under_the_sanitizer(tmp_path):
-    """nero_amd/csrc/relight_plan.h as a stand-alone program built with -fsanitize=undefined: at P * padded(D) = the largest admitted total
-    the grid covers every lane, no index passes 2^31 - 1, the workspace holds the last partial and nothing overflows on the way"""
-    import shutil
-    import subprocess
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'relight_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'relight_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stderr[-2000:])
-    rows = [tuple(int(x) for x in ln.split()) for ln in run.stdout.splitlines()]
+    """nero_amd/csrc/relight_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): at P * padded(D) = the
+    largest admitted total the grid covers every lane, no index passes 2^31 - 1, the workspace holds the last partial and nothing overflows on
+    the way"""
+    rows = [tuple(int(x) for x in ln.split()) for ln in run_host_program(tmp_path, 'relight_plan_main.cpp').splitlines()]
     assert len(rows) == 18
     for Dd, Ds, P_, total, threads, blocks in rows:
         pad = -(-(Dd + Ds) // 64) * 64

@@ -1,12 +1,8 @@
-"""CPU tier of the relighter's third strategy (include/nero_hip_envsample.h, nero_amd/csrc/envsample.hip): the fifth header is bound through
-_lib.py beside the pinned four, the new entry points refuse bad arguments before any device call, the launch arithmetic holds at its limits
-under the sanitizer, and the restatement (tests/envsample_ref.py) is checked against quadrature: the MIS estimator and the two-strategy
+"""CPU tier of the relighter's third strategy (include/nero_hip_envsample.h, nero_amd/csrc/envsample.hip; its binding:
+tests/test_binding_cpu.py): the entry points refuse bad arguments before any device call, the launch arithmetic holds at its limits
+under the sanitizers, and the restatement (tests/envsample_ref.py) is checked against quadrature: the MIS estimator and the two-strategy
 estimator share one expectation (which is what fixes S), and MIS has the smaller error under a map with a hot texel."""
-import ctypes as C
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,13 +11,10 @@ import torch
 from tests import envsample_ref as ER
 from tests import mc_shade_ref as R
 from tests import relight_ref as RR
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_envsample.h')
 ERR_ARG = -1
 F64 = torch.float64
-NAMES = {'nero_env_cdf_workspace_bytes': 2, 'nero_env_cdf': 11, 'nero_relight_mis_rays': 20, 'nero_relight_mis_workspace_bytes': 4,
-         'nero_bvh_relight_mis': 25}
 
 
 @pytest.fixture(scope='module')
@@ -32,27 +25,7 @@ def RL():
     return relight
 
 
-# ---- binding, arguments, plan -----------------------------------------------------------------------------------------------------------------
-def test_the_fifth_header_is_bound_beside_the_pinned_four(RL):
-    from nero_amd import _lib as L
-    assert len(L.HEADER_PATHS) == 4 and L.LATER_HEADER_PATHS == (HEADER,)
-    assert len(L.parse_headers()) == 184                                            # the defaults are as they were
-    later = L.parse_headers(L.LATER_HEADER_PATHS)
-    assert {k: len(v[1]) for k, v in later.items()} == NAMES
-    assert len(L.parse_headers(L.HEADER_PATHS + L.LATER_HEADER_PATHS)) == 184 + len(NAMES)
-    for name, n_par in NAMES.items():
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par
-        assert fn.restype is (C.c_size_t if name.endswith('workspace_bytes') else C.c_int)
-    assert L.lib.nero_env_cdf.argtypes[5] is C.c_float and L.lib.nero_bvh_relight_mis.argtypes[23] is C.c_size_t
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                              # bind()'s default: the four, and nothing of the fifth
-    assert fresh.nero_bvh_relight_mis.argtypes is None and fresh.nero_bvh_relight.argtypes is not None
-    with pytest.raises(ImportError, match='nero_env_cdf'):                          # a name twice across ANY two headers
-        L.parse_headers(L.HEADER_PATHS + L.LATER_HEADER_PATHS + (HEADER,))
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert build.index("'nero_hip_surface.h'") < build.index("'nero_hip_envsample.h'")
-
-
+# ---- arguments, plan --------------------------------------------------------------------------------------------------------------------------
 def test_entry_points_refuse_bad_arguments_without_a_device(RL):
     from nero_amd import _lib as L
     lib = L.lib
@@ -102,15 +75,10 @@ def test_entry_points_refuse_bad_arguments_without_a_device(RL):
 
 
 def test_plan_arithmetic_at_the_limits_under_the_sanitizer(tmp_path):
-    """nero_amd/csrc/envsample_plan.h as a stand-alone program built with -fsanitize=undefined"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'envsample_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'envsample_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stderr[-2000:])
-    maps = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('map')]
-    mis = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('mis')]
+    """nero_amd/csrc/envsample_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program)"""
+    stdout = run_host_program(tmp_path, 'envsample_plan_main.cpp')
+    maps = [tuple(int(x) for x in ln.split()[1:]) for ln in stdout.splitlines() if ln.startswith('map')]
+    mis = [tuple(int(x) for x in ln.split()[1:]) for ln in stdout.splitlines() if ln.startswith('mis')]
     assert len(maps) == 9 and len(mis) == 16
     for eh, ew, N, B, fixed in maps:
         assert N == eh * ew and B == ER.weight_bits(N) == min(40, 62 - (N - 1).bit_length()) and (N << B) <= 2 ** 62

@@ -1,11 +1,9 @@
-"""CPU tier of the surface sampler (include/nero_hip_surface.h, nero_amd/surface.py): the fourth header is bound by _lib.py like the
-others, its entry points refuse bad arguments before any device call, the limit arithmetic holds at n = 2^31 - 1 and T = 2^31 - 2 under the
-sanitizer, and the restatement (tests/surface_ref.py) has the properties the contract promises: the stratified counts, the chi-square of
+"""CPU tier of the surface sampler (include/nero_hip_surface.h, nero_amd/surface.py; its binding: tests/test_binding_cpu.py): the entry
+points refuse bad arguments before any device call, the limit arithmetic holds at n = 2^31 - 1 and T = 2^31 - 2 under the sanitizers,
+and the restatement (tests/surface_ref.py) has the properties the contract promises: the stratified counts, the chi-square of
 independent draws, the moments of the barycentric weights, the silence of degenerate triangles, a closed form, and the command lines."""
-import ctypes as C
 import importlib.util
 import os
-import re
 import subprocess
 import sys
 
@@ -13,11 +11,10 @@ import numpy as np
 import pytest
 
 from tests import surface_ref as SR
+from tests.helpers import run_host_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_surface.h')
 ERR_ARG = -1
-NAMES = {'nero_surface_cdf_workspace_bytes': 1, 'nero_surface_cdf': 8, 'nero_surface_sample': 16}
 T_MAX, N_MAX = 2 ** 31 - 2, 2 ** 31 - 1
 SEEDS = (0, 1, 2)
 N_IID = 64000
@@ -49,29 +46,6 @@ def _script(name):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def test_the_fourth_header_is_bound_by_lib_py(SF):
-    from nero_amd import _lib as L
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', open(HEADER).read(), flags=re.S)
-    protos = {name: params.count(',') + 1 for name, params in re.findall(r'\b(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)}
-    assert protos == NAMES
-    assert L.HEADER_PATHS[3] == HEADER and len(L.HEADER_PATHS) == 4
-    assert not hasattr(SF, 'SIGNATURES') and not hasattr(SF, 'HEADER_PATH') and not hasattr(SF, '_bind')
-    assert {n for n, s in L.parse_headers().items() if s[2] == 'nero_hip_surface.h'} == set(protos)
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: what bind() alone gives, whatever was imported
-    for lib in (fresh, L.lib):
-        for name, n_par in protos.items():
-            fn = getattr(lib, name)
-            assert fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-            assert fn.restype is (C.c_size_t if name == 'nero_surface_cdf_workspace_bytes' else C.c_int)
-        assert lib.nero_surface_cdf_workspace_bytes.argtypes == [C.c_int64]
-        a = lib.nero_surface_sample.argtypes
-        assert a[1] is C.c_int64 and a[3] is C.c_int64 and a[6:9] == [C.c_int64] * 3 and a[9] is C.c_uint and a[10] is C.c_int
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert 'nero_hip_surface.h' in build                              # a change of the header rebuilds the library
-    src = open(os.path.join(ROOT, 'nero_amd', 'surface.py')).read()
-    assert 'environ' not in src and 'getenv' not in src                # the module reads no environment variable
 
 
 def test_entry_points_refuse_bad_arguments_without_a_device(SF):
@@ -106,16 +80,10 @@ def test_entry_points_refuse_bad_arguments_without_a_device(SF):
 
 
 def test_limit_arithmetic_under_the_sanitizer(tmp_path):
-    """nero_amd/csrc/surface_plan.h as a stand-alone program built with -fsanitize=undefined: at n = 2^31 - 1 and T = 2^31 - 2 no index or
-    byte count overflows, and B = min(40, 62 - L) keeps T 2^B <= 2^62"""
-    import shutil
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'surface_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'surface_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
-    rows = [tuple(int(x) for x in ln.split()) for ln in run.stdout.splitlines() if not ln.startswith('bad')]
+    """nero_amd/csrc/surface_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): at n = 2^31 - 1 and
+    T = 2^31 - 2 no index or byte count overflows, and B = min(40, 62 - L) keeps T 2^B <= 2^62"""
+    stdout = run_host_program(tmp_path, 'surface_plan_main.cpp')
+    rows = [tuple(int(x) for x in ln.split()) for ln in stdout.splitlines() if not ln.startswith('bad')]
     assert len(rows) == 14
     for T, L_, B, blocks, wbytes in rows:
         assert L_ == (T - 1).bit_length() and B == min(40, 62 - L_) == SR.weight_bits(T)

@@ -1,21 +1,13 @@
-"""CPU tier of the texture lookup (include/nero_hip_texfetch.h, nero_amd/csrc/tex_fetch.hip, nero_amd/texfetch.py): the ninth header bound
-through _lib.py beside the pinned eight, the entry points' refusals before any device call, the restatement (tests/texfetch_ref.py) checked
-against itself, and the pyramid's level arithmetic as a stand-alone program under the sanitizers."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
+"""CPU tier of the texture lookup (include/nero_hip_texfetch.h, nero_amd/csrc/tex_fetch.hip, nero_amd/texfetch.py; its binding:
+tests/test_binding_cpu.py): the entry points' refusals before any device call, the restatement (tests/texfetch_ref.py) checked against
+itself, and the pyramid's level arithmetic as a stand-alone program under the sanitizers."""
 import numpy as np
 import pytest
 
 from tests import texfetch_ref as TR
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_texfetch.h')
 ERR_ARG = -1
-NAMES = {'nero_tex_mip_levels': 2, 'nero_tex_mip_bytes': 2, 'nero_tex_pack': 7, 'nero_tex_mip_build': 4, 'nero_tex_face_scale': 11,
-         'nero_tex_materials': 18, 'nero_tex_vertex_materials': 13}
 
 
 @pytest.fixture(scope='module')
@@ -26,41 +18,7 @@ def L():
     return _lib
 
 
-# ---- 1. the surface: binding and refusals ---------------------------------------------------------------------------------------------------
-def test_the_ninth_header_is_bound_beside_the_pinned_eight(L):
-    inc = lambda h: os.path.join(ROOT, 'include', h)
-    assert len(L.HEADER_PATHS) == 4 and L.LATER_HEADER_PATHS == (inc('nero_hip_envsample.h'),)                 # the pinned tuples: as they were
-    assert L.BOUNCE_HEADER_PATHS == (inc('nero_hip_bounce.h'),) and L.NORMALS_HEADER_PATHS == (inc('nero_hip_normals.h'),)
-    assert L.DENOISE_HEADER_PATHS == (inc('nero_hip_denoise.h'),)
-    assert L.TEXFETCH_HEADER_PATHS == (HEADER,)
-    new = L.parse_headers(L.TEXFETCH_HEADER_PATHS)
-    assert {k: len(v[1]) for k, v in new.items()} == NAMES
-    eight = L.HEADER_PATHS + L.LATER_HEADER_PATHS + L.BOUNCE_HEADER_PATHS + L.NORMALS_HEADER_PATHS + L.DENOISE_HEADER_PATHS
-    every = eight + L.TEXFETCH_HEADER_PATHS
-    assert len(L.parse_headers(every)) == len(L.parse_headers(eight)) + len(NAMES)              # a name declared once across ALL headers
-    assert not set(new) & set(L.parse_headers(eight))
-    exported = C.CDLL(L.LIB_PATH)
-    for name, n_par in NAMES.items():
-        assert hasattr(exported, name)
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par
-        assert fn.restype is (C.c_size_t if name.endswith('mip_bytes') else C.c_int)
-    p, i64, f = C.c_void_p, C.c_int64, C.c_float
-    assert L.lib.nero_tex_materials.argtypes == [p, i64, i64, p, p, i64, p, i64, p, p, p, p, i64, f, f, p, p, p]
-    assert L.lib.nero_tex_vertex_materials.argtypes == [p, i64, i64, p, p, i64, p, p, i64, i64, p, p, p]
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                              # bind()'s default: the four, nothing of the later ones
-    assert fresh.nero_tex_materials.argtypes is None and fresh.nero_surface_cdf.argtypes is not None
-    with pytest.raises(ImportError, match='nero_tex_mip_levels'):                   # a name twice across ANY two headers
-        L.parse_headers(every + (HEADER,))
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    public = build[build.index('public = ('):build.index('deps = ')]
-    assert public.index("'nero_hip_denoise.h'") < public.index("'nero_hip_texfetch.h'")
-    assert public.rstrip().endswith("'nero_hip_texfetch.h')")                       # the build lists the new header last
-    for mod in ('texfetch.py', 'relight.py'):
-        assert '.argtypes' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()   # nothing is bound outside _lib.py
-        assert '.restype' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()
-
-
+# ---- 1. the surface: refusals (the binding: tests/test_binding_cpu.py) ----------------------------------------------------------------------
 def test_level_counts_and_sizes_of_the_pyramid(L):
     lib = L.lib
     for (h, w), n in {(1, 1): 1, (2, 2): 2, (4, 2): 2, (6, 10): 2, (8, 8): 4, (64, 64): 7, (96, 80): 5, (1000, 1000): 4, (2048, 2048): 12,
@@ -252,21 +210,16 @@ def test_vertex_owners_of_the_restatement():
 
 # ---- 3. levels and offsets ------------------------------------------------------------------------------------------------------------------
 def test_pyramid_arithmetic_under_the_sanitizers(tmp_path):
-    """nero_amd/csrc/tex_fetch_plan.h as a stand-alone program built with -fsanitize=address,undefined, run as a child: the level counts and
+    """nero_amd/csrc/tex_fetch_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): the level counts and
     offsets tile the pyramid without gap or overlap at 1 x 1, 2 x 2, 4 x 2, 6 x 10, 1000 x 1000, 16384 x 16384 and the GPU tier's other
     sizes; the argument checks hold at their edges"""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'tex_fetch_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'tex_fetch_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
-    assert run.stdout.splitlines()[-1] == 'bad 0'
-    rows = {(r[0], r[1]): r[2:] for r in (tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('P '))}
+    lines = run_host_program(tmp_path, 'tex_fetch_plan_main.cpp').splitlines()
+    assert lines[-1] == 'bad 0'
+    rows = {(r[0], r[1]): r[2:] for r in (tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('P '))}
     assert len(rows) == 12
     for (h, w), (L_, records, nbytes) in rows.items():
         assert L_ == TR.levels(h, w) and records == sum((h >> k) * (w >> k) for k in range(L_)) and nbytes == 8 * records
     assert rows[(1, 1)] == (1, 1, 8) and rows[(2, 2)] == (2, 5, 40) and rows[(4, 2)] == (2, 10, 80) and rows[(6, 10)] == (2, 75, 600)
     assert rows[(1000, 1000)][0] == 4 and rows[(16384, 16384)][0] == 15 and rows[(16384, 16384)][1] == (4 ** 15 - 1) // 3
-    lv = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('V ')]
+    lv = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('V ')]
     assert [r[2:] for r in lv if r[:2] == (1000, 1000)] == [(0, 1000, 1000, 0), (1, 500, 500, 1000000), (2, 250, 250, 1250000), (3, 125, 125, 1312500)]

@@ -1,21 +1,14 @@
 """CPU tier of the vertex normals (include/nero_hip_normals.h, nero_amd/csrc/mesh_normals.hip, nero_amd.mesh.vertex_normals): the
-restatement (tests/normals_ref.py) against analysis -- spheres, a cube, permutations, reversal, cancelling faces --, the seventh header bound
-through _lib.py beside the pinned six, the entry points' refusals before any device call, the limit arithmetic under the sanitizers, the PLY
-round trip with normals and winding_sign."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
+restatement (tests/normals_ref.py) against analysis -- spheres, a cube, permutations, reversal, cancelling faces --, the entry points'
+refusals before any device call, the limit arithmetic under the sanitizers, the PLY round trip with normals and winding_sign.  The
+header's binding: tests/test_binding_cpu.py."""
 import numpy as np
 import pytest
 
 from tests import normals_ref as NR
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'nero_hip_normals.h')
 ERR_ARG = -1
-NAMES = {'nero_vertex_normals_workspace_bytes': 2, 'nero_vertex_normals': 9}
 T_MAX = 2 ** 31 - 2
 MODES = ('area', 'angle')
 
@@ -136,38 +129,7 @@ def test_refused_and_degenerate_faces_are_counted_and_silent():
         assert info2[:3].tolist() == [4, 1, 2] and info2[3] == info[3]
 
 
-# ---- 2. the surface: binding and refusals ---------------------------------------------------------------------------------------------------
-def test_the_seventh_header_is_bound_beside_the_pinned_six(M):
-    from nero_amd import _lib as L
-    inc = lambda h: os.path.join(ROOT, 'include', h)
-    assert len(L.HEADER_PATHS) == 4 and L.LATER_HEADER_PATHS == (inc('nero_hip_envsample.h'),)                 # the pinned tuples: as they were
-    assert L.BOUNCE_HEADER_PATHS == (inc('nero_hip_bounce.h'),) and L.NORMALS_HEADER_PATHS == (HEADER,)
-    assert len(L.parse_headers()) == 184 and len(L.parse_headers(L.LATER_HEADER_PATHS)) == 5
-    assert len(L.parse_headers((L.HEADER_PATH,))) == 172
-    new = L.parse_headers(L.NORMALS_HEADER_PATHS)
-    assert {k: len(v[1]) for k, v in new.items()} == NAMES
-    every = L.HEADER_PATHS + L.LATER_HEADER_PATHS + L.BOUNCE_HEADER_PATHS + L.NORMALS_HEADER_PATHS
-    assert len(L.parse_headers(every)) == 184 + 5 + len(L.parse_headers(L.BOUNCE_HEADER_PATHS)) + len(NAMES)
-    exported = C.CDLL(L.LIB_PATH)
-    for name, n_par in NAMES.items():
-        assert hasattr(exported, name)
-        fn = getattr(L.lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == n_par
-        assert fn.restype is (C.c_size_t if name.endswith('workspace_bytes') else C.c_int)
-    assert L.lib.nero_vertex_normals_workspace_bytes.argtypes == [C.c_int64, C.c_int64]
-    a = L.lib.nero_vertex_normals.argtypes
-    assert a[1] is C.c_int64 and a[3] is C.c_int64 and a[4] is C.c_int and a[0] is C.c_void_p and a[8] is C.c_void_p
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                              # bind()'s default: the four, nothing of the later ones
-    assert fresh.nero_vertex_normals.argtypes is None and fresh.nero_surface_cdf.argtypes is not None
-    with pytest.raises(ImportError, match='nero_vertex_normals'):                   # a name twice across ANY two headers
-        L.parse_headers(every + (HEADER,))
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()
-    assert build.index("'nero_hip_bounce.h'") < build.index("'nero_hip_normals.h'")
-    for mod in ('mesh.py', 'relight.py'):
-        assert '.argtypes' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()   # nothing is bound outside _lib.py
-        assert '.restype' not in open(os.path.join(ROOT, 'nero_amd', mod)).read()
-
-
+# ---- 2. the surface: refusals (the binding: tests/test_binding_cpu.py) ----------------------------------------------------------------------
 def test_entry_points_refuse_bad_arguments_without_a_device(M):
     from nero_amd import _lib as L
     lib = L.lib
@@ -195,19 +157,14 @@ def test_entry_points_refuse_bad_arguments_without_a_device(M):
 
 # ---- 3. limits ------------------------------------------------------------------------------------------------------------------------------
 def test_limit_arithmetic_under_the_sanitizers(tmp_path):
-    """nero_amd/csrc/normals_plan.h as a stand-alone program built with -fsanitize=address,undefined, run as a child: B at T = 1, 2^21,
+    """nero_amd/csrc/normals_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): B at T = 1, 2^21,
     2^21 + 1 and 2^31 - 2; the sums stay within 2^61 -- T 2^B <= 2^61 for area (|q| <= 2^B), T 2^(B + 2) <= 2^61 for angle -- and the
     workspace bytes at the limits do not overflow.  The area bound is reached with equality exactly when T is a power of two of at least
     2^21 (T = 2^21: 2^21 2^40); every other T stays strictly below, and 2^61 itself is a quarter of what an int64 holds."""
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'normals_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'normals_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stdout[-300:], run.stderr[-2000:])
-    assert run.stdout.splitlines()[-1] == 'bad 0'
-    t_rows = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('T ')]
-    v_rows = [tuple(int(x) for x in ln.split()[1:]) for ln in run.stdout.splitlines() if ln.startswith('V ')]
+    lines = run_host_program(tmp_path, 'normals_plan_main.cpp').splitlines()
+    assert lines[-1] == 'bad 0'
+    t_rows = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('T ')]
+    v_rows = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith('V ')]
     assert len(t_rows) == 14 and len(v_rows) == 14
     for T, L_, Ba, Bg, blocks in t_rows:
         assert L_ == (T - 1).bit_length()

@@ -1,18 +1,15 @@
-"""CPU tier of the visibility queries (include/nero_hip_visibility.h): the second header is bound like the first, the entry points refuse
+"""CPU tier of the visibility queries (include/nero_hip_visibility.h; its binding: tests/test_binding_cpu.py): the entry points refuse
 bad arguments before any device call, the numpy restatement of the AO sample set (tests/ao_ref.py) has the properties the kernels rely on,
 ao_bytes is the rounded linear level, and the occlusion map travels through the OBJ / MTL writer and reader."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import ao_ref as A
+from tests.helpers import run_host_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VIS_HEADER = os.path.join(ROOT, 'include', 'nero_hip_visibility.h')
 ERR_ARG = -1
 
 
@@ -22,44 +19,6 @@ def L():
     ge.build()
     from nero_amd import _lib
     return _lib
-
-
-def _params(text):
-    """{name: parameter count} by this test's own rule: comments out, then `type name(params);`"""
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
-    return {name: 0 if params.strip() in ('', 'void') else params.count(',') + 1
-            for name, params in re.findall(r'\b(nero_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', text)}
-
-
-def test_the_second_header_is_bound_like_the_first(L):
-    protos = _params(open(VIS_HEADER).read())
-    assert sorted(protos) == ['nero_ao_rays', 'nero_bvh_ao', 'nero_bvh_occluded']
-    assert [protos[k] for k in sorted(protos)] == [10, 11, 9]
-    assert {n for n, s in L.parse_headers().items() if s[2] == 'nero_hip_visibility.h'} == set(protos)
-    fresh = L.bind(C.CDLL(L.LIB_PATH))                                # a fresh handle: exported, and what bind() alone gives
-    for lib in (fresh, L.lib):
-        for name, n_par in protos.items():
-            fn = getattr(lib, name)
-            assert fn.restype is C.c_int and fn.argtypes is not None and len(fn.argtypes) == n_par, (name, fn.argtypes)
-        assert lib.nero_ao_rays.argtypes[5] is C.c_uint and lib.nero_bvh_occluded.argtypes[5] is C.c_float
-    assert L.HEADER_PATHS[0] == L.HEADER_PATH and L.HEADER_PATHS[1] == VIS_HEADER and len(L.HEADER_PATHS) == 4
-    build = open(os.path.join(ROOT, '__graft_entry__.py')).read()     # the order build() lists them in; each one a build dependency
-    at = [build.index(f"'{os.path.basename(p)}'") for p in L.HEADER_PATHS]
-    assert at == sorted(at)
-
-
-def test_no_name_is_declared_twice(L, tmp_path):
-    first = L.parse_header(open(L.HEADER_PATH).read())
-    second = L.parse_header(open(VIS_HEADER).read())
-    assert not set(first) & set(second)
-    assert len(first) == 172                                          # the first header is as it was: new entry points go into the others
-    assert set(L.parse_headers(L.HEADER_PATHS[:2])) == set(first) | set(second)
-    assert set(L.parse_headers()) == set().union(*(L.parse_header(open(p).read()) for p in L.HEADER_PATHS))
-    assert len(L.parse_headers()) == 172 + 3 + 6 + 3
-    dup = tmp_path / 'dup.h'
-    dup.write_text('int nero_fresh(int n);\nint nero_version(void);\n')
-    with pytest.raises(ImportError, match='nero_version'):
-        L.parse_headers((L.HEADER_PATH, str(dup)))
 
 
 def test_entry_points_refuse_bad_arguments_without_a_device(L):
@@ -97,17 +56,9 @@ def test_entry_points_refuse_bad_arguments_without_a_device(L):
 
 
 def test_grid_arithmetic_at_the_limit_under_the_sanitizer(tmp_path):
-    """nero_amd/csrc/visibility_plan.h as a stand-alone program built with -fsanitize=undefined: at n * S = the largest admitted total, for
-    every S and both workgroup sizes, the grid covers every ray, no index passes 2^31 - 1 and nothing overflows on the way"""
-    import shutil
-    import subprocess
-    cxx = shutil.which('g++') or shutil.which('clang++') or '/opt/rocm/llvm/bin/clang++'
-    exe = str(tmp_path / 'visibility_plan')
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=undefined', '-fno-sanitize-recover=all',
-                           os.path.join(ROOT, 'tests', 'visibility_plan_main.cpp'), '-o', exe])
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0 and run.stderr == '', (run.returncode, run.stderr[-2000:])
-    rows = [tuple(int(x) for x in ln.split()) for ln in run.stdout.splitlines()]
+    """nero_amd/csrc/visibility_plan.h as a stand-alone program under the sanitizers (tests.helpers.run_host_program): at n * S = the largest
+    admitted total, for every S and both workgroup sizes, the grid covers every ray, no index passes 2^31 - 1 and nothing overflows on the way"""
+    rows = [tuple(int(x) for x in ln.split()) for ln in run_host_program(tmp_path, 'visibility_plan_main.cpp').splitlines()]
     assert len(rows) == 16
     for S, total, threads, blocks in rows:
         assert total == (A.MAX_RAYS // S) * S and total > A.MAX_RAYS - S
