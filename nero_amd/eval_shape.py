@@ -97,14 +97,31 @@ def eval_point_clouds(pts_pr, pts_gt):
     return float(chamfer(pts_pr, pts_gt)[0])
 
 
-def eval_meshes(pr_mesh, gt_mesh, n=500000, seed=0, stratified=True):
+def point_to_mesh(points, mesh_or_tracer, bvh_build='host', sort=True):
+    """for every point its distance to the nearest point of the mesh's SURFACE (RayTracer.closest, nero_bvh_closest): float32 [n], exact up
+    to float32 rounding -- no floor from a sample spacing, unlike nearest_dist against samples of the mesh.  numpy in -> numpy out, a tensor in
+    -> a device tensor out (nearest_dist's contract).  mesh_or_tracer: as render_depth takes it; pass a RayTracer to reuse one tree.  sort:
+    the launch order of the queries (RayTracer.closest); the result does not depend on it."""
+    as_numpy = not torch.is_tensor(points)
+    rt, _ = _tracer(mesh_or_tracer, bvh_build)
+    dist = rt.closest(_points(points, _device(points)), sort=sort)[0]
+    return dist.cpu().numpy() if as_numpy else dist
+
+
+def eval_meshes(pr_mesh, gt_mesh, n=500000, seed=0, stratified=True, exact=False, bvh_build='host'):
     """the real-shape procedure from two MESHES, each a (vertices, triangles) pair: eval.md samples 500k points on the surface of the
     predicted and of the ground-truth mesh alike (there with CloudCompare, here with nero_amd.surface.sample_surface: area-weighted,
-    deterministic in n and seed) before eval_real_shape.py takes the Chamfer distance of the two point sets"""
+    deterministic in n and seed) before eval_real_shape.py takes the Chamfer distance of the two point sets.  exact: the same two sample
+    sets, each measured to the OTHER MESH'S SURFACE (point_to_mesh; CloudCompare's cloud-to-mesh distance) instead of to the other set's
+    nearest sample, then (mean + mean) / 2 on the host as chamfer takes its means: no floor from the sample spacing."""
     from .surface import sample_surface
     dev = _device(*pr_mesh, *gt_mesh)
     cloud = lambda m: sample_surface(_points(m[0], dev), m[1], n, seed=seed, stratified=stratified)      # (device tensors: nothing comes back)
-    return eval_point_clouds(cloud(pr_mesh), cloud(gt_mesh))
+    if not exact:
+        return eval_point_clouds(cloud(pr_mesh), cloud(gt_mesh))
+    dist_gt = point_to_mesh(cloud(gt_mesh), tuple(pr_mesh), bvh_build).cpu().numpy()
+    dist_pr = point_to_mesh(cloud(pr_mesh), tuple(gt_mesh), bvh_build).cpu().numpy()
+    return float((np.mean(dist_gt) + np.mean(dist_pr)) / 2)
 
 
 # ---- voxel down-sampling -------------------------------------------------------------------------------------------------------------------

@@ -171,3 +171,50 @@ class RayTracer:
             L.check(L.lib.nero_bvh_occluded(self._handle(), rays_o.data_ptr(), rays_d.data_ptr(), n, tp, tmax_all, sp, out.data_ptr(),
                                             L.stream_ptr()))
         return out.view(*prefix)
+
+    def closest(self, points, max_dist=None, sort=False):
+        """exact point-to-mesh distance (nero_bvh_closest): -> (dist float32, face int32, bary float32 [..., 2], point float32 [..., 3]) of the
+        points' leading shape -- the distance to the nearest point of the surface, the lowest face index among the faces that attain it, that
+        point's weights (b1, b2) on the face's second and third corner, and the point itself.  max_dist: None (no limit) or a positive float;
+        a point with nothing within it, or with a non-finite coordinate, reports face -1, dist +inf and zeros.  sort: the queries are put in
+        the order of a 30-bit Morton key of their position before the call (neighbouring lanes then walk neighbouring subtrees) and the
+        outputs back in the caller's order after it; the outputs are the same bits either way."""
+        points = points.float().contiguous()
+        if not points.is_cuda:
+            points = points.cuda()
+        prefix = points.shape[:-1]
+        pts = points.view(-1, 3)
+        n = pts.shape[0]
+        dev = pts.device
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        bary = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if n > 0:
+            order = None
+            if sort:
+                order = torch.sort(_morton30(pts), stable=True)[1]
+                pts = pts[order].contiguous()
+            with torch.cuda.device(dev):
+                L.check(L.lib.nero_bvh_closest(self._handle(), pts.data_ptr(), n, float('inf') if max_dist is None else float(max_dist),
+                                               dist.data_ptr(), face.data_ptr(), bary.data_ptr(), point.data_ptr(), L.stream_ptr()))
+            if order is not None:
+                back = torch.empty_like(order)
+                back[order] = torch.arange(n, device=dev)
+                dist, face, bary, point = dist[back], face[back], bary[back], point[back]
+        return dist.view(*prefix), face.view(*prefix), bary.view(*prefix, 2), point.view(*prefix, 3)
+
+
+def _morton30(pts):
+    """30-bit Morton key (10 bits per axis, over the points' own bounding box) of float32 points [n,3] -> int64 [n]; a non-finite coordinate
+    counts as 0.  Plumbing for RayTracer.closest(sort=True): only the ORDER of the queries depends on it."""
+    p = torch.nan_to_num(pts, nan=0.0, posinf=0.0, neginf=0.0)
+    lo, hi = p.min(0).values, p.max(0).values
+    q = ((p - lo) / (hi - lo).clamp_min(1e-30) * 1023.0).clamp(0, 1023).long()
+
+    def spread(x):                      # abcdefghij -> a00b00c00d00e00f00g00h00i00j
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        return (x | (x << 2)) & 0x09249249
+    return spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)

@@ -5,6 +5,10 @@
     python scripts/eval_shape.py --pr A.ply --gt B.ply --samples 500000 [--seed S] [--iid]
         eval.md's full recipe for two MESHES: N points sampled on each surface on the GPU (nero_amd/surface.py, what eval.md gives to
         CloudCompare), then the same distances.  A PLY without faces is used as it is.
+    python scripts/eval_shape.py --pr A.ply --gt B.ply --samples 500000 --exact
+        the same two sample sets, each measured to the other MESH'S SURFACE (exact point-to-triangle distances through the tracer's BVH,
+        CloudCompare's cloud-to-mesh distance) instead of to the other set's nearest sample: no floor from the sample spacing.  Both files
+        must have faces.
     python scripts/eval_shape.py --mesh M.ply --views views.npz (--gt-points P.ply | --gt-depths D.npz)
         eval_synthetic_shape.py: the mesh's depth map in every view of views.npz (poses [n,3,4] world -> camera, Ks [n,3,3], hw [n,2]),
         back-projected and voxel-down-sampled, against the ground-truth points (the data set's eval_pts.ply) or the points made the same way
@@ -30,6 +34,8 @@ def parse(argv=None):
                          'vertices; a PLY without faces is used as it is')
     ap.add_argument('--seed', type=int, default=0, help='--samples: seed of the sampler')
     ap.add_argument('--iid', action='store_true', help='--samples: independent draws instead of stratified ones')
+    ap.add_argument('--exact', action='store_true',
+                    help='--samples: measure every sample to the other mesh\'s surface (point to triangle) instead of to its nearest sample')
     ap.add_argument('--mesh', type=str, help='extracted mesh (PLY) for the synthetic procedure')
     ap.add_argument('--views', type=str, help='npz with poses [n,3,4], Ks [n,3,3], hw [n,2]')
     ap.add_argument('--gt-points', type=str, help='ground-truth eval points (PLY)')
@@ -38,7 +44,7 @@ def parse(argv=None):
     ap.add_argument('--unproject-offset', type=float, default=0.0,
                     help='0 = the reference (integer pixel coordinates), 0.5 = through the pixel centres')
     ap.add_argument('--bvh-build', choices=('host', 'device'), default='host',
-                    help='--mesh/--views: where the ray tracer builds its tree (device: on the GPU, same tree)')
+                    help='--mesh/--views and --exact: where the ray tracer builds its tree (device: on the GPU, same tree)')
     ap.add_argument('--batch_size', type=int, default=None, help='accepted for compatibility with the reference; nothing is batched')
     a = ap.parse_args(argv)
     real, syn = a.pr is not None or a.gt is not None, a.mesh is not None or a.views is not None
@@ -48,6 +54,8 @@ def parse(argv=None):
         ap.error('the real-shape procedure needs both --pr and --gt')
     if a.samples is not None and (syn or a.samples < 1):
         ap.error('--samples N (N >= 1) belongs to the real-shape procedure, --pr A.ply --gt B.ply')
+    if a.exact and a.samples is None:
+        ap.error('--exact belongs to --pr A.ply --gt B.ply --samples N')
     if syn:
         if a.mesh is None or a.views is None:
             ap.error('the synthetic procedure needs both --mesh and --views')
@@ -84,7 +92,14 @@ def main(argv=None):
     from nero_amd import mesh as M
     if a.pr is not None:
         stem = Path(a.pr).stem
-        chamfer = E.eval_point_clouds(_cloud(a.pr, a), _cloud(a.gt, a))
+        if a.exact:
+            for path in (a.pr, a.gt):
+                if not has_faces(path):
+                    sys.exit(f'eval_shape: --exact measures to a surface, and {path} has no faces')
+            chamfer = E.eval_meshes(M.read_ply(a.pr), M.read_ply(a.gt), n=a.samples, seed=a.seed, stratified=not a.iid, exact=True,
+                                    bvh_build=a.bvh_build)
+        else:
+            chamfer = E.eval_point_clouds(_cloud(a.pr, a), _cloud(a.gt, a))
     else:
         stem = Path(a.mesh).stem
         v, f = M.read_ply(a.mesh)
