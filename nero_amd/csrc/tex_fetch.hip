@@ -3,7 +3,7 @@
 //   One lane owns one output (a texel, a face, a hit, a vertex).  A tap is one 8-byte load of a record; its five bytes are decoded through
 //   the 256-entry table, which every workgroup stages in LDS first (one entry per thread).  Level sizes and offsets travel by value in a
 //   Plan (tex_fetch_plan.h); a record is addressed as off[k] + y w_k + x with y and x clamped to the level, so no lane leaves the pyramid
-//   whatever its coordinates are.
+//   whatever its coordinates are.  The level-of-detail rule and the addressing are tex_lod.h's, shared with detail_transfer.hip.
 // The file is compiled without floating-point contraction: every fp32 operation is the one the numpy restatement of the tests performs
 // (tests/texfetch_ref.py).  Wide LOADS only: all arithmetic is written per component (tests/test_no_packed_fp32.py).
 #include <hip/hip_runtime.h>
@@ -13,6 +13,7 @@
 #include "../../include/nero_hip_texfetch.h"
 #include "common.h"
 #include "tex_fetch_plan.h"
+#include "tex_lod.h"
 
 #pragma clang fp contract(off)
 
@@ -50,8 +51,6 @@ __global__ __launch_bounds__(THREADS) void tex_mip_kernel(const uint2* __restric
 }
 
 // ---- per-face texel density -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool in_range(int j, int64_t n) { return j >= 0 && (int64_t)j < n; }
-
 __global__ __launch_bounds__(THREADS) void tex_face_scale_kernel(const float* __restrict__ verts, int64_t V, const int* __restrict__ tris,
                                                                  const float* __restrict__ vt, int64_t Vt, const int* __restrict__ ft, int64_t T,
                                                                  float wf, float hf, float* __restrict__ scale) {
@@ -94,8 +93,6 @@ __device__ __forceinline__ Texel5 decode(const uint2 q, const float* lut) {
     return t;
 }
 
-__device__ __forceinline__ float lerp(float p, float q, float f) { return p + f * (q - p); }
-
 __device__ __forceinline__ Texel5 lerp5(const Texel5& p, const Texel5& q, float f) {
     Texel5 t;
     t.r = lerp(p.r, q.r, f);
@@ -106,39 +103,16 @@ __device__ __forceinline__ Texel5 lerp5(const Texel5& p, const Texel5& q, float 
     return t;
 }
 
-// where a coordinate falls in a level n texels wide: c = fminf(fmaxf(u n - 0.5, -1), n) (NaN -> -1), i0 = floorf(c) in [-1, n], f = c - i0
-struct Axis {
-    int i0;
-    float f;
-};
-
-__device__ __forceinline__ Axis axis_of(float u, int n) {
-    const float nf = (float)n;
-    const float c = fminf(fmaxf(u * nf - 0.5f, -1.0f), nf);                 // fmaxf and fminf return the other operand for a NaN
-    const float fl = floorf(c);
-    Axis a;
-    a.i0 = (int)fl;
-    a.f = c - fl;
-    return a;
-}
-
-__device__ __forceinline__ int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-// the bilinear fetch in level k; ax and ay (of that level) are returned for dbg
+// the bilinear fetch in level k (addresses: tex_lod.h); ax and ay (of that level) are returned for dbg
 __device__ __forceinline__ Texel5 bilinear(const uint2* __restrict__ pyr, const Plan& P, int k, float u, float v, const float* lut, Axis* ax_out,
                                            Axis* ay_out) {
-    const int wk = P.w[k], hk = P.h[k];
-    const Axis ax = axis_of(u, wk), ay = axis_of(v, hk);
-    const int x0 = clamp_index(ax.i0, wk), x1 = clamp_index(ax.i0 + 1, wk);  // in [0, w_k - 1]
-    const int y0 = clamp_index(ay.i0, hk), y1 = clamp_index(ay.i0 + 1, hk);  // in [0, h_k - 1]
-    const uint2* lvl = pyr + P.off[k];                                      // off[k] + y w_k + x < off[k] + h_k w_k <= records
-    const int64_t r0 = (int64_t)y0 * wk, r1 = (int64_t)y1 * wk;
-    const uint2 q00 = lvl[r0 + x0], q01 = lvl[r0 + x1], q10 = lvl[r1 + x0], q11 = lvl[r1 + x1];
-    const Texel5 top = lerp5(decode(q00, lut), decode(q01, lut), ax.f);
-    const Texel5 bot = lerp5(decode(q10, lut), decode(q11, lut), ax.f);
-    *ax_out = ax;
-    *ay_out = ay;
-    return lerp5(top, bot, ay.f);
+    const Taps t = taps_of(P, k, u, v);                                     // every record number lies below P.records
+    const uint2 q00 = pyr[t.r00], q01 = pyr[t.r01], q10 = pyr[t.r10], q11 = pyr[t.r11];
+    const Texel5 top = lerp5(decode(q00, lut), decode(q01, lut), t.ax.f);
+    const Texel5 bot = lerp5(decode(q10, lut), decode(q11, lut), t.ax.f);
+    *ax_out = t.ax;
+    *ay_out = t.ay;
+    return lerp5(top, bot, t.ay.f);
 }
 
 __device__ __forceinline__ void stage_lut(float* l_lut, const float* __restrict__ lut) {
@@ -183,14 +157,11 @@ __global__ __launch_bounds__(THREADS) void tex_materials_kernel(const uint2* __r
             for (int j = 0; j < 8; ++j) dbg[8 * i + j] = 0.0f;
         return;
     }
-    const float bu = bary[2 * i], bv = bary[2 * i + 1];
-    const float w0 = (1.0f - bu) - bv;
-    const float u = (w0 * vt[2 * (int64_t)j0] + bu * vt[2 * (int64_t)j1]) + bv * vt[2 * (int64_t)j2];
-    const float v = (w0 * vt[2 * (int64_t)j0 + 1] + bu * vt[2 * (int64_t)j1 + 1]) + bv * vt[2 * (int64_t)j2 + 1];
-    const float s = fmaxf(((depth[i] * spread) * scale[f]) * lod_scale, 1.0f);        // >= 1, or +inf; a NaN gives 1
-    const int e = (int)((__float_as_uint(s) >> 23) & 255u) - 127;                     // in [0, 128]
-    const int l = e < P.L - 1 ? e : P.L - 1;
-    const float t = l < P.L - 1 ? s * __uint_as_float((uint32_t)(127 - l) << 23) - 1.0f : 0.0f;   // l == e there: s 2^-l in [1, 2), exact
+    float u, v;
+    hit_uv(vt, j0, j1, j2, bary[2 * i], bary[2 * i + 1], &u, &v);
+    const Lod lod = lod_of(depth[i], spread, scale[f], lod_scale, P.L);
+    const int l = lod.l;
+    const float t = lod.t;
     Axis ax, ay, bx, by;
     Texel5 m = bilinear(pyr, P, l, u, v, l_lut, &ax, &ay);
     if (t != 0.0f) m = lerp5(m, bilinear(pyr, P, l + 1, u, v, l_lut, &bx, &by), t);   // l + 1 <= L - 1 where t != 0

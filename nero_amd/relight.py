@@ -396,10 +396,16 @@ class Relighter:
     camera's hits take their materials from the maps, filtered to the pixel's footprint (nero_amd/texfetch.py; DESIGN.md 9.12.4);
     lod_bias shifts the level of detail (+1: one level blurrier).  self.mat5 is then texfetch.vertex_materials: one level-0 fetch per
     vertex, which is what the bounce kernels shade the surface at a SECONDARY hit from -- an approximation: a bounce sees the maps at
-    the vertex spacing.  Without textures nothing changes."""
+    the vertex spacing.  Without textures nothing changes.
+    normal_map: None, or the dict nero_amd.transfer.bake_normal_map returns -- 'normal' uint8 [h,w,3], 'vt' [Vt,2], 'ft' [T,3], optional
+    'space' ('tangent', the default, or 'object') -- independent of textures: surface() perturbs its normal with the map (the fused
+    lookup of nero_amd/transfer.py, filtered to the pixel's footprint like the materials) just before normalising, so
+    the estimator and the denoiser's guides see the detailed normal.  A tangent-space map wants the frame it was baked in: pass the same
+    `normals` mode (the bake's result records it).  Secondary hits of bounces=1 keep the per-vertex normals: an approximation, like the
+    textures there.  Without normal_map nothing changes."""
 
     def __init__(self, verts, tris, materials, env, convention='blender', env_rotation=None, tracer=None, build='device',
-                 geometry_type='schlick', normals=None, device=None, bounces=0, textures=None, lod_bias=0.0):
+                 geometry_type='schlick', normals=None, device=None, bounces=0, textures=None, lod_bias=0.0, normal_map=None):
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         as_t = lambda a, dt: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
         self.device = dev
@@ -417,6 +423,15 @@ class Relighter:
         else:
             self.mat5 = torch.cat([as_t(materials[k], torch.float32).reshape(V, -1) for k in ('metallic', 'roughness', 'albedo')], -1)   # perceptual
         assert self.mat5.shape[1] == 5, self.mat5.shape
+        self.normal_map = None
+        if normal_map is not None:                                      # pyramid, texel density, tangents and signs: once
+            from . import texfetch, transfer
+            self.normal_map = transfer.NormalMap(normal_map['normal'], normal_map.get('space', 'tangent'), device=dev)
+            self.nm_vt, self.nm_ft = as_t(normal_map['vt'], torch.float32).reshape(-1, 2), as_t(normal_map['ft'], torch.int32).reshape(-1, 3)
+            if self.nm_ft.shape != self.tris.shape:
+                raise ValueError(f'normal_map: ft has {self.nm_ft.shape[0]} faces, the mesh {self.tris.shape[0]}')
+            self.nm_scale = texfetch.face_scale(self.verts, self.tris.int(), self.nm_vt, self.nm_ft, self.normal_map.h, self.normal_map.w)
+            self.nm_tangent, self.nm_sign = transfer.uv_tangents(self.verts, self.tris.int(), self.nm_vt, self.nm_ft)
         # 'angle' / 'area': smooth normals computed here, once, and stored OUTWARD whatever the winding (the bounce kernels read them at
         # secondary hits without turning them); where they fail (zero, not finite) surface() falls back to the flat normal
         self._computed_normals = isinstance(normals, str)
@@ -449,12 +464,20 @@ class Relighter:
     @classmethod
     def from_asset(cls, obj_path, env, **kw):
         """the textured asset write_textured_obj stored -- <name>.obj with its MTL and the three maps beside it -- under `env`; **kw: the
-        other arguments of Relighter"""
+        other arguments of Relighter.  When the MTL names a normal map it is passed on as normal_map (normal_map=None in kw: ignore it),
+        and `normals` then defaults to the frame mode the asset records ('angle' / 'area'; an asset baked with the caller's own normals
+        needs them again)"""
         from .texture import read_textured_obj
         asset = read_textured_obj(obj_path)
         missing = [k for k in ('albedo', 'metallic', 'roughness') if k not in asset]
         if missing:
             raise ValueError(f'{obj_path}: no {", ".join(missing)} map beside it (the MTL names {asset["map_Kd"]!r})')
+        if 'normal' in asset and 'normal_map' not in kw:
+            kw['normal_map'] = {'normal': asset['normal'], 'vt': asset['vt'], 'ft': asset['ft'], 'space': asset['normal_space']}
+            if asset['normal_frame'] in NORMAL_MODES:
+                kw.setdefault('normals', asset['normal_frame'])
+            elif asset['normal_space'] == 'tangent' and kw.get('normals') is None:
+                raise ValueError(f"{obj_path}: its normal map was baked in the frame of the caller's own normals: pass them as normals=")
         return cls(asset['v'], asset['f'], None, env, textures=asset, **kw)
 
     def light_table(self, clamp=None):
@@ -509,6 +532,10 @@ class Relighter:
                 good = torch.isfinite(smooth).all(-1, keepdim=True) & (smooth != 0).any(-1, keepdim=True)
                 smooth = torch.where(good, smooth, nrm)
             nrm = smooth
+        if self.normal_map is not None:
+            from . import transfer
+            nrm = transfer.apply_normal_map(self.normal_map, self.nm_vt, self.nm_ft, self.nm_scale, self.nm_tangent, self.nm_sign, face[idx],
+                                            bary[idx], depth[idx], nrm, spread, self.lod_bias)
         nrm = torch.nn.functional.normalize(nrm, dim=-1)
         return {'depth': depth, 'hit': hit, 'idx': idx, 'pts': pts, 'normal': nrm, 'mat5': mat5}
 

@@ -647,7 +647,10 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
     `f a/b` faces; <name>.mtl whose map_Kd names the albedo image; feat0_<cas>.png (albedo), feat1_<cas>.png (metallic), feat2_<cas>.png
     (roughness), the two scalar maps as three equal channels (COLOR_GRAY2BGR), image row 0 = texel row 0.  maps: the dict bake_materials
     returns.  When it holds 'ao' (bake_materials(..., ao={...})), feat3_<cas>.png (ambient occlusion, three equal channels) is written too
-    and the MTL names it in a map_Ka line; without 'ao' the files are what they were.  Differences from the reference: lossless PNG instead of
+    and the MTL names it in a map_Ka line; without 'ao' the files are what they were.  When it holds 'normal' (nero_amd.transfer.bake_normal_map / bake_asset), feat4_<cas>.png is
+    written and the MTL gains `norm feat4_<cas>.png` and the comment `# nero_normal_map space=<tangent|object> normals=<angle|area|custom>`
+    (maps['space'], maps['normals']: a tangent-space map means something only with the frame it was baked in); without 'normal' the
+    files are byte for byte what they were.  Differences from the reference: lossless PNG instead of
     JPEG.  -> the path of the OBJ."""
     os.makedirs(dir, exist_ok=True)
     v = _np(verts, np.float64).reshape(-1, 3)
@@ -662,6 +665,13 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
     keys = ('albedo', 'metallic', 'roughness')
     if 'ao' in maps:
         names, keys = names + [names[0].replace('feat0_', 'feat3_', 1)], keys + ('ao',)
+    norm_name = None
+    if 'normal' in maps:
+        space, frame = maps.get('space', 'tangent'), maps.get('normals', 'angle')
+        if space not in ('tangent', 'object') or frame not in ('angle', 'area', 'custom'):
+            raise ValueError(f"write_textured_obj: a normal map of space {space!r} and frame normals {frame!r}")
+        norm_name = names[0].replace('feat0_', 'feat4_', 1)
+        names, keys = names + [norm_name], keys + ('normal',)
     for fname, key in zip(names, keys):
         img = np.ascontiguousarray(_np(maps[key]), dtype=np.uint8)
         if img.ndim == 2:
@@ -680,13 +690,16 @@ def write_textured_obj(dir, verts, tris, vt, ft, maps, name='mesh_0', use_pil=No
         fh.write(f'newmtl defaultMat\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nTr 1\nillum 1\nNs 0\nmap_Kd {names[0]}\n')
         if 'ao' in maps:
             fh.write(f'map_Ka {names[3]}\n')
+        if norm_name is not None:
+            fh.write(f'norm {norm_name}\n# nero_normal_map space={space} normals={frame}\n')
     return obj
 
 
 def read_textured_obj(path, load_maps=True):
     """what write_textured_obj writes -> {'v' float64 [V,3], 'f' int64 [T,3], 'vt' float32 [Vt,2] (the file's 1 - v undone), 'ft' int64 [T,3],
     'mtllib', 'map_Kd', 'map_Ka' (only when the MTL has such a line), and with load_maps 'albedo' [h,w,3], 'metallic' [h,w], 'roughness' [h,w] and, when
-    the MTL has a map_Ka line, 'ao' [h,w] uint8 from the PNGs beside it}"""
+    the MTL has a map_Ka line, 'ao' [h,w] uint8 from the PNGs beside it; when the MTL has a `norm` line, 'norm' (the file name),
+    'normal_space', 'normal_frame' (from the nero_normal_map comment; 'tangent' and 'angle' without one) and with load_maps 'normal' [h,w,3]}"""
     lines = open(path).read().split('\n')
     pick = lambda key: [ln[len(key):] for ln in lines if ln.startswith(key)]
     v = np.array([x.split() for x in pick('v ')], dtype=np.float64).reshape(-1, 3)
@@ -704,6 +717,13 @@ def read_textured_obj(path, load_maps=True):
         ka = [ln.split(None, 1)[1].strip() for ln in mtl if ln.startswith('map_Ka ')]
         if ka:
             out['map_Ka'] = ka[0]
+        nm = [ln.split(None, 1)[1].strip() for ln in mtl if ln.startswith('norm ')]
+        if nm:
+            out['norm'] = nm[0]
+            note = dict(kv.split('=', 1) for ln in mtl if ln.startswith('# nero_normal_map ') for kv in ln.split()[2:] if '=' in kv)
+            out['normal_space'], out['normal_frame'] = note.get('space', 'tangent'), note.get('normals', 'angle')
+            if load_maps and os.path.exists(os.path.join(d, nm[0])):
+                out['normal'] = read_png(os.path.join(d, nm[0]))
     if load_maps and out['map_Kd'] and out['map_Kd'].startswith('feat0_'):
         for k, key in enumerate(('albedo', 'metallic', 'roughness')):
             p = os.path.join(d, f'feat{k}_' + out['map_Kd'][6:])

@@ -15,7 +15,17 @@ comes from the clean-up.  With `charts` the number of charts, the scale (texels 
 printed, a warning is given when any texel is covered twice, and the atlas is saved as <name>_atlas.npz next to the OBJ (vt, ft, vt_vertex,
 vt_chart, chart, rects, scale).  --ao-samples N (a power of two in [8, 1024]; 0, the default: no AO map) also bakes an ambient-occlusion map
 from N shadow rays per texel, no longer than --ao-radius (default: unbounded) and started --ao-bias above the surface; it is written as
-feat3_<cas>.png and named by a map_Ka line of the MTL."""
+feat3_<cas>.png and named by a map_Ka line of the MTL.
+
+    python scripts/extract_texture_maps.py --mesh dense.ply --ckpt model.pth --target-faces 100000 --atlas charts --normal-map --out out_dir
+
+--target-faces N (simplify the mesh to at most N faces first) or --low-mesh L.ply (a simplified mesh made elsewhere) bake the asset of the
+SIMPLIFIED mesh with nero_amd.transfer.bake_asset: every texel is projected onto the dense mesh, the networks are evaluated there, and the
+OBJ holds the simplified mesh.  --normal-map also writes the dense mesh's shading normals as feat4_<cas>.png (`norm` in the MTL, with the
+space and the frame mode in a comment): --normal-space tangent (the default) or object, --max-dist D bounds how far a texel may reach for
+the dense surface.  Without --uv the atlas is --atlas as above (--gutter applies to `charts`; `triangles`, the default, holds
+2 (size // 4)^2 faces and raises naming the smallest workable --size otherwise: 100 000 faces want --atlas charts).  --normal-map alone bakes on the mesh itself (a flat map).  A --uv atlas must then belong to the simplified mesh; no AO
+map is baked on this path."""
 import argparse
 import json
 import os
@@ -50,6 +60,11 @@ def main(argv=None):
     ap.add_argument('--ao-samples', type=int, default=0, help='shadow rays per texel of the ambient-occlusion map; 0: no AO map')
     ap.add_argument('--ao-radius', type=float, default=None, help='longest shadow ray (default: unbounded)')
     ap.add_argument('--ao-bias', type=float, default=1e-4, help='shadow rays start this far above the surface')
+    ap.add_argument('--target-faces', type=int, default=None, help='simplify the mesh to at most this many faces and bake the asset of that mesh')
+    ap.add_argument('--low-mesh', help='PLY of a simplified mesh to bake the asset of')
+    ap.add_argument('--normal-map', action='store_true', help="also bake the dense mesh's normals into a normal map")
+    ap.add_argument('--normal-space', choices=('tangent', 'object'), default='tangent')
+    ap.add_argument('--max-dist', type=float, default=None, help='how far a texel may reach for the dense surface (default: no limit)')
     ap.add_argument('--out', required=True)
     ap.add_argument('--name', default='mesh_0')
     args = ap.parse_args(argv)
@@ -72,6 +87,24 @@ def main(argv=None):
     if args.uv:
         z = np.load(args.uv)
         vt, ft = z['vt'], z['ft']
+    if args.target_faces is not None and args.low_mesh:
+        ap.error('give --target-faces or --low-mesh, not both')
+    if args.target_faces is not None or args.low_mesh or args.normal_map:
+        if args.ao_samples > 0:
+            ap.error('no ambient-occlusion map is baked on the transferred asset: drop --ao-samples')
+        from nero_amd import transfer
+        lv, lf = read_ply(args.low_mesh) if args.low_mesh else (None, None)
+        maps = transfer.bake_asset(net, verts=lv, tris=lf, target_faces=args.target_faces, vt=vt, ft=ft, size=args.size, ssaa=args.ssaa, pad=args.pad,
+                                   atlas=args.atlas, gutter=args.gutter, space=args.normal_space, max_dist=args.max_dist)
+        if not args.normal_map:
+            maps.pop('normal')
+        obj = TX.write_textured_obj(args.out, maps['verts'], maps['tris'], maps['vt'], maps['ft'], maps, name=args.name)
+        print(json.dumps({'obj': obj, 'size': args.size, 'ssaa': args.ssaa, 'pad': args.pad, 'source_triangles': int(len(f)),
+                          'triangles': int(maps['tris'].shape[0]), 'covered_texels': int(maps['mask'].sum()),
+                          'atlas': 'given' if args.uv else ('chart_atlas' if args.atlas == 'charts' else 'simple_atlas'),
+                          'normal_map': bool(args.normal_map), 'normal_space': args.normal_space, 'normals': maps['normals'],
+                          'unmatched': maps['unmatched'], 'max_moved': maps['max_moved'], 'max_dist': args.max_dist}))
+        return
     info = None
     if vt is None and args.atlas == 'charts':
         vt, ft, info = TX.chart_atlas(net.mesh_vertices, net.mesh_triangles, args.size, gutter=args.gutter)

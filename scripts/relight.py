@@ -7,7 +7,8 @@
 
 --textured: --mesh is the textured OBJ extract_texture_maps.py wrote, with its MTL and the albedo / metallic / roughness maps beside it; the
 materials are read from the maps at every hit, filtered to the pixel's footprint; --lod-bias B shifts the level of detail
-(+1: one level blurrier).  --material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
+(+1: one level blurrier).  When the asset has a normal map (extract_texture_maps.py --normal-map) it perturbs the shading normal at every hit
+ and --normals defaults to the frame the map was baked in; --no-normal-map ignores it.  --material DIR holds metallic.npy, roughness.npy, albedo.npy as extract_materials.py writes them (per vertex of --mesh); with --cfg/--model the
 materials are predicted from the trained Stage-II network instead.  --normals angle (or area) shades with smooth vertex normals computed
 from the mesh instead of flat face normals.  --denoise filters the picture's signals with the edge-aware denoiser
 (DESIGN.md 9.12.3).  Writes <out>/<name>/<k>.png, RGBA, one per view of the reference's orbit."""
@@ -46,8 +47,10 @@ def main(argv=None):
                     help="how the map is laid out: Blender's equirectangular image, or this project's env_light grid (is_real 0 / 1)")
     ap.add_argument('--bounces', type=int, default=0, choices=[0, 1],
                     help='1: a direction that meets the mesh fetches the light that surface sends back (one inter-reflection) instead of black')
-    ap.add_argument('--normals', default='flat', choices=['flat', 'angle', 'area'],
-                    help='flat: face normals; angle / area: smooth vertex normals computed from the mesh, face normals weighted by angle or by area')
+    ap.add_argument('--normals', default=None, choices=['flat', 'angle', 'area'],
+                    help='flat (the default): face normals; angle / area: smooth vertex normals computed from the mesh, face normals weighted by angle '
+                         "or by area.  With a textured asset that has a normal map the default is the frame the map records")
+    ap.add_argument('--no-normal-map', action='store_true', help="--textured: ignore the asset's normal map")
     ap.add_argument('--denoise', action='store_true',
                     help='filter the diffuse, specular and indirect signals with the edge-aware denoiser before they are summed (DESIGN.md 9.12.3): '
                          'fewer --samples for the same noise')
@@ -61,6 +64,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.lod_bias is not None and not a.textured:
         ap.error('--lod-bias needs --textured')
+    if a.no_normal_map and not a.textured:
+        ap.error('--no-normal-map needs --textured')
     if a.textured and (a.material or a.cfg or a.model):
         ap.error('--textured reads the materials from the maps: give no --material, --cfg or --model')
     denoise = None
@@ -106,7 +111,16 @@ def main(argv=None):
         ap.error('--samples takes one to three positive integers')
     samples = tuple(a.samples) if len(a.samples) == 3 else tuple((a.samples * 2)[:2])
     tex_kw = dict(textures=textures, lod_bias=a.lod_bias or 0.0) if a.textured else {}
-    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if a.normals == 'flat' else a.normals, **tex_kw)
+    normals = a.normals
+    if a.textured and 'normal' in textures and not a.no_normal_map:
+        tex_kw['normal_map'] = {'normal': textures['normal'], 'vt': textures['vt'], 'ft': textures['ft'], 'space': textures['normal_space']}
+        if normals is None and textures['normal_frame'] in ('angle', 'area'):
+            normals = textures['normal_frame']
+        elif textures['normal_frame'] not in ('angle', 'area') and textures['normal_space'] == 'tangent':
+            # (as Relighter.from_asset: the frame normals of such an asset are not in the file, and --normals cannot stand in for them)
+            raise SystemExit(f"{a.mesh}: its tangent-space normal map was baked in the frame of normals the asset does not hold "
+                             f"(normals={textures['normal_frame']}): relight it through Relighter.from_asset(..., normals=<those normals>), or pass --no-normal-map")
+    rl = Relighter(verts, tris, materials, a.hdr, convention=a.convention, normals=None if normals in (None, 'flat') else normals, **tex_kw)
     out_dir = os.path.join(a.out, a.name)
     paths = rl.render_orbit(out_dir, num=a.num, azimuth=a.azimuth, elevation=a.elevation, dist=a.cam_dist, h=a.height, w=a.width,
                             samples=samples, ssaa=a.ssaa, clamp=a.clamp, bounces=a.bounces, denoise=denoise)
